@@ -2,8 +2,14 @@
 """Headline benchmark: rank-r SVD GB/s on the ERA5 snapshot matrix + fp32 MFMA fraction.
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--workload cfg2|cfg3|cfg4|small]
-                    [--spectrum planted|powerlaw] [--no-hard-spectrum] [--no-cpu-baseline]
+                    [--spectrum planted|powerlaw] [--dump-outputs DIR]
+                    [--full [--no-hard-spectrum] [--no-cpu-baseline] [--no-calibrate]]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
+
+A plain run sets up, warms up, times the K steps, writes the outputs of the last timed step when
+--dump-outputs is given, and prints the line below without the fields marked [--full].  Those
+(per-launch and per-collective timing inside the timed region, the roofline, the stage split,
+calibration, CPU baseline, hard spectrum) take instrumentation or runs of their own: --full.
 
 Workloads (BASELINE.json `configs`), all synthetic on the device, row-centred
 with K5, held as row blocks of <= 131072 space points:
@@ -21,15 +27,17 @@ with K5, held as row blocks of <= 131072 space points:
 The default for --workload can also be set with DMDX_BENCH_WORKLOAD (the driver passes no flags).
 A step = one full SVD with X resident in HBM.
 
-Output: ONE JSON line on rank 0 (contract in the task statement) with
+Output: ONE JSON line on rank 0 with
   value          = rows of all ranks * n * 4 bytes * K / max-over-ranks wall      [GB/s]
-  roofline       = fp32-MFMA roofline of the Gram kernel (standard workloads): algorithmic flops
+  ms_per_step    = max-over-ranks wall of the K timed steps / K
+  outputs        = (--dump-outputs) the arrays written, see dump_outputs
+  roofline       = [--full] fp32-MFMA roofline of the Gram kernel (standard workloads): algorithmic flops
                    m*n*(n+1) per launch / average launch time measured with HIP events on the
                    launch stream inside the timed region; peak 157.3 TFLOP/s
-  hard_spectrum  = (N = 1, cfg2) the same step on the gap-free power-law matrix
+  hard_spectrum  = [--full] (N = 1, cfg2) the same step on the gap-free power-law matrix
                    (make_powerlaw_blocks), outside the timed region: ms per step and the share
                    of the eigen stage, which no longer depends on the spectrum
-  cpu_baseline   = (N = 1) the reference's two CPU calls, np.linalg.svd(...)[:r]
+  cpu_baseline   = [--full] (N = 1) the reference's two CPU calls, np.linalg.svd(...)[:r]
                    (era5_svd.py:251) and sklearn randomized_svd(X, r) (era5_svd.py:258), timed
                    on a bounded sample (8760 leading rows x every 2nd column: ~26 s; all columns
                    with --cpu-baseline-full: ~200 s) of the same X on the host cores, plus the HIP
@@ -300,6 +308,35 @@ def hard_spectrum(m: int, n: int, r: int, device, kern, steps: int = 2) -> dict:
     return out
 
 
+DUMP_BYTES = 60_000_000     # array bytes of one dump: the files stay under 64 MB
+
+
+def dump_outputs(res, out_dir: str) -> dict:
+    """Write what a caller of the timed step receives, from its last call, as `out_dir`/<name>.npy:
+    s (k,) and V = Vh^T (n, k) in float64, whole, and the left singular vectors of this rank's rows
+    in float32: U.npy (rows, k) when all of them fit in DUMP_BYTES, else U_sample.npy, the rows
+    drawn without replacement by np.random.RandomState(0) (in increasing order; the same rows for
+    the same workload), as many as fit.  Rank 0's rows are the leading rows of the global X."""
+    Ut = res.Ut.float()
+    s = res.s.double().cpu().numpy()
+    V = res.Vh.double().T.cpu().numpy()
+    k, rows = Ut.shape
+    fit = (DUMP_BYTES - s.nbytes - V.nbytes) // (4 * k)
+    if fit <= 0:
+        raise SystemExit(f"--dump-outputs: s and V alone exceed {DUMP_BYTES} bytes")
+    arrays = {"s": s, "V": V}
+    if rows <= fit:
+        arrays["U"] = Ut.T.cpu().numpy()
+    else:
+        pick = np.sort(np.random.RandomState(0).choice(rows, size=fit, replace=False))
+        idx = torch.from_numpy(pick).to(Ut.device)
+        arrays["U_sample"] = Ut.index_select(1, idx).T.cpu().numpy()
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), np.ascontiguousarray(a))
+    return {"dir": out_dir, "arrays": {name: {"shape": list(a.shape), "dtype": str(a.dtype)} for name, a in arrays.items()}}
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -309,6 +346,11 @@ def main():
     ap.add_argument("--rank", type=int, default=None, help="override the workload's rank (cfg4: 50 or 200)")
     ap.add_argument("--spectrum", default="planted", choices=["planted", "powerlaw"],
                     help="powerlaw: run the timed steps themselves on the gap-free matrix")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write s, V and (a seeded sample of) U of the last timed step as DIR/<name>.npy")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what the headline does not need: per-launch / per-collective timing, "
+                         "roofline, stage split, calibration, CPU baseline, hard spectrum")
     ap.add_argument("--no-hard-spectrum", action="store_true",
                     help="skip the extra power-law steps reported under `hard_spectrum` (N = 1, cfg2)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
@@ -318,6 +360,8 @@ def main():
     ap.add_argument("--no-calibrate", action="store_true",
                     help="skip the ~0.3 s on-box micro-benchmarks (register-only fp32 MFMA loop, HBM copy, K1 clock)")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
 
     world = int(os.environ.get("WORLD_SIZE", "1"))
     rank = int(os.environ.get("RANK", "0"))
@@ -406,45 +450,40 @@ def main():
     for _ in range(args.warmup):
         res = step()
     barrier()
-    # per-launch HIP events: ~20 launches per standard step (free); the randomized path issues
-    # thousands of launches per step, where recording them would be the thing measured
-    kern.events = [] if svd_type == "standard" else None
     issued = comm.n_collectives
-    if hasattr(comm, "start_timing"):
-        comm.start_timing()          # one HIP event pair per collective (6 per standard step)
-    # per step: a HIP event at its start / end on the launch stream (no host synchronisation) and
-    # the clock-probe counters of its stamped kernels (K1 / K2 / K3: three atomics per workgroup)
-    step_ev = [torch.cuda.Event(enable_timing=True) for _ in range(args.steps + 1)]
-    clk = torch.zeros((max(args.steps, 1), 3), dtype=torch.int64, device=device)
+    if args.full:
+        # per-launch HIP events: ~20 launches per standard step (free); the randomized path issues
+        # thousands of launches per step, where recording them would be the thing measured
+        kern.events = [] if svd_type == "standard" else None
+        if hasattr(comm, "start_timing"):
+            comm.start_timing()          # one HIP event pair per collective (6 per standard step)
+        # per step: a HIP event at its start / end on the launch stream (no host synchronisation) and
+        # the clock-probe counters of its stamped kernels (K1 / K2 / K3: three atomics per workgroup)
+        step_ev = [torch.cuda.Event(enable_timing=True) for _ in range(args.steps + 1)]
+        clk = torch.zeros((args.steps, 3), dtype=torch.int64, device=device)
     t0 = time.perf_counter()
     for i in range(args.steps):
-        step_ev[i].record()
-        kern.clock_probe(clk[i])
+        if args.full:
+            step_ev[i].record()
+            kern.clock_probe(clk[i])
         res = step()
-    step_ev[args.steps].record()
-    kern.clock_probe(None)
+    if args.full:
+        step_ev[args.steps].record()
+        kern.clock_probe(None)
     barrier()
     dt = time.perf_counter() - t0
-    issued = (comm.n_collectives - issued) / max(args.steps, 1)
-    coll = comm.stop_timing() if hasattr(comm, "stop_timing") else {}
-    events, kern.events = (kern.events or []), None
-    step_ms = [step_ev[i].elapsed_time(step_ev[i + 1]) for i in range(args.steps)]
-    step_clock = [100.0 * c / t if t > 0 else None for c, t, _ in clk.tolist()]
+    issued = (comm.n_collectives - issued) / args.steps
+    if args.full:
+        coll = comm.stop_timing() if hasattr(comm, "stop_timing") else {}
+        events, kern.events = (kern.events or []), None
+        step_ms = [step_ev[i].elapsed_time(step_ev[i + 1]) for i in range(args.steps)]
+        step_clock = [100.0 * c / t if t > 0 else None for c, t, _ in clk.tolist()]
     if dist is not None:
         tmax = torch.tensor([dt], dtype=torch.float64, device=device)
         dist.all_reduce(tmax, op=dist.ReduceOp.MAX)
         dt = float(tmax.item())
-
-    # per-kernel times from the HIP events recorded inside the timed region
-    # (the Gram of the row blocks is ONE launch of the batched K1, dmdx_syrk_blocks_f32,
-    # followed by its reduce kernel on the same stream; both are inside the event pair)
-    by_name: dict[str, list[float]] = {}
-    for name, shape, e0, e1 in events:
-        key = name
-        if name in ("syrk", "syrk_blocks"):
-            key = "syrk" if shape[1] == n else "syrk_small"
-        by_name.setdefault(key, []).append(e0.elapsed_time(e1))
-    nblk = len(blocks)
+    # before anything else runs: later calls may reuse the device buffers the result lives in
+    dumped = dump_outputs(res, args.dump_outputs) if args.dump_outputs and rank == 0 else None
 
     out = {
         "metric": "rank-r SVD GB/s on ERA5 snapshot matrix (X resident in HBM)",
@@ -468,107 +507,118 @@ def main():
         "world_size": world,
         "backend": backend,
         "collectives_per_step": issued,     # what this rank handed to torch.distributed inside the timed region
+        "devices": devices,
+        "row_blocks": len(blocks),
+        "svd_info": {k: (float(v) if isinstance(v, (int, float)) else v) for k, v in res.info.items()},
+        "s_head": [float(x) for x in res.s[:3].cpu()],
+    }
+    if dumped is not None:
+        out["outputs"] = dumped
+    if args.full:
         # wall time of this rank's collectives inside the timed region, per step, by kind (HIP events
         # around each call on the launch stream; gloo: host clock): so that a multi-GPU line explains itself
-        "collective_ms": {k: {"calls_per_step": v["calls"] / max(args.steps, 1), "ms_per_step": v["ms"] / max(args.steps, 1),
-                              "bytes_per_step": v["bytes"] / max(args.steps, 1)} for k, v in coll.items()},
-        "devices": devices,
-        "step_ms": step_ms,                 # every timed step (HIP events on the launch stream, rank 0)
-        "step_core_clock_mhz": step_clock,  # core clock held by the stamped kernels (K1 / K2 / K3) of each step
-    }
-    if svd_type == "standard":
-        syrk_ms = float(np.mean(by_name["syrk"]))            # average Gram launch (all row blocks of X)
-        flops = float(m) * n * (n + 1)                         # algorithmic flops of that launch
-        achieved = flops / (syrk_ms * 1e-3) / 1e12
-        # HBM-side traffic of the Gram kernel: PMC numbers cannot be collected from inside this
-        # process; they come from the committed rocprofv3 --pmc passes of this same command
-        # (profiles/r2_bench_rocprof_summary.json, else round 1's: FETCH_SIZE doubled per the gfx950
-        # note of MI355X_MICROARCH.md, plus WRITE_SIZE, per launch).
-        traffic, traffic_src = None, None
-        if args.workload == "cfg2" and args.spectrum == "planted":
-            for name in ("r3_bench_rocprof_summary.json", "r2_bench_rocprof_summary.json", "r1_bench_rocprof_summary.json"):
-                try:
-                    with open(os.path.join(ROOT, "profiles", name)) as f:
-                        traffic = float(json.load(f)["traffic"]["bytes_per_launch_corrected"])
-                    traffic_src = name
-                    break
-                except Exception:
-                    continue
-        per_launch = [float(x) for x in by_name["syrk"]]      # one Gram launch per timed step, in order
-        fr = [flops / (x * 1e-3) / 1e12 / PEAK_FP32_MFMA_TFLOPS for x in per_launch]
-        nf = min(5, len(fr))
-        clocks = [c for c in step_clock if c]
-        out["roofline"] = {
-            "bound": "mfma",
-            "kernel": "syrk_batch_kernel (K1 Gram of all row blocks in one launch, dmdx_syrk_blocks_f32)",
-            "achieved": achieved,
-            "peak": PEAK_FP32_MFMA_TFLOPS,
-            "unit": "TFLOP/s",
-            "frac": achieved / PEAK_FP32_MFMA_TFLOPS,
-            "traffic": traffic,
-            "traffic_unit": f"bytes/launch (L2<->fabric, PMC; profiles/{traffic_src})" if traffic_src else None,
-            "flops_per_launch": flops,
-            "ms_per_launch": syrk_ms,
-            # what the kernel SUSTAINS: `frac` is the mean over the timed steps; the chip warms up over
-            # the first ~20 steps (it gives clock back), so a long run ends lower than it starts
-            "frac_first5": float(np.mean(fr[:nf])), "frac_last5": float(np.mean(fr[-nf:])),
-            "frac_min": float(min(fr)), "frac_max": float(max(fr)),
-            "core_clock_mhz_first5": float(np.mean(clocks[:nf])) if clocks else None,
-            "core_clock_mhz_last5": float(np.mean(clocks[-nf:])) if clocks else None,
-            # the same launches priced at the clock the chip actually held (nominal: 2400 MHz)
-            "frac_at_held_clock": float(np.mean([f * 2400.0 / c for f, c in zip(fr, step_clock) if c])) if clocks else None,
-        }
-    else:
-        # randomized: 2 n_iter + 2 = 6 passes over X of 2 m n l flops each (K2 / K3 alternate); the
-        # per-kernel split lives in profiles/ (rocprofv3 --kernel-trace of scripts/bench_cfg4.py)
-        l = r + 20
-        flops = 6 * 2.0 * m * n * l
-        out["roofline"] = {"bound": "mfma", "kernel": "K2 skinny16 (Y = X Q, fused Gram) + K3 gemm_tn (Z = X^T Y), 6 passes over X",
-                           "achieved": flops * args.steps / dt / 1e12, "peak": PEAK_FP32_MFMA_TFLOPS,
-                           "unit": "TFLOP/s", "frac": flops * args.steps / dt / 1e12 / PEAK_FP32_MFMA_TFLOPS,
-                           "traffic": None, "flops_per_step": flops,
-                           "note": "whole-step algorithmic rate of ONE rank's shard (per GPU; no per-launch "
-                                   "events in the timed region)"}
-        # the phases of one more step, outside the timed region (every phase boundary synchronises)
-        ph = dsvd.svd_randomized(blocks, r, n_oversamples=20, n_iter=2, random_state=0, comm=comm, kern=kern, timings=True).info
-        out["stage_ms"] = {k: float(v) for k, v in ph.get("phase_ms", {}).items()}
-        out["stage_ms"]["total"] = float(ph["t_total"]) * 1e3
-    if svd_type == "standard":
-        # stage split of one more step, outside the timed region (the stage timers synchronise)
-        # (the minimum of three calls per stage: a single call once showed a 41 ms `refine` on the
-        # driver's box where every other run has 2.3 ms -- a 208 MB allocation served by the driver
-        # instead of the caching allocator; all three calls are listed)
-        sts = [dsvd.svd_snapshots(blocks, r, comm=comm, kern=kern, timings=True).info for _ in range(3)]
-        keys = ["t_gram", "t_eig", "t_project", "t_refine", "t_total"] + (["t_polish"] if "t_polish" in sts[0] else [])
-        out["stage_ms"] = {k[2:]: float(min(st[k] for st in sts)) * 1e3 for k in keys}
-        out["stage_ms_calls"] = [{k[2:]: float(st[k]) * 1e3 for k in keys} for st in sts]
-    out["kernel_ms_per_step"] = {k: float(np.sum(v)) / args.steps for k, v in by_name.items()}
-    out["row_blocks"] = nblk
-    out["svd_info"] = {k: (float(v) if isinstance(v, (int, float)) else v)
-                       for k, v in (res.info if res is not None else {}).items()}
-    out["s_head"] = [float(x) for x in res.s[:3].cpu()] if res is not None else None
-    if rank == 0 and world == 1 and not args.no_calibrate:
-        out["calibration"] = calibrate(device, kern, blocks if svd_type == "standard" else None)
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
-        out["cpu_baseline"] = cpu_baseline(blocks[0], r, kern, args.cpu_baseline_rows, m, args.cpu_baseline_full)
-        # The full-width sample SURVEY.md 8(d) asks for (all n columns: 17520 x 8760 at cfg2) costs ~7.4 x
-        # the half-width one (203.8 s against 27.8 s on the 128-thread box).  The default run has to
-        # end within minutes and its CPU leg is meant to be 10-30 s of work, so the full-width sample
-        # is taken by default only when the half-width timing predicts <= 2 minutes for it (a faster
-        # host than the 128-thread boxes seen so far); `--cpu-baseline-full` (or
-        # DMDX_BENCH_CPU_FULL=2) takes it regardless -- profiles/r2_bench_cpu_full.json is such a run.
-        half = out["cpu_baseline"]
-        if (not args.cpu_baseline_full and args.workload == "cfg2" and os.environ.get("DMDX_BENCH_CPU_FULL", "1") != "0"
-                and args.cpu_baseline_rows is None
-                and (7.5 * half["seconds"] <= 120.0 or os.environ.get("DMDX_BENCH_CPU_FULL") == "2")):
-            full = cpu_baseline(blocks[0], r, kern, None, m, True)
-            full["half_width_sample"] = {k: half[k] for k in ("value", "seconds", "sample", "parity", "randomized") if k in half}
-            out["cpu_baseline"] = full
-    if rank == 0 and world == 1 and not args.no_hard_spectrum and args.workload == "cfg2" and args.spectrum == "planted":
-        del blocks
-        kern.release_workspace()
-        torch.cuda.empty_cache()
-        out["hard_spectrum"] = hard_spectrum(m, n, r, device, kern)
+        out["collective_ms"] = {k: {"calls_per_step": v["calls"] / args.steps, "ms_per_step": v["ms"] / args.steps,
+                                    "bytes_per_step": v["bytes"] / args.steps} for k, v in coll.items()}
+        out["step_ms"] = step_ms                 # every timed step (HIP events on the launch stream, rank 0)
+        out["step_core_clock_mhz"] = step_clock  # core clock held by the stamped kernels (K1 / K2 / K3) of each step
+        # per-kernel times from the HIP events recorded inside the timed region
+        # (the Gram of the row blocks is ONE launch of the batched K1, dmdx_syrk_blocks_f32,
+        # followed by its reduce kernel on the same stream; both are inside the event pair)
+        by_name: dict[str, list[float]] = {}
+        for name, shape, e0, e1 in events:
+            key = name
+            if name in ("syrk", "syrk_blocks"):
+                key = "syrk" if shape[1] == n else "syrk_small"
+            by_name.setdefault(key, []).append(e0.elapsed_time(e1))
+        if svd_type == "standard":
+            syrk_ms = float(np.mean(by_name["syrk"]))            # average Gram launch (all row blocks of X)
+            flops = float(m) * n * (n + 1)                         # algorithmic flops of that launch
+            achieved = flops / (syrk_ms * 1e-3) / 1e12
+            # HBM-side traffic of the Gram kernel: PMC numbers cannot be collected from inside this
+            # process; they come from the committed rocprofv3 --pmc passes of this same command
+            # (profiles/r2_bench_rocprof_summary.json, else round 1's: FETCH_SIZE doubled per the gfx950
+            # note of MI355X_MICROARCH.md, plus WRITE_SIZE, per launch).
+            traffic, traffic_src = None, None
+            if args.workload == "cfg2" and args.spectrum == "planted":
+                for name in ("r3_bench_rocprof_summary.json", "r2_bench_rocprof_summary.json", "r1_bench_rocprof_summary.json"):
+                    try:
+                        with open(os.path.join(ROOT, "profiles", name)) as f:
+                            traffic = float(json.load(f)["traffic"]["bytes_per_launch_corrected"])
+                        traffic_src = name
+                        break
+                    except Exception:
+                        continue
+            per_launch = [float(x) for x in by_name["syrk"]]      # one Gram launch per timed step, in order
+            fr = [flops / (x * 1e-3) / 1e12 / PEAK_FP32_MFMA_TFLOPS for x in per_launch]
+            nf = min(5, len(fr))
+            clocks = [c for c in step_clock if c]
+            out["roofline"] = {
+                "bound": "mfma",
+                "kernel": "syrk_batch_kernel (K1 Gram of all row blocks in one launch, dmdx_syrk_blocks_f32)",
+                "achieved": achieved,
+                "peak": PEAK_FP32_MFMA_TFLOPS,
+                "unit": "TFLOP/s",
+                "frac": achieved / PEAK_FP32_MFMA_TFLOPS,
+                "traffic": traffic,
+                "traffic_unit": f"bytes/launch (L2<->fabric, PMC; profiles/{traffic_src})" if traffic_src else None,
+                "flops_per_launch": flops,
+                "ms_per_launch": syrk_ms,
+                # what the kernel SUSTAINS: `frac` is the mean over the timed steps; the chip warms up over
+                # the first ~20 steps (it gives clock back), so a long run ends lower than it starts
+                "frac_first5": float(np.mean(fr[:nf])), "frac_last5": float(np.mean(fr[-nf:])),
+                "frac_min": float(min(fr)), "frac_max": float(max(fr)),
+                "core_clock_mhz_first5": float(np.mean(clocks[:nf])) if clocks else None,
+                "core_clock_mhz_last5": float(np.mean(clocks[-nf:])) if clocks else None,
+                # the same launches priced at the clock the chip actually held (nominal: 2400 MHz)
+                "frac_at_held_clock": float(np.mean([f * 2400.0 / c for f, c in zip(fr, step_clock) if c])) if clocks else None,
+            }
+        else:
+            # randomized: 2 n_iter + 2 = 6 passes over X of 2 m n l flops each (K2 / K3 alternate); the
+            # per-kernel split lives in profiles/ (rocprofv3 --kernel-trace of scripts/bench_cfg4.py)
+            l = r + 20
+            flops = 6 * 2.0 * m * n * l
+            out["roofline"] = {"bound": "mfma", "kernel": "K2 skinny16 (Y = X Q, fused Gram) + K3 gemm_tn (Z = X^T Y), 6 passes over X",
+                               "achieved": flops * args.steps / dt / 1e12, "peak": PEAK_FP32_MFMA_TFLOPS,
+                               "unit": "TFLOP/s", "frac": flops * args.steps / dt / 1e12 / PEAK_FP32_MFMA_TFLOPS,
+                               "traffic": None, "flops_per_step": flops,
+                               "note": "whole-step algorithmic rate of ONE rank's shard (per GPU; no per-launch "
+                                       "events in the timed region)"}
+            # the phases of one more step, outside the timed region (every phase boundary synchronises)
+            ph = dsvd.svd_randomized(blocks, r, n_oversamples=20, n_iter=2, random_state=0, comm=comm, kern=kern, timings=True).info
+            out["stage_ms"] = {k: float(v) for k, v in ph.get("phase_ms", {}).items()}
+            out["stage_ms"]["total"] = float(ph["t_total"]) * 1e3
+        if svd_type == "standard":
+            # stage split of one more step, outside the timed region (the stage timers synchronise)
+            # (the minimum of three calls per stage: a single call once showed a 41 ms `refine` on one
+            # machine where every other run has 2.3 ms -- a 208 MB allocation served by the driver
+            # instead of the caching allocator; all three calls are listed)
+            sts = [dsvd.svd_snapshots(blocks, r, comm=comm, kern=kern, timings=True).info for _ in range(3)]
+            keys = ["t_gram", "t_eig", "t_project", "t_refine", "t_total"] + (["t_polish"] if "t_polish" in sts[0] else [])
+            out["stage_ms"] = {k[2:]: float(min(st[k] for st in sts)) * 1e3 for k in keys}
+            out["stage_ms_calls"] = [{k[2:]: float(st[k]) * 1e3 for k in keys} for st in sts]
+        out["kernel_ms_per_step"] = {k: float(np.sum(v)) / args.steps for k, v in by_name.items()}
+        if rank == 0 and world == 1 and not args.no_calibrate:
+            out["calibration"] = calibrate(device, kern, blocks if svd_type == "standard" else None)
+        if rank == 0 and world == 1 and not args.no_cpu_baseline:
+            out["cpu_baseline"] = cpu_baseline(blocks[0], r, kern, args.cpu_baseline_rows, m, args.cpu_baseline_full)
+            # The full-width sample SURVEY.md 8(d) asks for (all n columns: 17520 x 8760 at cfg2) costs ~7.4 x
+            # the half-width one (203.8 s against 27.8 s on a 128-thread host).  A --full run has to
+            # end within minutes and its CPU leg is meant to be 10-30 s of work, so the full-width sample
+            # is taken by default only when the half-width timing predicts <= 2 minutes for it (a faster
+            # host than the 128-thread ones seen so far); `--cpu-baseline-full` (or
+            # DMDX_BENCH_CPU_FULL=2) takes it regardless -- profiles/r2_bench_cpu_full.json is such a run.
+            half = out["cpu_baseline"]
+            if (not args.cpu_baseline_full and args.workload == "cfg2" and os.environ.get("DMDX_BENCH_CPU_FULL", "1") != "0"
+                    and args.cpu_baseline_rows is None
+                    and (7.5 * half["seconds"] <= 120.0 or os.environ.get("DMDX_BENCH_CPU_FULL") == "2")):
+                full = cpu_baseline(blocks[0], r, kern, None, m, True)
+                full["half_width_sample"] = {k: half[k] for k in ("value", "seconds", "sample", "parity", "randomized") if k in half}
+                out["cpu_baseline"] = full
+        if rank == 0 and world == 1 and not args.no_hard_spectrum and args.workload == "cfg2" and args.spectrum == "planted":
+            del blocks
+            kern.release_workspace()
+            torch.cuda.empty_cache()
+            out["hard_spectrum"] = hard_spectrum(m, n, r, device, kern)
     if rank == 0:
         print(json.dumps(out), flush=True)
     if dist is not None:

@@ -1,5 +1,5 @@
-import numpy as np, sys, traceback, torch
-sys.path.insert(0, "/root/repo")
+import numpy as np, os, sys, traceback, torch
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from dmd_era5_amd import svd as dsvd
 from dmd_era5_amd.kernels import default_kernels
 K = default_kernels()

@@ -1,7 +1,9 @@
-import numpy as np, torch, sys
-sys.path.insert(0, "/root/repo")
+import numpy as np, os, torch, sys
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path[:0] = [ROOT, os.path.join(ROOT, "tests")]
 from dmd_era5_amd.engine import svd_numpy
-g = np.load("/root/repo/tests/golden/conditioning_2048x160.npz")
+from parity_utils import load_golden
+g = load_golden(os.path.join(ROOT, "tests", "golden"), "conditioning_2048x160")
 for tag in ("raw", "cen"):
     X = g[f"{tag}_X"]; k = int(g["k"])
     for typ in ("standard", "randomized"):

@@ -17,10 +17,12 @@ The reference package itself is not importable here (xarray/netCDF4/pyprojroot/d
 are not installed: ordinary ModuleNotFoundError), so SVD values are pinned on the
 third-party calls it makes, not on reference fixtures (it holds none: "parity
 unpinned" by reference tests).
-  * conditioning_2048x160.npz -- temperature-like data with and without its time mean (the
+  * conditioning_2048x160 -- temperature-like data with and without its time mean (the
     un-centred matrix has s_1 ~ 3e3 s_2): fp32 and fp64 `np.linalg.svd` of both, the inputs included.
 Vectors are stored sign-normalised (largest |entry| of each U column positive).
+The two larger fixtures are written in pieces (save_parts) and read with tests/parity_utils.load_golden.
 """
+import glob
 import os
 import sys
 
@@ -30,6 +32,33 @@ from sklearn.utils.extmath import randomized_svd
 HERE = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, os.path.join(HERE, "..", ".."))
 from oracle import era5_oracle as orc  # noqa: E402
+
+PART_BYTES = 900_000   # array bytes per piece: every committed file stays under 1 MiB
+
+
+def save_parts(stem, arrays):
+    """np.savez_compressed of `arrays` as <stem>.part<i>.npz pieces of at most PART_BYTES of data;
+    an array larger than PART_BYTES / 2 is cut by rows into <key>__<j>."""
+    items = []
+    for key, a in arrays.items():
+        a = np.asarray(a)
+        if a.nbytes > PART_BYTES // 2:
+            nrow = max(1, (PART_BYTES // 2) // (a.nbytes // a.shape[0]))
+            items += [(f"{key}__{j}", a[r:r + nrow]) for j, r in enumerate(range(0, a.shape[0], nrow))]
+        else:
+            items.append((key, a))
+    parts, cur, size = [], {}, 0
+    for key, a in items:
+        if cur and size + a.nbytes > PART_BYTES:
+            parts.append(cur)
+            cur, size = {}, 0
+        cur[key] = a
+        size += a.nbytes
+    parts.append(cur)
+    for old in glob.glob(stem + ".part*.npz"):
+        os.remove(old)
+    for i, part in enumerate(parts):
+        np.savez_compressed(f"{stem}.part{i}.npz", **part)
 
 
 def main():
@@ -80,7 +109,7 @@ def main():
             assert np.allclose(so, sr, rtol=1e-5), (so, sr)
             out.update({f"{tag}_s": sr, f"{tag}_U": Ur, f"{tag}_V": Vr,
                         f"{tag}_omega": omega.astype(np.float32)})
-        np.savez_compressed(os.path.join(HERE, name + ".npz"), **out)
+        save_parts(os.path.join(HERE, name), out)
     # 4. conditioning pair: the same anomalies with and without a large
     # time-mean (temperature-like: 280 + O(1..10) anomalies).  Un-centred, s_1 is ~3e3 x s_2, which
     # is what stresses a Gram-based SVD; centred, it is the well-conditioned problem.
@@ -96,7 +125,7 @@ def main():
         U64, V64 = orc.svd_flip(U64, V64)
         out.update({f"{tag}_X": X, f"{tag}_s32": s32, f"{tag}_s64": s64,
                     f"{tag}_U64": U64.astype(np.float32), f"{tag}_V64": V64.astype(np.float32)})
-    np.savez_compressed(os.path.join(HERE, "conditioning_2048x160.npz"), **out)
+    save_parts(os.path.join(HERE, "conditioning_2048x160"), out)
     print("golden fixtures written to", HERE)
 
 

@@ -1,4 +1,8 @@
-"""Comparison rules for SVD factors (sign ambiguity, gaps) used by the tests."""
+"""Comparison rules for SVD factors (sign ambiguity, gaps) used by the tests, and the golden
+fixture loader."""
+import glob
+import os
+
 import numpy as np
 
 EPS32 = float(np.finfo(np.float32).eps)
@@ -34,3 +38,23 @@ def vec_tolerance(s_ref, c=64.0):
             g.append(s2[i] - s2[i + 1])
         gap[i] = max(min(g), 1e-300) if g else s2[i]
     return c * EPS32 * s2[0] / gap
+
+
+def load_golden(golden_dir, name):
+    """The arrays of golden fixture `name`: <name>.npz, or the pieces <name>.part<i>.npz that
+    tests/golden/make_golden.py writes so that no committed file exceeds 1 MiB (an array cut by
+    rows is stored as <key>__<j> and comes back whole)."""
+    paths = sorted(glob.glob(os.path.join(golden_dir, name + ".part*.npz")),
+                   key=lambda p: int(p[len(os.path.join(golden_dir, name + ".part")):-len(".npz")]))
+    out, cut = {}, {}
+    for path in paths or [os.path.join(golden_dir, name + ".npz")]:
+        with np.load(path) as g:
+            for key in g.files:
+                base, sep, j = key.rpartition("__")
+                if sep and j.isdigit():
+                    cut.setdefault(base, {})[int(j)] = g[key]
+                else:
+                    out[key] = g[key]
+    for base, pieces in cut.items():
+        out[base] = np.concatenate([pieces[j] for j in sorted(pieces)])
+    return out

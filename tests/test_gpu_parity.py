@@ -9,7 +9,7 @@ import pytest
 import torch
 
 from oracle import era5_oracle as orc
-from parity_utils import EPS32, col_cosines, sv_tolerance
+from parity_utils import EPS32, col_cosines, load_golden, sv_tolerance
 
 pytestmark = pytest.mark.gpu
 
@@ -226,7 +226,7 @@ def _check_against(U, s, V, Uref, sref, Vref, s_tol, cos_min):
 def test_standard_svd_matches_numpy_golden(refine):
     from dmd_era5_amd.engine import svd_numpy
 
-    g = np.load(os.path.join(GOLDEN, "lowrank_4096x192.npz"))
+    g = load_golden(GOLDEN, "lowrank_4096x192")
     X = orc.lowrank_matrix(4096, 192, 100, 0)
     U, s, V = svd_numpy(X, "standard", 50, refine=refine)
     assert U.shape == (4096, 50) and s.shape == (50,) and V.shape == (50, 192)
@@ -259,7 +259,7 @@ def test_standard_svd_cfg1_mock_slice():
 def test_randomized_svd_matches_sklearn_golden():
     from dmd_era5_amd.engine import svd_numpy
 
-    g = np.load(os.path.join(GOLDEN, "lowrank_4096x192.npz"))
+    g = load_golden(GOLDEN, "lowrank_4096x192")
     X = orc.lowrank_matrix(4096, 192, 100, 0)
     U, s, V = svd_numpy(X, "randomized", 50, random_state=0)     # reference defaults
     # same Omega, same subspaces; normaliser differs (CholeskyQR vs LU) -> rounding-level
@@ -864,7 +864,7 @@ def test_uncentred_temperature_like_data_matches_numpy_fp64():
     relative on every singular value against numpy fp64 (numpy's own fp32 LAPACK: 6e-8)."""
     from dmd_era5_amd.engine import svd_numpy
 
-    g = np.load(os.path.join(GOLDEN, "conditioning_2048x160.npz"))
+    g = load_golden(GOLDEN, "conditioning_2048x160")
     k = int(g["k"])
     for tag in ("raw", "cen"):
         U, s, V = svd_numpy(g[f"{tag}_X"], "standard", k, device="cuda:0")

@@ -452,7 +452,7 @@ def test_bench_two_ranks_on_one_gpu_over_gloo(workload, ranks):
     run = subprocess.run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", str(w),
                           "--master-addr", "127.0.0.1", "--master-port", str(port),
                           os.path.join(root, "bench.py"), "--gpus", str(w), "--steps", "2", "--warmup", "1",
-                          "--no-cpu-baseline", "--no-calibrate"] + extra,
+                          "--full", "--no-cpu-baseline", "--no-calibrate"] + extra,
                          env=env, capture_output=True, text=True, timeout=600, cwd=root)
     assert run.returncode == 0, run.stdout[-3000:] + run.stderr[-3000:]
     lines = [ln for ln in run.stdout.splitlines() if ln.startswith("{")]
@@ -480,6 +480,48 @@ def test_bench_two_ranks_on_one_gpu_over_gloo(workload, ranks):
         assert out["roofline"]["bound"] == "mfma" and out["roofline"]["frac"] > 0
         if w >= 2:
             assert "one packed-triangle Gram all-reduce" in out["config"]["sharding"]
+
+
+def test_bench_plain_run_is_lean_and_dumps_the_same_outputs_twice(tmp_path):
+    """A plain bench.py run prints the headline fields and none of what --full measures; with
+    --dump-outputs it writes the SVD of its last timed step, and a second run with the same
+    arguments writes the same one (the inputs are seeded)."""
+    import json
+    import os
+    import subprocess
+    import sys
+
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    runs = []
+    for tag in ("a", "b"):
+        run = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--steps", "3",
+                              "--warmup", "1", "--workload", "small", "--dump-outputs", str(tmp_path / tag)],
+                             capture_output=True, text=True, timeout=600, cwd=root)
+        assert run.returncode == 0, run.stdout[-3000:] + run.stderr[-3000:]
+        lines = [ln for ln in run.stdout.splitlines() if ln.startswith("{")]
+        assert len(lines) == 1, run.stdout[-2000:]
+        runs.append(json.loads(lines[0]))
+    out = runs[0]
+    assert out["steps"] == 3 and out["warmup"] == 1 and out["unit"] == "GB/s" and out["higher_is_better"] is True
+    assert out["dtype"] == "f32" and out["metric"] and out["ms_per_step"] > 0
+    m, n = out["config"]["m_total"], out["config"]["n"]
+    assert abs(out["value"] * out["ms_per_step"] / (m * n * 4.0 / 1e6) - 1) < 1e-9
+    for key in ("roofline", "step_ms", "collective_ms", "stage_ms", "kernel_ms_per_step", "calibration",
+                "cpu_baseline", "hard_spectrum"):
+        assert key not in out, key
+    assert sorted(out["outputs"]["arrays"]) == ["U", "V", "s"]
+    k = out["config"]["rank"]
+    s, V, U = (np.load(tmp_path / "a" / f"{a}.npy") for a in ("s", "V", "U"))
+    assert s.shape == (k,) and V.shape == (n, k) and U.shape == (m, k)
+    assert s.dtype == V.dtype == np.float64 and U.dtype == np.float32
+    assert np.array_equal(s[:3], np.array(out["s_head"]))
+    planted = 100.0 * 0.9 ** np.arange(3) * np.sqrt(float(m) * n)
+    assert np.all(np.abs(s[:3] / planted - 1.0) < 0.05)
+    assert np.abs(V.T @ V - np.eye(k)).max() < 1e-6
+    assert np.abs(U.T.astype(np.float64) @ U - np.eye(k)).max() < 1e-3
+    s2, V2, U2 = (np.load(tmp_path / "b" / f"{a}.npy") for a in ("s", "V", "U"))
+    assert np.allclose(s2, s, rtol=1e-6, atol=0)
+    assert col_cosines(U2, U).min() > 1 - 1e-5 and col_cosines(V2, V).min() > 1 - 1e-5
 
 
 @pytest.mark.parametrize("svd_type,center,scale,d", [("standard", True, False, 2), ("standard", True, True, 1),

@@ -12,7 +12,7 @@ import torch.multiprocessing as mp
 
 from kernel_double import CpuKernelDouble
 from oracle import era5_oracle as orc
-from parity_utils import col_cosines, sv_tolerance
+from parity_utils import col_cosines, load_golden, sv_tolerance
 
 from dmd_era5_amd import svd as dsvd
 
@@ -25,7 +25,7 @@ def _xt(X):
 
 
 def test_snapshots_matches_golden():
-    g = np.load(os.path.join(GOLDEN, "lowrank_4096x192.npz"))
+    g = load_golden(GOLDEN, "lowrank_4096x192")
     X = orc.lowrank_matrix(4096, 192, 100, 0)
     for refine in (True, False):
         r = dsvd.svd_snapshots(_xt(X), 50, refine=refine, kern=K)
@@ -163,7 +163,7 @@ def test_graded_refinement_matrix_keeps_relative_accuracy_without_the_jacobi_ker
 
 
 def test_randomized_same_omega_as_sklearn():
-    g = np.load(os.path.join(GOLDEN, "lowrank_4096x192.npz"))
+    g = load_golden(GOLDEN, "lowrank_4096x192")
     X = orc.lowrank_matrix(4096, 192, 100, 0)
     r = dsvd.svd_randomized(_xt(X), 50, random_state=0, kern=K)
     assert r.info["n_iter"] == 4 and r.info["l"] == 60
@@ -298,7 +298,7 @@ def test_uncentred_data_takes_the_mean_deflated_route():
     """Temperature-like data with its time mean left in (s_1 ~ 3e4 s_2): the engine detects the
     dominant mean and deflates it exactly (centred Gram + Schur complement of the mean
     direction); the result is the SVD of the UN-centred matrix (golden: numpy fp64), and the caller's X is left untouched."""
-    g = np.load(os.path.join(GOLDEN, "conditioning_2048x160.npz"))
+    g = load_golden(GOLDEN, "conditioning_2048x160")
     k = int(g["k"])
     for tag, expect in (("raw", True), ("cen", False)):
         X = g[f"{tag}_X"]
@@ -321,7 +321,7 @@ def test_uncentred_data_with_delay_embedding(d):
     the centred data plus (tiled mean) 1^T; the ones vector is no longer in the null space of the
     centred Gram (window sums of a centred series are small, not zero), which the projected form
     P A^T A P handles exactly.  Truth: numpy fp64 SVD of the materialised embedding."""
-    g = np.load(os.path.join(GOLDEN, "conditioning_2048x160.npz"))
+    g = load_golden(GOLDEN, "conditioning_2048x160")
     X = g["raw_X"][:600]
     Xe = orc.delay_embed(X, d)
     Ue, se, Ve = orc.svd_standard(Xe.astype(np.float64), 8)
@@ -440,6 +440,40 @@ def test_powerlaw_generator_has_the_spectrum_it_claims():
     # one global matrix: stacking the shards keeps the spectrum (x sqrt(2)), it does not double the rank
     s2 = np.linalg.svd(np.concatenate([X, Y]), compute_uv=False)
     assert np.all(np.abs(s2 / (expect * np.sqrt(2)) - 1) < 3.5 * np.sqrt(n / m))
+
+
+def test_bench_dump_outputs_writes_the_result_within_its_budget(tmp_path, monkeypatch):
+    """bench.dump_outputs (--dump-outputs): s and V whole in float64, U whole in float32 while it
+    fits the byte budget, else the same seeded rows of it every time, and never more than the budget."""
+    import bench
+
+    k, n, rows = 4, 30, 5000
+    rng = np.random.RandomState(1)
+    res = dsvd.SvdResult(Ut=torch.from_numpy(rng.standard_normal((k, rows)).astype(np.float32)),
+                         s=torch.from_numpy(np.sort(rng.random_sample(k))[::-1].copy()),
+                         Vh=torch.from_numpy(rng.standard_normal((k, n))))
+    got = bench.dump_outputs(res, str(tmp_path / "whole"))
+    assert sorted(got["arrays"]) == ["U", "V", "s"]
+    s, V, U = (np.load(tmp_path / "whole" / f"{a}.npy") for a in ("s", "V", "U"))
+    assert s.dtype == V.dtype == np.float64 and U.dtype == np.float32
+    assert np.array_equal(s, res.s.numpy()) and np.array_equal(V, res.Vh.numpy().T)
+    assert np.array_equal(U, res.Ut.numpy().T)
+
+    budget = 1 << 16
+    monkeypatch.setattr(bench, "DUMP_BYTES", budget)
+    for d in ("a", "b"):
+        got = bench.dump_outputs(res, str(tmp_path / d))
+        assert sorted(got["arrays"]) == ["U_sample", "V", "s"]
+        assert sum(f.stat().st_size for f in (tmp_path / d).iterdir()) <= budget + 3 * 128   # + .npy headers
+    Ua, Ub = np.load(tmp_path / "a" / "U_sample.npy"), np.load(tmp_path / "b" / "U_sample.npy")
+    assert Ua.dtype == np.float32 and Ua.shape[1] == k and 0 < Ua.shape[0] < rows
+    assert np.array_equal(Ua, Ub)
+    pick = np.sort(np.random.RandomState(0).choice(rows, size=Ua.shape[0], replace=False))
+    assert np.array_equal(Ua, res.Ut.numpy().T[pick])
+
+    monkeypatch.setattr(bench, "DUMP_BYTES", 8 * (k + n * k))
+    with pytest.raises(SystemExit):
+        bench.dump_outputs(res, str(tmp_path / "c"))
 
 
 @pytest.mark.parametrize("l,n,decades", [(20, 300, 3), (60, 500, 7), (7, 7, 2)])
