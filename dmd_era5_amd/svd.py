@@ -722,24 +722,33 @@ def as_blocks(Xt) -> list[torch.Tensor]:
     return [Xt[:, a:b].contiguous() for a, b in split_rows(m)]
 
 
-def _gram_blocks(blocks, kern, comm: Comm) -> torch.Tensor:
-    """G = sum over the local row blocks and over the ranks of X_b^T X_b (fp64, both triangles).
-    Across ranks only the upper triangle travels: n (n + 1) / 2 doubles, 307 MB instead of 614 MB
-    at n = 8760 (the one large exchange of the row-sharded method of snapshots)."""
-    G = kern.syrk_blocks(blocks) if len(blocks) > 1 else kern.syrk(blocks[0])
+def _accumulate_tn(kern, Ablocks, Bblocks=None, out: torch.Tensor | None = None) -> torch.Tensor:
+    """sum_b A_b^T B_b over lists of row blocks (the Gram sum_b A_b^T A_b without ``Bblocks``), fp64,
+    added to ``out`` when given (the blocks of a streamed piece add to those of the pieces before):
+    one batched launch (K1 / K3), or the single-block kernel for one block and nothing to add to."""
+    if out is None and len(Ablocks) == 1:
+        return kern.syrk(Ablocks[0]) if Bblocks is None else kern.gemm_tn(Ablocks[0], Bblocks[0])
+    return kern.syrk_blocks(Ablocks, out=out) if Bblocks is None else kern.gemm_tn_blocks(Ablocks, Bblocks, out=out)
+
+
+def _allreduce_gram(G: torch.Tensor, kern, comm: Comm) -> torch.Tensor:
+    """Sum a Gram matrix (fp64, both triangles) over the ranks.  Only the upper triangle travels:
+    n (n + 1) / 2 doubles, 307 MB instead of 614 MB at n = 8760 (the one large exchange of the
+    row-sharded method of snapshots)."""
     n = G.shape[0]
+    tag = "gram_allreduce" if n >= 1024 else "small_gram_allreduce"
     if comm.exchanges and n >= 64 and hasattr(kern, "pack_triu"):
-        packed = comm.allreduce_sum_(kern.pack_triu(G), tag="gram_allreduce" if n >= 1024 else "small_gram_allreduce")
-        return kern.unpack_triu(packed, n, out=G)
-    return comm.allreduce_sum_(G, tag="gram_allreduce" if n >= 1024 else "small_gram_allreduce")
+        return kern.unpack_triu(comm.allreduce_sum_(kern.pack_triu(G), tag=tag), n, out=G)
+    return comm.allreduce_sum_(G, tag=tag)
+
+
+def _gram_blocks(blocks, kern, comm: Comm) -> torch.Tensor:
+    """G = sum over the local row blocks and over the ranks of X_b^T X_b (fp64, both triangles)."""
+    return _allreduce_gram(_accumulate_tn(kern, blocks), kern, comm)
 
 
 def _gemm_tn_blocks(Ablocks, Bblocks, kern, comm: Comm) -> torch.Tensor:
-    if len(Ablocks) > 1:
-        C = kern.gemm_tn_blocks(list(Ablocks), list(Bblocks))
-    else:
-        C = kern.gemm_tn(Ablocks[0], Bblocks[0])
-    return comm.allreduce_sum_(C, tag="xty_allreduce")
+    return comm.allreduce_sum_(_accumulate_tn(kern, Ablocks, Bblocks), tag="xty_allreduce")
 
 
 def _project_blocks(kern, Xblocks, Wt: torch.Tensor, d: int, whole: torch.Tensor | None = None):
@@ -974,6 +983,189 @@ def _complete_unit_rows(Ub, ok: torch.Tensor, comm: Comm) -> None:
         U[bad] = Rb
 
 
+def _snapshots(pieces, persistent: bool, n_components: int, rows_global: int, delay: int, oversample,
+               flip_sign: bool, comm: Comm, kern, deflate_mean, refine: bool = True, eig_method: str = "auto",
+               stats: dict | None = None, phase: _PhaseClock | None = None):
+    """The method of snapshots over a piece source, the one implementation behind
+    :func:`svd_snapshots` and :func:`svd_snapshots_streaming`.  Every call ``pieces()`` is one pass
+    over X and yields, piece after piece, lists of (n, mb) row blocks: pass 1 accumulates the Gram,
+    the last pass projects, the polish step is one pass in between.  ``persistent``: every pass
+    yields the same tensors (X resident in HBM: pass 1 centres the blocks of an un-centred X in
+    place, and they are un-centred before returning, on an exception too); otherwise every pass
+    reads fresh copies, which get the row means stored in pass 1 subtracted again.  ``stats``:
+    :func:`_shard_stats` of all of X when known, else the dominant-mean test runs on the first
+    piece of every rank.  ``rows_global``: rows of the embedded matrix over all ranks (caps k like
+    numpy's slicing).  ``phase``: the stage clock of ``timings``.
+    Returns ([(Ublocks, whole) per piece], s, Vh, info), see :func:`_project_blocks` for ``whole``."""
+    kern = _kern(kern)
+    phase = phase or _PhaseClock(None, False)
+    info: dict = {}
+    G = w = musq = None
+    mus: list | None = None          # row means per block, in the order the pieces yield them
+    centred: list = []               # blocks of a persistent source that pass 1 centred in place
+
+    def later_pass():
+        """Pass 2 or 3: (blocks, their row means or None) per piece, the blocks as pass 1 left them."""
+        off = 0
+        for blocks in pieces():
+            blocks = list(blocks)
+            mp = None if mus is None else mus[off:off + len(blocks)]
+            if mp is not None and not persistent:
+                for B, mu in zip(blocks, mp):
+                    B -= mu
+            off += len(blocks)
+            yield blocks, mp
+
+    try:
+        for pi, blocks in enumerate(pieces()):
+            blocks = list(blocks)
+            if pi == 0:
+                if deflate_mean is None:
+                    st = stats if stats is not None else _shard_stats(blocks, comm, delay, True)
+                    # > 99 % of the energy in the per-row time mean: below that ratio s_1 / s_2 stays in
+                    # the hundreds, which the plain Gram route resolves (and the deflation's Schur
+                    # complement is exact only up to lambda_2 / lambda_1)
+                    deflate_mean = refine and blocks[0].shape[0] - delay + 1 > 2 and st["mean2"] > 100.0 * st["var"]
+                mus = [] if deflate_mean else None
+            if mus is not None:
+                mp = [kern.row_center_scale_(B, False)[0] for B in blocks]
+                mus += mp
+                if persistent:
+                    centred += blocks
+            G = _accumulate_tn(kern, blocks, out=G)
+            if mus is not None:
+                # w = A^T mu (n,), |mu|^2: one K3 pass with a single column
+                wp = _accumulate_tn(kern, [mu[None, :].contiguous() for mu in mp], blocks).reshape(-1)
+                sq = torch.stack([(mu.double() ** 2).sum() for mu in mp]).sum().reshape(1)
+                w, musq = (wp, sq) if w is None else (w + wp, musq + sq)
+        if G is None:
+            raise ValueError("svd_snapshots_streaming: no pieces")
+        G = _allreduce_gram(G, kern, comm)
+        if not bool(torch.isfinite(torch.diagonal(G)).all()):
+            # NaN / Inf in X: what np.linalg.svd (the reference's call, era5_svd.py:251) reports
+            raise np.linalg.LinAlgError("SVD did not converge")
+        if mus is not None:
+            comm.allreduce_sum_(w, tag="xty_allreduce")
+            comm.allreduce_sum_(musq)
+        if delay > 1:
+            G = kern.delay_shift_sum(G, delay)
+            if mus is not None:   # w_E[t] = sum_k w[t + k]
+                ndw = w.numel() - delay + 1
+                w = torch.stack([w[kd:kd + ndw] for kd in range(delay)]).sum(dim=0)
+        nd, dev = G.shape[0], G.device
+        phase("t_gram")
+
+        k = min(n_components, nd, rows_global)  # np.linalg.svd(full_matrices=False)[:k]
+        p = oversample if oversample is not None else max(8, k // 4)
+        l = min(nd, k + p) if refine else k
+        lam_d = None
+        if mus is None:
+            lam, V = top_eigh(G, l, method=eig_method, info=info, kern=kern)
+        else:
+            lam, V, lam_d, l = _eig_mean_deflated(G, w, musq, delay, l, eig_method, info, kern)
+        comm.broadcast_(lam, V, tag="eig_broadcast")
+        lam1 = lam[0].clamp_min(1e-300)
+        ref = lam[1] if (mus is not None and lam.numel() > 1) else lam1   # the deflated scale
+        steep = float(lam[min(k, lam.numel()) - 1]) < 1e-7 * float(ref)
+        polish = steep and refine
+        if polish:
+            # Steep spectrum (s_k < 3e-4 s_1): G (sums of fp32 products) resolves eigenvalues down
+            # to ~1e-9 lambda_1 only, so the trailing wanted directions are poorly determined by
+            # it.  One subspace iteration on X itself, V <- orth(E^T (E V)) (a K2 and a K3 pass, both
+            # while a piece is resident), fixes them up to the rounding of those products (~1e-7
+            # s_1 / s_j relative); the Rayleigh-Ritz below then runs on the un-normalised E V.
+            tp0 = _sync_time(dev) if phase.on else 0.0
+            Vt32 = _pitched(kern, V.T.contiguous().to(torch.float32))
+            if mus is not None:
+                ones_v = V.sum(dim=0).to(torch.float32)
+                my = torch.zeros(V.shape[1], dtype=torch.float64, device=dev)
+            Zt = None
+            for blocks, mp in later_pass():
+                Eb = [embed_view(B, delay) for B in blocks]
+                Yb = [kern.skinny(E, Vt32) for E in Eb]
+                if mp is not None:   # E = A + mu~ 1^T on the centred blocks: Y += mu~ (1^T V) ...
+                    for Y, mu in zip(Yb, mp):
+                        Y.addmm_(ones_v[:, None], mu.repeat(delay)[None, :])
+                        my += Y.double() @ mu.double().repeat(delay)
+                Zt = _accumulate_tn(kern, Eb, Yb, out=Zt)               # (l, nd) = (A^T Y)^T
+                del Yb
+            comm.allreduce_sum_(Zt, tag="xty_allreduce")
+            if mus is not None:   # ... and E^T Y = A^T Y + 1 (mu~^T Y)
+                comm.allreduce_sum_(my)
+                Zt = Zt + my[:, None]
+            Zn = Zt / torch.linalg.vector_norm(Zt, dim=1, keepdim=True).clamp_min(1e-300)
+            V = _orth(Zn.T.contiguous(), kern=kern)   # (columns span ~s_j^2: normalised first, CholeskyQR is not scale invariant)
+            comm.broadcast_(V)
+            lam = torch.ones_like(lam)                                # no S^-1 scaling of E V below
+            info["polished"] = True
+            if phase.on:
+                info["t_polish"] = _sync_time(dev) - tp0              # (part of t_eig: two passes over X)
+        elif steep:
+            info["warning"] = ("s_k < 3e-4 s_1 and refine=False: the Gram matrix of fp32 products resolves "
+                               "eigenvalues down to ~1e-9 lambda_1 only")
+        if polish:
+            good = torch.ones_like(lam, dtype=torch.bool)
+        elif mus is not None:
+            # resolvable: above the rounding of the deflated Gram (scale lam_d[0]) and above the
+            # rounding the dominant entry alpha leaves in the small Rayleigh-Ritz problem
+            good = lam > torch.maximum(lam_d[0].abs() * 1e-13, lam1 * 1e-15)
+        else:
+            good = lam > lam1 * 1e-14
+        s0 = torch.sqrt(torch.where(good, lam, torch.ones_like(lam)))
+        inv_s0 = torch.where(good, 1.0 / s0, torch.zeros_like(s0))
+        s0 = torch.where(good, s0, torch.zeros_like(s0))
+        phase("t_eig")
+
+        Wt = _pitched(kern, (V * inv_s0).T.contiguous().to(torch.float32))  # (l, nd)
+        if mus is not None:
+            cvec = (V.sum(dim=0) * inv_s0).to(torch.float32)
+        Up = []
+        for blocks, mp in later_pass():
+            Upp = [kern.skinny(embed_view(B, delay), Wt) for B in blocks]  # (l, d*mb): U' = E V S^-1
+            if mp is not None:   # + mu~ (1^T V) S^-1: the part of E the centred blocks no longer hold
+                for U, mu in zip(Upp, mp):
+                    U.addmm_(cvec[:, None], mu.repeat(delay)[None, :])
+            Up.append(Upp)
+        phase("t_project")
+
+        if refine:
+            # Rayleigh-Ritz in span(V): (XV)^T (XV) = S (U'^T U') S, graded by S so the
+            # small singular values keep their relative accuracy.
+            Mm = _gram_blocks([U for piece in Up for U in piece], kern, comm)   # (l, l) fp64
+            mu_, Z = _graded_eigh(s0, Mm, kern)
+            mu_ = mu_[:k].contiguous()
+            Z = Z[:, :k].contiguous()
+            comm.broadcast_(mu_, Z)
+            s = torch.sqrt(mu_.clamp_min(0.0))
+            ok = s > s0[0] * 1e-7 if (mus is None and not polish) else s > s[0] * 1e-7
+            inv_s = torch.where(ok, 1.0 / torch.where(ok, s, torch.ones_like(s)), torch.zeros_like(s))
+            Rm = (s0[:, None] * Z) * inv_s[None, :]                   # (l, k): U = U' R
+            Rt = _pitched(kern, Rm.T.contiguous().to(torch.float32))
+            # (k, d*mb) blocks, piece by piece: U' of a piece is dropped as soon as its U exists; the
+            # U of a single piece (X resident) is written straight into one (k, M) tensor
+            Ub = []
+            for piece in Up:
+                Ub.append(_project_blocks(kern, piece, Rt, delay) if len(Up) == 1 else
+                          ([kern.skinny(U, Rt) for U in piece], None))
+                piece.clear()
+            Vh = (V @ Z).T.contiguous()
+        else:
+            s, ok = s0[:k], good[:k]
+            Ub = [([U[:k] for U in piece], None) for piece in Up]
+            Vh = V[:, :k].T.contiguous()
+        flat = [U for piece, _ in Ub for U in piece]
+        if not bool(ok.all()):
+            _complete_unit_rows(flat, ok, comm)
+            info["completed_directions"] = int((~ok).sum())
+    finally:
+        for B, mu in zip(centred, mus or ()):
+            B += mu                                                  # un-centre: the caller's X is intact again
+    if flip_sign:
+        _, Vh = _sign_flip(flat, Vh, comm, kern)
+    info.update(l=l, k=k, nd=nd)
+    return Ub, s, Vh, info
+
+
 @_magnitude_guard(with_mean=True)
 def svd_snapshots(Xt, n_components: int, delay: int = 1, oversample: int | None = None,
                   refine: bool = True, flip_sign: bool = True, comm: Comm | None = None,
@@ -999,147 +1191,22 @@ def svd_snapshots(Xt, n_components: int, delay: int = 1, oversample: int | None 
     span{q, V} restores the exact coupling, U' = E V S^-1 is formed as A V S^-1 + mu~ (1^T V) S^-1,
     and the blocks are un-centred again before returning.
     """
-    kern = _kern(kern)
     comm = comm or Comm()
-    info: dict = {}
     blocks = as_blocks(Xt)
-    dev = blocks[0].device
     if _stats is None:
         _stats = _shard_stats(blocks, comm, delay, deflate_mean is None)
-    if deflate_mean is None:
-        # > 99 % of the energy in the per-row time mean: below that ratio s_1 / s_2 stays in the
-        # hundreds, which the plain Gram route resolves (and the deflation's Schur complement is
-        # exact only up to lambda_2 / lambda_1)
-        deflate_mean = refine and blocks[0].shape[0] - delay + 1 > 2 and _stats["mean2"] > 100.0 * _stats["var"]
-    t0 = _sync_time(dev) if timings else 0.0
-    mus = [kern.row_center_scale_(B, False)[0] for B in blocks] if deflate_mean else None
-    try:
-        G = _gram_blocks(blocks, kern, comm)
-        if not bool(torch.isfinite(torch.diagonal(G)).all()):
-            # NaN / Inf in X: what np.linalg.svd (the reference's call, era5_svd.py:251) reports
-            raise np.linalg.LinAlgError("SVD did not converge")
-        if mus is not None:
-            # w = Xc^T mu (n,), |mu|^2: one K3 pass with a single column
-            w = _gemm_tn_blocks([mu[None, :].contiguous() for mu in mus], blocks, kern, comm).reshape(-1)
-            musq = torch.stack([(mu.double() ** 2).sum() for mu in mus]).sum().reshape(1)
-            comm.allreduce_sum_(musq)
-        if delay > 1:
-            G = kern.delay_shift_sum(G, delay)
-            if mus is not None:   # w_E[t] = sum_k w[t + k]
-                ndw = w.numel() - delay + 1
-                w = torch.stack([w[kd:kd + ndw] for kd in range(delay)]).sum(dim=0)
-        nd = G.shape[0]
-        t1 = _sync_time(dev) if timings else 0.0
-
-        Mg = _stats["rows"]
-        k = min(n_components, nd, Mg)  # np.linalg.svd(full_matrices=False)[:k]
-        p = oversample if oversample is not None else max(8, k // 4)
-        l = min(nd, k + p) if refine else k
-        lam_d = None
-        if mus is None:
-            lam, V = top_eigh(G, l, method=eig_method, info=info, kern=kern)
-        else:
-            lam, V, lam_d, l = _eig_mean_deflated(G, w, musq, delay, l, eig_method, info, kern)
-        comm.broadcast_(lam, V, tag="eig_broadcast")
-        lam1 = lam[0].clamp_min(1e-300)
-        ref = lam[1] if (mus is not None and lam.numel() > 1) else lam1   # the deflated scale
-        steep = float(lam[min(k, lam.numel()) - 1]) < 1e-7 * float(ref)
-        polish = steep and refine
-        tp0 = _sync_time(dev) if (timings and polish) else 0.0
-        if polish:
-            # Steep spectrum (s_k < 3e-4 s_1): G (sums of fp32 products) resolves eigenvalues down
-            # to ~1e-9 lambda_1 only, so the trailing wanted directions are poorly determined by
-            # it.  One subspace iteration on X itself, V <- orth(E^T (E V)) (a K2 and a K3 pass),
-            # fixes them up to the rounding of those products (~1e-7 s_1 / s_j relative); the
-            # Rayleigh-Ritz below then runs on the un-normalised E V.
-            Eb = [embed_view(B, delay) for B in blocks]
-            Vt32 = _pitched(kern, V.T.contiguous().to(torch.float32))
-            Yb = [kern.skinny(E, Vt32) for E in Eb]
-            if mus is not None:   # E = A + mu~ 1^T on the centred blocks: Y += mu~ (1^T V)
-                ones_v = V.sum(dim=0).to(torch.float32)
-                for Y, mu in zip(Yb, mus):
-                    Y.addmm_(ones_v[:, None], mu.repeat(delay)[None, :])
-            Zt = _gemm_tn_blocks(Eb, Yb, kern, comm)                  # (l, nd) = (A^T Y)^T
-            if mus is not None:   # ... and E^T Y = A^T Y + 1 (mu~^T Y)
-                my = torch.zeros(Zt.shape[0], dtype=torch.float64, device=dev)
-                for Y, mu in zip(Yb, mus):
-                    my += Y.double() @ mu.double().repeat(delay)
-                comm.allreduce_sum_(my)
-                Zt = Zt + my[:, None]
-            Zn = Zt / torch.linalg.vector_norm(Zt, dim=1, keepdim=True).clamp_min(1e-300)
-            V = _orth(Zn.T.contiguous(), kern=kern)   # (columns span ~s_j^2: normalised first, CholeskyQR is not scale invariant)
-            comm.broadcast_(V)
-            lam = torch.ones_like(lam)                                # no S^-1 scaling of E V below
-            info["polished"] = True
-            if timings:
-                info["t_polish"] = _sync_time(dev) - tp0              # (part of t_eig: two passes over X)
-        elif steep:
-            info["warning"] = ("s_k < 3e-4 s_1 and refine=False: the Gram matrix of fp32 products resolves "
-                               "eigenvalues down to ~1e-9 lambda_1 only")
-        good = lam > lam1 * 1e-14
-        if polish:
-            good = torch.ones_like(lam, dtype=torch.bool)
-            ref = lam1 = lam[0]
-        if mus is not None and not polish:
-            # resolvable: above the rounding of the deflated Gram (scale lam_d[0]) and above the
-            # rounding the dominant entry alpha leaves in the small Rayleigh-Ritz problem
-            good = lam > torch.maximum(lam_d[0].abs() * 1e-13, lam1 * 1e-15)
-        s0 = torch.sqrt(torch.where(good, lam, torch.ones_like(lam)))
-        inv_s0 = torch.where(good, 1.0 / s0, torch.zeros_like(s0))
-        s0 = torch.where(good, s0, torch.zeros_like(s0))
-        t2 = _sync_time(dev) if timings else 0.0
-
-        Wt = _pitched(kern, (V * inv_s0).T.contiguous().to(torch.float32))  # (l, nd)
-        Up = [kern.skinny(embed_view(B, delay), Wt) for B in blocks]  # (l, d*mb): U' = X V S^-1
-        if mus is not None:   # + mu~ (1^T V) S^-1: the part of E the centred blocks no longer hold
-            cvec = (V.sum(dim=0) * inv_s0).to(torch.float32)
-            for U, mu in zip(Up, mus):
-                U.addmm_(cvec[:, None], mu.repeat(delay)[None, :])
-        t3 = _sync_time(dev) if timings else 0.0
-
-        if refine:
-            # Rayleigh-Ritz in span(V): (XV)^T (XV) = S (U'^T U') S, graded by S so the
-            # small singular values keep their relative accuracy.
-            Mm = _gram_blocks(Up, kern, comm)                         # (l, l) fp64
-            mu_, Z = _graded_eigh(s0, Mm, kern)
-            mu_ = mu_[:k].contiguous()
-            Z = Z[:, :k].contiguous()
-            comm.broadcast_(mu_, Z)
-            s = torch.sqrt(mu_.clamp_min(0.0))
-            ok = s > s0[0] * 1e-7 if (mus is None and not polish) else s > s[0] * 1e-7
-            inv_s = torch.where(ok, 1.0 / torch.where(ok, s, torch.ones_like(s)), torch.zeros_like(s))
-            Rm = (s0[:, None] * Z) * inv_s[None, :]                   # (l, k): U = U' R
-            Rt = _pitched(kern, Rm.T.contiguous().to(torch.float32))
-            Ub, whole = _project_blocks(kern, Up, Rt, delay)          # (k, d*mb)
-            Vh = (V @ Z).T.contiguous()
-            if not bool(ok.all()):
-                _complete_unit_rows(Ub, ok, comm)
-                info["completed_directions"] = int((~ok).sum())
-        else:
-            s = s0[:k]
-            Ub, whole = [U[:k] for U in Up], None
-            Vh = V[:, :k].T.contiguous()
-            if not bool(good[:k].all()):
-                _complete_unit_rows(Ub, good[:k], comm)
-                info["completed_directions"] = int((~good[:k]).sum())
-    finally:
-        if mus is not None:
-            for B, mu in zip(blocks, mus):
-                B += mu                                              # un-centre: the caller's X is intact again
-    if flip_sign:
-        Ub, Vh = _sign_flip(Ub, Vh, comm, kern)
+    phase = _PhaseClock(blocks[0].device, timings)
+    [(Ub, whole)], s, Vh, info = _snapshots(lambda: (blocks,), True, n_components, _stats["rows"], delay, oversample,
+                                            flip_sign, comm, kern, deflate_mean, refine=refine,
+                                            eig_method=eig_method, stats=_stats, phase=phase)
     Ut = whole if whole is not None else _assemble_rows(Ub, delay)
     if timings:
-        t4 = _sync_time(dev)
-        info.update(t_gram=t1 - t0, t_eig=t2 - t1, t_project=t3 - t2, t_refine=t4 - t3,
-                    t_total=t4 - t0)
-    info.update(l=l, k=k, nd=nd, row_blocks=len(blocks))
+        phase("t_refine")
+        info.update(phase.acc, t_total=sum(phase.acc.values()))
+    info["row_blocks"] = len(blocks)
     return SvdResult(Ut=Ut, s=s, Vh=Vh, info=info)
 
 
-# ---------------------------------------------------------------------------
-# "standard", snapshot matrix larger than the HBM: two streaming passes
-# ---------------------------------------------------------------------------
 def svd_snapshots_streaming(pieces, n_components: int, rows_global: int, delay: int = 1,
                             oversample: int | None = None, flip_sign: bool = True,
                             comm: Comm | None = None, kern=None, deflate_mean: bool | None = None) -> tuple:
@@ -1149,9 +1216,9 @@ def svd_snapshots_streaming(pieces, n_components: int, rows_global: int, delay: 
     Pass 1 accumulates the Gram, the last pass projects: only the m x l basis U' stays resident
     (l = k + max(8, k/4) columns against X's n).
 
-    Same arithmetic as :func:`svd_snapshots` on the concatenation of all pieces -- Gram in fp64
-    across blocks, top-l eigenpairs, U' = E V S^-1, Rayleigh-Ritz refinement, sign convention --
-    including its two refinements, each at the price of what it needs here:
+    The same implementation as :func:`svd_snapshots` (:func:`_snapshots`, of which the resident
+    matrix is the one-piece case), its two refinements included, each at the price of what it
+    needs here:
     * a dominant per-row time mean (un-centred data; ``deflate_mean`` None = detected on the first
       piece of every rank, one exchange) is deflated exactly: the pieces are row-centred in place
       as they pass (K5 in pass 1, which also yields w = A^T mu and |mu|^2 with one extra
@@ -1161,135 +1228,15 @@ def svd_snapshots_streaming(pieces, n_components: int, rows_global: int, delay: 
       V <- orth(E^T (E V)) as ONE extra pass (both products while a piece is resident).
     ``rows_global``: rows of the embedded matrix over all ranks (caps k like numpy's slicing).
     Returns (Ublocks, s, Vh, info): ``Ublocks[i]`` = list of (k, d*mb) tensors of piece i."""
-    kern = _kern(kern)
-    comm = comm or Comm()
-    info: dict = {"streaming": True, "passes_over_X": 2}
-    G = None
-    mus: list | None = None          # per block, in the order the pieces yield them
-    w = None
-    musq = None
-    for pi, blocks in enumerate(pieces()):
-        blocks = list(blocks)
-        if pi == 0:
-            if deflate_mean is None:
-                st = _shard_stats(blocks, comm, delay, True)
-                deflate_mean = blocks[0].shape[0] - delay + 1 > 2 and st["mean2"] > 100.0 * st["var"]
-            if deflate_mean:
-                mus = []
-        if mus is not None:
-            mp = [kern.row_center_scale_(B, False)[0] for B in blocks]
-            wp = _gemm_tn_blocks([mu[None, :].contiguous() for mu in mp], blocks, kern, Comm()).reshape(-1)
-            w = wp if w is None else w + wp
-            sq = torch.stack([(mu.double() ** 2).sum() for mu in mp]).sum().reshape(1)
-            musq = sq if musq is None else musq + sq
-            mus.extend(mp)
-        G = kern.syrk_blocks(blocks, out=G) if (G is not None or len(blocks) > 1) else kern.syrk(blocks[0])
-    if G is None:
-        raise ValueError("svd_snapshots_streaming: no pieces")
-    n_t = G.shape[0]
-    if comm.exchanges and n_t >= 64 and hasattr(kern, "pack_triu"):
-        G = kern.unpack_triu(comm.allreduce_sum_(kern.pack_triu(G)), n_t, out=G)
-    else:
-        comm.allreduce_sum_(G)
-    if mus is not None:
-        comm.allreduce_sum_(w)
-        comm.allreduce_sum_(musq)
-    if not bool(torch.isfinite(torch.diagonal(G)).all()):
-        raise np.linalg.LinAlgError("SVD did not converge")
-    if delay > 1:
-        G = kern.delay_shift_sum(G, delay)
-        if mus is not None:
-            ndw = w.numel() - delay + 1
-            w = torch.stack([w[kd:kd + ndw] for kd in range(delay)]).sum(dim=0)
-    nd = G.shape[0]
-    dev = G.device
-    k = min(n_components, nd, rows_global)
-    p = oversample if oversample is not None else max(8, k // 4)
-    l = min(nd, k + p)
-    lam_d = None
-    if mus is None:
-        lam, V = top_eigh(G, l, info=info, kern=kern)
-    else:
-        lam, V, lam_d, l = _eig_mean_deflated(G, w, musq, delay, l, "auto", info, kern)
-    comm.broadcast_(lam, V)
-    lam1 = lam[0].clamp_min(1e-300)
-    ref = lam[1] if (mus is not None and lam.numel() > 1) else lam1
-
-    def centred(blocks, off):
-        """The piece as pass 1 saw it: the stored row means subtracted again (in place)."""
-        blocks = list(blocks)
-        if mus is not None:
-            for j, B in enumerate(blocks):
-                B -= mus[off + j]
-        return blocks
-
-    polish = float(lam[min(k, lam.numel()) - 1]) < 1e-7 * float(ref)
-    if polish:
-        # one subspace iteration on X itself (see svd_snapshots): Z = E^T (E V), piece by piece
-        Vt32 = _pitched(kern, V.T.contiguous().to(torch.float32))
-        ones_v = V.sum(dim=0).to(torch.float32)
-        Zt, my, off = None, torch.zeros(V.shape[1], dtype=torch.float64, device=dev), 0
-        for blocks in pieces():
-            blocks = centred(blocks, off)
-            Eb = [embed_view(B, delay) for B in blocks]
-            Yb = [kern.skinny(E, Vt32) for E in Eb]
-            if mus is not None:
-                for j, Y in enumerate(Yb):
-                    mu = mus[off + j]
-                    Y.addmm_(ones_v[:, None], mu.repeat(delay)[None, :])
-                    my += Y.double() @ mu.double().repeat(delay)
-            Zt = kern.gemm_tn_blocks(Eb, Yb, out=Zt) if (Zt is not None or len(Eb) > 1) else kern.gemm_tn(Eb[0], Yb[0])
-            off += len(blocks)
-            del Yb
-        comm.allreduce_sum_(Zt)
-        if mus is not None:
-            comm.allreduce_sum_(my)
-            Zt = Zt + my[:, None]
-        Zn = Zt / torch.linalg.vector_norm(Zt, dim=1, keepdim=True).clamp_min(1e-300)
-        V = _orth(Zn.T.contiguous(), kern=kern)
-        comm.broadcast_(V)
-        lam = torch.ones_like(lam)
-        info["polished"] = True
-        info["passes_over_X"] = 3
-    good = lam > lam1 * 1e-14
-    if polish:
-        good = torch.ones_like(lam, dtype=torch.bool)
-    elif mus is not None:
-        good = lam > torch.maximum(lam_d[0].abs() * 1e-13, lam1 * 1e-15)
-    s0 = torch.sqrt(torch.where(good, lam, torch.ones_like(lam)))
-    inv_s0 = torch.where(good, 1.0 / s0, torch.zeros_like(s0))
-    s0 = torch.where(good, s0, torch.zeros_like(s0))
-    Wt = _pitched(kern, (V * inv_s0).T.contiguous().to(torch.float32))
-    cvec = (V.sum(dim=0) * inv_s0).to(torch.float32)
-    Up, off = [], 0
-    for blocks in pieces():                                   # U' = E V S^-1
-        blocks = centred(blocks, off)
-        piece = [kern.skinny(embed_view(B, delay), Wt) for B in blocks]
-        if mus is not None:
-            for j, U in enumerate(piece):
-                U.addmm_(cvec[:, None], mus[off + j].repeat(delay)[None, :])
-        Up.append(piece)
-        off += len(blocks)
-    flat = [U for piece in Up for U in piece]
-    Mm = _gram_blocks(flat, kern, comm)
-    mu_, Z = _graded_eigh(s0, Mm, kern)
-    mu_, Z = mu_[:k].contiguous(), Z[:, :k].contiguous()
-    comm.broadcast_(mu_, Z)
-    s = torch.sqrt(mu_.clamp_min(0.0))
-    ok = s > s0[0] * 1e-7 if (mus is None and not polish) else s > s[0] * 1e-7
-    inv_s = torch.where(ok, 1.0 / torch.where(ok, s, torch.ones_like(s)), torch.zeros_like(s))
-    Rt = _pitched(kern, ((s0[:, None] * Z) * inv_s[None, :]).T.contiguous().to(torch.float32))
-    Ub = []
-    for piece in Up:                      # U = U' R, piece by piece; U' of the piece is dropped right away
-        Ub.append([kern.skinny(U, Rt) for U in piece])
-        piece.clear()
-    Vh = (V @ Z).T.contiguous()
-    if flip_sign:
-        _, Vh = _sign_flip([U for piece in Ub for U in piece], Vh, comm, kern)
-    info.update(l=l, k=k, nd=nd)
-    return Ub, s, Vh, info
+    Ub, s, Vh, info = _snapshots(pieces, False, n_components, rows_global, delay, oversample, flip_sign,
+                                 comm or Comm(), kern, deflate_mean)
+    info = {"streaming": True, "passes_over_X": 3 if info.get("polished") else 2, **info}
+    return [U for U, _ in Ub], s, Vh, info
 
 
+# ---------------------------------------------------------------------------
+# "randomized", snapshot matrix larger than the HBM: n_iter + 2 streaming passes
+# ---------------------------------------------------------------------------
 def svd_randomized_streaming(pieces, n_components: int, rows_global: int, n_time: int, delay: int = 1,
                              n_oversamples: int = 10, n_iter="auto", omega=None, random_state=None,
                              flip_sign: bool = True, comm: Comm | None = None, kern=None) -> tuple:
@@ -1308,13 +1255,7 @@ def svd_randomized_streaming(pieces, n_components: int, rows_global: int, n_time
     k = min(n_components, nd, rows_global)
     l = min(n_components + n_oversamples, nd, rows_global)
     n_it = resolve_n_iter(n_components, rows_global, nd, n_iter)
-    if omega is None:
-        rs = random_state if isinstance(random_state, np.random.RandomState) else np.random.RandomState(random_state)
-        omega = rs.normal(size=(nd, n_components + n_oversamples))[:, :l]
-    omega = torch.as_tensor(np.ascontiguousarray(np.asarray(omega).T, dtype=np.float32)) if not isinstance(omega, torch.Tensor) \
-        else omega.T.contiguous().to(torch.float32)
-    if tuple(omega.shape) != (l, nd):
-        raise ValueError(f"omega must be ({nd}, {l}), got {tuple(omega.shape)[::-1]}")
+    omega = _omega_t(omega, random_state, nd, n_components + n_oversamples, l)
     Qt, dev = None, None
     for _ in range(n_it):
         Z = None
@@ -1325,7 +1266,7 @@ def svd_randomized_streaming(pieces, n_components: int, rows_global: int, n_time
             Qp = _pitched(kern, Qt)
             Eb = [embed_view(B, delay) for B in blocks]
             Yb = [kern.skinny(E, Qp) for E in Eb]
-            Z = kern.gemm_tn_blocks(Eb, Yb, out=Z) if (Z is not None or len(Eb) > 1) else kern.gemm_tn(Eb[0], Yb[0])
+            Z = _accumulate_tn(kern, Eb, Yb, out=Z)
             del Yb
         comm.allreduce_sum_(Z)
         if not bool(torch.isfinite(Z).all()):
@@ -1345,7 +1286,7 @@ def svd_randomized_streaming(pieces, n_components: int, rows_global: int, n_time
     for pi, blocks in enumerate(pieces()):                     # B = Q^T E, piece by piece
         Eb = [embed_view(B, delay) for B in blocks]
         Qb = Qm[bounds[pi]:bounds[pi + 1]]
-        Bm = kern.gemm_tn_blocks(Eb, Qb, out=Bm) if (Bm is not None or len(Eb) > 1) else kern.gemm_tn(Eb[0], Qb[0])
+        Bm = _accumulate_tn(kern, Eb, Qb, out=Bm)
     comm.allreduce_sum_(Bm)
     Uhat, s, Vh = _svd_wide(Bm, kern)
     Uhat, s, Vh = Uhat.contiguous(), s.contiguous(), Vh.contiguous()
@@ -1446,6 +1387,22 @@ def resolve_n_iter(n_components: int, m: int, n: int, n_iter="auto") -> int:
     return int(n_iter)
 
 
+def _omega_t(omega, random_state, nd: int, width: int, l: int) -> torch.Tensor:
+    """Omega^T, the (l, nd) fp32 test matrix of the range finder: the caller's (nd, l) ``omega``
+    (array or tensor), else the first l columns of ``RandomState(random_state).normal(size=(nd,
+    width))`` -- the very draw sklearn makes (extmath.py:297)."""
+    if omega is None:
+        rs = random_state if isinstance(random_state, np.random.RandomState) else np.random.RandomState(random_state)
+        omega = rs.normal(size=(nd, width))[:, :l]
+    if isinstance(omega, torch.Tensor):
+        Qt = omega.T.contiguous().to(torch.float32)
+    else:
+        Qt = torch.from_numpy(np.ascontiguousarray(np.asarray(omega).T, dtype=np.float32))
+    if tuple(Qt.shape) != (l, nd):
+        raise ValueError(f"omega must be ({nd}, {l}), got {tuple(Qt.shape)[::-1]}")
+    return Qt
+
+
 @_magnitude_guard(with_mean=False)
 def svd_randomized(Xt, n_components: int, delay: int = 1, n_oversamples: int = 10,
                    n_iter="auto", power_iteration_normalizer: str = "auto",
@@ -1485,17 +1442,7 @@ def svd_randomized(Xt, n_components: int, delay: int = 1, n_oversamples: int = 1
     # EXPLICIT power_iteration_normalizer="none" is taken literally (sklearn's arithmetic, its
     # loss of the trailing directions included).
     normalise = not asked_none
-    if omega is None:
-        rs = random_state if isinstance(random_state, np.random.RandomState) else \
-            np.random.RandomState(random_state)
-        omega = rs.normal(size=(nd, n_components + n_oversamples))[:, :l]
-    if isinstance(omega, np.ndarray):
-        omega = torch.from_numpy(np.ascontiguousarray(omega.T, dtype=np.float32))
-        Qt = omega.to(dev)
-    else:
-        Qt = omega.T.contiguous().to(device=dev, dtype=torch.float32)
-    if tuple(Qt.shape) != (l, nd):
-        raise ValueError(f"omega must be ({nd}, {l}), got {tuple(Qt.shape)[::-1]}")
+    Qt = _omega_t(omega, random_state, nd, n_components + n_oversamples, l).to(dev)
     t0 = _sync_time(dev) if timings else 0.0
     # The (k, M) result is allocated FIRST: requested at the end, next to X and the m x l iterates
     # (cfg4: 227.6 + 13.7 GB resident, 12.5 GB wanted), the caching allocator finds its one cached

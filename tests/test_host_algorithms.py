@@ -204,12 +204,19 @@ def test_row_blocks_do_not_change_the_answer(monkeypatch):
 
 
 def test_rank_deficient_input_gives_zero_tail():
+    """Rank 3, k = 6: the directions of the zero singular values get an orthonormal completion (as
+    LAPACK's U does), with X resident and streamed in two pieces alike."""
     rs = np.random.RandomState(1)
     X = (rs.standard_normal((500, 3)) @ rs.standard_normal((3, 40))).astype(np.float32)
-    r = dsvd.svd_snapshots(_xt(X), 6, kern=K)
-    s = r.s.numpy()
-    assert np.all(s[:3] > 1) and np.all(s[3:] < 1e-3 * s[0])
-    assert np.isfinite(r.Ut.numpy()).all()
+    Xt = _xt(X)
+    r = dsvd.svd_snapshots(Xt, 6, kern=K)
+    Ub, s_st, _, _ = dsvd.svd_snapshots_streaming(lambda: ([Xt[:, :240].contiguous()], [Xt[:, 240:].contiguous()]),
+                                                  6, 500, kern=K)
+    for s, Ut in ((r.s, r.Ut), (s_st, torch.cat([u for p in Ub for u in p], dim=1))):
+        s = s.numpy()
+        assert np.all(s[:3] > 1) and np.all(s[3:] < 1e-3 * s[0])
+        assert np.isfinite(Ut.numpy()).all()
+        assert torch.allclose(Ut.double() @ Ut.double().T, torch.eye(6, dtype=torch.float64), atol=1e-5)
 
 
 # ---------------------------------------------------------------- world_size 2 over gloo
