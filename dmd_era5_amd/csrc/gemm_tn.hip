@@ -1322,6 +1322,29 @@ int run_xty_small(const float* const* X, const int64_t* ldx, const float* const*
   return 0;
 }
 
+// A call that runs as several launches (row split, groups of 16 blocks, K3s + its tail launch) checks what
+// every one of them will check BEFORE the first one: a refused call leaves the outputs and the workspace
+// untouched.  (The per-launch checks of run_tn / run_batch used to fire between launches: a group of blocks
+// behind the first 16 with a larger plan or a too long leading dimension left C half accumulated.)
+int tn_refusal(const char* who, const int64_t* lda, const int64_t* ldb, int nblocks, int64_t ld_limit,
+               const void* ws, size_t ws_bytes, size_t need) {
+  for (int j = 0; j < nblocks; ++j)
+    if (lda[j] >= ld_limit || ldb[j] >= ld_limit) {
+      dmdx_set_error("%s: leading dimension %lld / %lld >= %lld not supported (use smaller row blocks)", who,
+                     (long long)lda[j], (long long)ldb[j], (long long)ld_limit);
+      return DMDX_E_UNSUPPORTED;
+    }
+  if (ws == nullptr || ws_bytes < need) {
+    dmdx_set_error("%s: workspace %zu bytes < required %zu", who, ws_bytes, need);
+    return DMDX_E_WORKSPACE;
+  }
+  return 0;
+}
+#define DMDX_REFUSE_BEFORE_LAUNCH(expr) \
+  do {                                  \
+    if (const int rc_ = (expr)) return rc_; \
+  } while (0)
+
 }  // namespace
 
 extern "C" {
@@ -1354,7 +1377,6 @@ int dmdx_syrk_f32(const float* X, int64_t m, int64_t n, int64_t ldx, double* G64
   DMDX_CHECK_ARG(m >= 1 && n >= 1 && n < (1 << 30), "syrk: bad shape m=%lld n=%lld", (long long)m,
                  (long long)n);
   DMDX_CHECK_ARG(ldx >= 1 && ldg >= n && (!G32 || ldg32 >= n), "syrk: bad leading dimension");
-  DMDX_CHECK_ARG(ldx < (1ll << 24), "syrk: ldx >= 2^24 not supported (use row blocks)");
   return run_tn(X, ldx, X, ldx, m, n, n, 1, G64, ldg, G32, ldg32, accumulate, workspace, workspace_bytes,
                 (hipStream_t)stream);
 }
@@ -1378,6 +1400,8 @@ int dmdx_syrk_blocks_f32(const float* const* X, const int64_t* m, const int64_t*
   DMDX_CHECK_ARG(n >= 1 && n < (1 << 30) && ldg >= n && (!G32 || ldg32 >= n), "syrk_blocks: bad n / ldg");
   for (int j = 0; j < nblocks; ++j)
     DMDX_CHECK_ARG(X[j] && m[j] >= 1 && ldx[j] >= 1, "syrk_blocks: bad block %d", j);
+  DMDX_REFUSE_BEFORE_LAUNCH(tn_refusal("syrk_blocks", ldx, ldx, nblocks, int64_t(1) << 24, workspace, workspace_bytes,
+                                       dmdx_syrk_blocks_workspace_bytes(m, nblocks, n)));
   return run_batch(X, ldx, X, ldx, m, nblocks, n, n, 1, G64, ldg, G32, ldg32, accumulate, workspace,
                    workspace_bytes, (hipStream_t)stream);
 }
@@ -1417,8 +1441,9 @@ int dmdx_gemm_tn_f32(const float* A, int64_t lda, const float* B, int64_t ldb, i
                  "gemm_tn: bad shape");
   DMDX_CHECK_ARG(lda >= 1 && ldb >= 1 && ldc >= na && (!C32 || ldc32 >= na),
                  "gemm_tn: bad leading dimension");
-  DMDX_CHECK_ARG(lda < (1ll << 24) && ldb < (1ll << 24),
-                 "gemm_tn: leading dimension >= 2^24 not supported (use row blocks)");
+  // (a product that runs as two launches is refused as a whole: nothing is written before an error)
+  DMDX_REFUSE_BEFORE_LAUNCH(tn_refusal("gemm_tn", &lda, &ldb, 1, int64_t(1) << 25, workspace, workspace_bytes,
+                                       dmdx_gemm_tn_workspace_bytes(K, na, nb)));
   // column-major C[a + b*ldc] == row-major D[b][a]: D rows <- B columns, D cols <- A columns
   if (const int64_t cut = tn_row_split(nb)) {
     const int rc = run_tn(B, ldb, A, lda, K, cut, na, 0, C64, ldc, C32, ldc32, accumulate, workspace,
@@ -1462,6 +1487,8 @@ int dmdx_gemm_tn_blocks_f32(const float* const* A, const int64_t* lda, const flo
                  "gemm_tn_blocks: bad shape / ldc");
   for (int j = 0; j < nblocks; ++j)
     DMDX_CHECK_ARG(A[j] && B[j] && K[j] >= 1 && lda[j] >= 1 && ldb[j] >= 1, "gemm_tn_blocks: bad block %d", j);
+  DMDX_REFUSE_BEFORE_LAUNCH(tn_refusal("gemm_tn_blocks", lda, ldb, nblocks, int64_t(1) << 24, workspace, workspace_bytes,
+                                       dmdx_gemm_tn_blocks_workspace_bytes(K, nblocks, na, nb)));
   // column-major C[a + b*ldc] == row-major D[b][a]: D rows <- B columns, D cols <- A columns
   if (xty_small_ok(A, lda, B, ldb, K, nblocks, nb, na, C32))
     return run_xty_small(A, lda, B, ldb, K, nblocks, nb, na, C64, ldc, accumulate, workspace, workspace_bytes,

@@ -25,6 +25,29 @@
  *     no allocation (workspaces are caller-provided);
  *   - return value 0 = ok, < 0 = error (-(hipError_t) or DMDX_E_*);
  *     dmdx_last_error() gives the message for the calling thread.
+ *
+ * Memory contract (tests/test_gpu_memory_edges.py holds every entry point to it)
+ *   - only the logical rows x cols elements of an operand take part: the ld - rows elements behind
+ *     every column, the rows past K and whatever lies before or behind a matrix are never used for
+ *     a result (they may hold NaN) and never written -- also by the in-place kernels (K5,
+ *     dmdx_scale_columns_f32) and for outputs with a leading dimension larger than the matrix
+ *     (ldg, ldg32, ldc, ldc32, ldy, ldgd, ldv, ldz, ldl, ldi);
+ *   - with accumulate == 0 every logical element of an output is written and none is read;
+ *   - a workspace needs no initialisation, `*_workspace_bytes` is sufficient, and nothing is
+ *     written behind it; K7L / K10 zero their barrier words themselves;
+ *   - a call that is refused (DMDX_E_*) has written nothing, even when it would have run as
+ *     several launches (groups of 16 blocks, the row split of K3);
+ *   - alignment: NO fp32 entry point requires one.  16-byte aligned bases with leading dimensions
+ *     that are multiples of 4 select the fast paths -- K1 / K3: LDS-DMA staging (all operands of a
+ *     launch, ld < 2^22; K3s also wants K >= 512 per block and no fp32 copy); K2: 16-byte loads and
+ *     stores (X, W, Y, and m % 4 == 0); K5: the tiled float4 kernel (X) -- everything else takes
+ *     the register / scalar paths with the same results to rounding.  K % 4 and n % 4 are free.
+ *     The fp64 MFMA kernels K8 / K9 / K11 REQUIRE what their comments state (even widths and
+ *     leading dimensions of the inputs, 16-byte aligned inputs and workspace) and return
+ *     DMDX_E_INVALID otherwise; their outputs and K6 / K7 / K7L / K10 take any leading dimension;
+ *   - leading dimensions of K1 / K3 operands: < 2^25 on the single entry points, < 2^24 per block
+ *     on the blocks entry points, DMDX_E_UNSUPPORTED beyond; K2: m + 4 ldx < 2^29
+ *     (DMDX_E_INVALID beyond).
  */
 #ifndef DMDX_H
 #define DMDX_H
