@@ -94,7 +94,7 @@ __global__ __launch_bounds__(256) void row_center_scale_kernel(float* __restrict
   for (int e = 0; e < R; ++e) {
     double mc = s1[e] / (double)n;
     double var = s2[e] / (double)n - mc * mc;
-    sd[e] = (float)sqrt(var > 0.0 ? var : 0.0);
+    sd[e] = (float)sqrt(var < 0.0 ? 0.0 : var);   // (a NaN stays one: the std of a row with a NaN is NaN, not 0)
     if (e < nr) sdev[r0 + e] = sd[e];
   }
 #pragma unroll 8
@@ -187,7 +187,7 @@ __global__ __launch_bounds__(256) void row_center_scale_tiled_kernel(float* __re
   for (int e = 0; e < 4; ++e) {
     const double mc = s1[e] / (double)n;
     const double var = s2[e] / (double)n - mc * mc;
-    sd[e] = (float)sqrt(var > 0.0 ? var : 0.0);
+    sd[e] = (float)sqrt(var < 0.0 ? 0.0 : var);   // (a NaN stays one)
   }
   if (ty == 0)
     for (int e = 0; e < nr; ++e) sdev[r0 + e] = sd[e];

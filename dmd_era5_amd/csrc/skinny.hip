@@ -90,14 +90,17 @@ __global__ __launch_bounds__(256, 1) void skinny_kernel(
   auto load_x = [&](int64_t kcol) -> f32x4 {
     const int64_t ka = kcol < n ? kcol : n - 1, kb = kcol + 4 < n ? kcol + 4 : n - 1;  // scalar clamps
     const float* q = X + (lh ? kb : ka) * ldx + crow;
+    // a column past the end is clamped for the ADDRESS only and contributes zeros: the duplicate of
+    // column n - 1 would meet W's zero padding, and an Inf there would give Inf * 0 = NaN in the row
+    const bool inside = lh ? kcol + 4 < n : kcol < n;
+    f32x4 v;
     if (ALIGNED) {
-      return *reinterpret_cast<const f32x4*>(q);
+      v = *reinterpret_cast<const f32x4*>(q);
     } else {
-      f32x4 v;
 #pragma unroll
       for (int e = 0; e < 4; ++e) v[e] = (crow + e < m) ? q[e] : 0.f;
-      return v;
     }
+    return inside ? v : f32x4{0.f, 0.f, 0.f, 0.f};
   };
 
   // W staging: C pieces of 16 bytes per thread per chunk (column wcol + 32 i, k-piece wq)

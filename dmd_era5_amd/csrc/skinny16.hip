@@ -115,16 +115,19 @@ __global__ __launch_bounds__(256, WPS) void skinny16_kernel(
   // slow path (tail chunks, unaligned operands): kcol = the column of lane group kk = 0
   auto load_x = [&](int64_t kcol) -> f32x4 {
     int64_t kc = kcol + 4 * kk;
-    kc = kc < n ? kc : n - 1;
+    // a column past the end is clamped for the ADDRESS only and contributes zeros: the duplicate of
+    // column n - 1 would meet W's zero padding, and an Inf there would give Inf * 0 = NaN in the row
+    const bool inside = kc < n;
+    kc = inside ? kc : n - 1;
     const float* q = X + kc * ldx + crow;
+    f32x4 v;
     if (ALIGNED) {
-      return *reinterpret_cast<const f32x4*>(q);
+      v = *reinterpret_cast<const f32x4*>(q);
     } else {
-      f32x4 v;
 #pragma unroll
       for (int e = 0; e < 4; ++e) v[e] = (crow + e < m) ? q[e] : 0.f;
-      return v;
     }
+    return inside ? v : f32x4{0.f, 0.f, 0.f, 0.f};
   };
 
   // W staging: 128 C16 pieces of 16 bytes per chunk, piece idx = tid + 256 i -> column idx >> 3, k-piece idx & 7

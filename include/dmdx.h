@@ -48,6 +48,40 @@
  *   - leading dimensions of K1 / K3 operands: < 2^25 on the single entry points, < 2^24 per block
  *     on the blocks entry points, DMDX_E_UNSUPPORTED beyond; K2: m + 4 ldx < 2^29
  *     (DMDX_E_INVALID beyond).
+ *
+ * Value contract (tests/test_gpu_value_domain.py holds every fp32 entry point to it)
+ *   - NaN / Inf propagate like IEEE arithmetic on the logical operands, nothing more and nothing less:
+ *     the class (finite / NaN / +Inf / -Inf) of every output element is the one numpy's fp64 product of
+ *     the same fp32 inputs has, and an output element a non-finite input element does not take part in
+ *     is bit-identical to the result without it.  K1 (single and blocks): X[i, j] non-finite makes row
+ *     and column j of G (G[j, j] included) non-finite; K3 / K3 blocks / K3s: an element of A hits one
+ *     row of C, an element of B one column; K2: X[i, k] hits row i of Y, W[k, c] column c, and the
+ *     fused Gram is non-finite exactly where Y^T Y is; the fp32 copies (G32, C32) have the class of the
+ *     fp64 result.  Clamped addresses (rows past m, columns past n or l, padded 16-column granules)
+ *     never carry a value into a result: where a clamped duplicate would meet a zero pad it is replaced
+ *     by zero (Inf * 0 would be NaN).  The host relies on this: it raises LinAlgError when diag(G) or
+ *     the range-finder iterate Z is not finite (svd.py) instead of iterating on NaN.  K5: a NaN in row i
+ *     makes mean[i], std[i] and row i NaN and leaves every other row alone, also the three others of
+ *     its float4.  The small fp64 solvers (K7, K7L, K10) are only called with finite input;
+ *   - a CONSTANT row under K5 with scale: mean[i] is the constant exactly, std[i] is exactly 0 and the
+ *     row becomes 0 / 0 = NaN, as numpy's (x - mean) / std of the reference's standardize_data does
+ *     (slice_tools.py:171-179).  That is the contract, not an accident: the SVD that follows raises
+ *     LinAlgError, it never returns factors of such a matrix.  (The ingest's all-zero filler rows are
+ *     kept away from K5 by the host for this reason.)  Without scale the row becomes exactly 0;
+ *   - magnitudes: the kernels are correct for |x| in [2^-40, 2^40] (products 2^-80 .. 2^80, sums of 2^20
+ *     and more of them stay inside fp32; subnormals are not flushed), which is what the host's magnitude
+ *     guard hands them: it rescales by a power of two only when max|x| leaves that interval.  Inside it a
+ *     power-of-two factor commutes with every rounding: K1 / K3 of 2^e X equal 2^2e times the result for
+ *     X bit for bit, K2 of 2^e X gives 2^e Y and 2^2e G.  All-positive (un-centred) data keep the error
+ *     bound of one fp32 chain of at most 4096 rows + a blocked fp32 sum of at most 16 chain results + fp64
+ *     beyond: ((min(K, 4096) / 2 + 18) 2^-24) sum |a||b|, whatever K is;
+ *   - small integers are exact: while a_A a_B K < 2^24 for operands with integer entries |a| <= a_A,
+ *     |b| <= a_B (K2: n a_X a_W < 2^24; its fused Gram: max|y|^2 m < 2^24) every partial sum is an
+ *     exactly representable integer in any order, and K1 / K3 / K2 return the integer result bit for bit
+ *     in fp64 and in the fp32 copy -- a dropped, repeated or clamped row anywhere in millions of rows
+ *     changes the result.  K5 on integer rows with an integer mean: mean and the centred rows are exact,
+ *     std is the fp64 root rounded to fp32, the scaled row is the correctly rounded fp32 quotient (the
+ *     library is built without fast-math flags).  K6 / K8 / K9 / K11 are exact below 2^53.
  */
 #ifndef DMDX_H
 #define DMDX_H
