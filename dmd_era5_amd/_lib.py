@@ -58,6 +58,11 @@ SIGNATURES = {
     "dmdx_potrf_trtri_workspace_bytes": (_sz, [_i64]),
     "dmdx_potrf_trtri_f64": (C.c_int, [_p, _i64, _i64, C.c_double, _p, _i64, _p, _i64, _p, _p, _sz, _p]),
     "dmdx_gemm_nt_f64": (C.c_int, [_p, _i64, _i64, _i64, _p, _i64, _i64, _p, _i64, _p]),
+    "dmdx_expand_max_k": (C.c_int, []),
+    "dmdx_expand_f32": (C.c_int, [_p, _i64, _i64, _i64, _p, _i64, _i64, _p, _p, _p, _i64, _p]),
+    "dmdx_expand_score_workspace_bytes": (_sz, [_i64, _i64, _i64]),
+    "dmdx_expand_score_f32": (C.c_int, [_p, _i64, _i64, _i64, _p, _i64, _i64, _p, _p, _p, _i64, _p, _p, _p, C.c_int,
+                                        _p, _sz, _p]),
     "dmdx_pack_triu_f64": (C.c_int, [_p, _i64, _i64, _p, _p]),
     "dmdx_unpack_triu_f64": (C.c_int, [_p, _i64, _p, _i64, _p]),
     "dmdx_exp_basis": (C.c_int, [_p, _p, _i64, _i64, _p, _p, C.c_int, _p]),

@@ -55,6 +55,7 @@ __all__ = [
     "retrieve_svd_results",
     "add_config_attributes",
     "main",
+    "reconstruct_from_svd_results",
 ]
 
 logger = setup_logger("ERA5-SVD", "era5_svd.log")
@@ -203,6 +204,58 @@ def combine_svd_results(U, s, V, coords, **kwargs) -> Dataset:
         if kwargs.get(key) is not None:
             ds[key] = kwargs[key]
     return ds
+
+
+def reconstruct_from_svd_results(svd_ds: Dataset, n_components: int | None = None, times=None,
+                                 destandardize: bool = True, kern=None) -> DataArray:
+    """The data matrix of an SVD result, regenerated from its factors: ``U[:, :r] diag(s[:r]) V[:r, times]``
+    as the ``(space, time)`` DataArray the file's own ``X`` variable is (same coordinates and dtype) --
+    what ``save_data_matrix = False`` left out, or its rank-r approximation.
+
+    ``svd_ds``: the Dataset ``main()`` returns or ``retrieve_svd_results`` loads.  ``n_components``: r
+    (default: all stored).  ``times``: indices into the file's time axis (default: all).
+    ``destandardize``: apply ``X_std`` and ``X_mean`` when the file has them (it has them only for a
+    delay embedding d > 1 -- the reference's quirk, ref :400-414 -- so for d = 1 the standardized
+    matrix is what comes back either way).  fp32 results are formed by K12 on the device in row
+    blocks; float64 results (the small-slice fp64 route) take the library's fp64 product."""
+    U, s, V = (np.asarray(svd_ds[k].values) for k in ("U", "s", "V"))
+    k = int(s.shape[0])
+    r = k if n_components is None else int(n_components)
+    if not 1 <= r <= k:
+        raise ValueError(f"n_components = {r} outside 1 .. {k}")
+    tidx = np.arange(V.shape[1]) if times is None else np.atleast_1d(np.asarray(times, dtype=np.int64))
+    names = set(svd_ds.data_vars)
+    mu = np.asarray(svd_ds["X_mean"].values) if destandardize and "X_mean" in names else None
+    sd = np.asarray(svd_ds["X_std"].values) if destandardize and "X_std" in names else None
+    M = int(U.shape[0])
+    if U.dtype == np.float64:
+        X = (U[:, :r] * s[:r]) @ V[:r][:, tidx]
+        if sd is not None:
+            X *= sd[:, None]
+        if mu is not None:
+            X += mu[:, None]
+    else:
+        import torch
+
+        from . import forecast
+        from .svd import _kern, split_rows
+
+        kern = _kern(kern)
+        dev = torch.device("cuda" if getattr(kern, "name", "") == "hip" else "cpu")
+        Ct = forecast.svd_coefficients(torch.from_numpy(s[:r].astype(np.float64)),
+                                       torch.from_numpy(V[:r].astype(np.float64)), torch.from_numpy(tidx)).to(dev)
+        X = np.empty((M, tidx.shape[0]), dtype=U.dtype)
+        for a, b in split_rows(M):
+            Ut = torch.from_numpy(np.ascontiguousarray(U[a:b, :r].T.astype(np.float32, copy=False))).to(dev)
+            vec = [None if v is None else [torch.from_numpy(np.ascontiguousarray(v[a:b], dtype=np.float32))] for v in (mu, sd)]
+            (Xt,) = forecast.expand_blocks([Ut], Ct, vec[0], vec[1], kern=kern)
+            X[a:b] = Xt.T.cpu().numpy()
+            del Xt, Ut
+    row = {c: svd_ds.coords[c] for c in ("space", "original_variable", "delay", "time") if c in svd_ds.coords}
+    if times is not None:
+        tc = svd_ds.coords["time"]
+        row["time"] = Coord("time", np.asarray(tc.values)[tidx])
+    return DataArray(X, ("space", "time"), row)
 
 
 # --------------------------------------------------------------------------------------

@@ -1,0 +1,273 @@
+"""From the rank-k factors back to ERA5 fields: reconstruction, DMD forecast and their score.
+
+``svd.py`` turns a slice into ``U, s, V`` and ``bopdmd.py`` fits the optimized DMD on the reduced
+coordinates ``H = V S``; both stop in the coordinates of ``U``.  This module evaluates
+
+        x(t) = mu + sigma * (U c(t))            on the grid, per row block of U,
+
+with ``c(t)`` either the SVD coefficients ``diag(s) Vh[:, t]`` (the rank-k reconstruction of the
+decomposed snapshots) or the fitted model ``Re(Phi(t) diag(b) modes^T)`` at arbitrary times (the
+forecast), and scores it against real snapshots without materialising the fields: K12
+(``HipKernels.expand`` / ``expand_score``, csrc/expand.hip).
+
+Layout as everywhere in the package (kernels.py): a column-major matrix is held as its row-major
+transpose -- U blocks are ``(k, rows)`` (``SvdResult.Ut``), coefficients ``Ct`` are ``(T, k)``,
+fields and snapshots ``(T, rows)``.  A delay-embedded U block is ``(k, d * rows)`` with delay j in
+columns ``[j * rows, (j + 1) * rows)`` (svd._assemble_rows).
+
+``kern=None`` means the HIP provider, as in svd.py.  A provider WITHOUT ``expand`` (the CPU kernel
+double of the tests) takes the plain torch expression, as ``svd._tn`` does for K9.
+"""
+from __future__ import annotations
+
+from dataclasses import dataclass
+
+import torch
+
+from .bopdmd import OptDMDResult, _phi
+from .svd import Comm, _kern, _pitched, embed_view
+
+__all__ = ["svd_coefficients", "dmd_coefficients", "expand_blocks", "iter_fields", "score_blocks", "DmdForecast"]
+
+
+# ---------------------------------------------------------------------------
+# coefficients c(t), (T, k) fp32
+# ---------------------------------------------------------------------------
+def svd_coefficients(s: torch.Tensor, Vh: torch.Tensor, cols=None) -> torch.Tensor:
+    """``(diag(s) Vh[:, cols])^T`` as (T, k) fp32: the coefficients of the rank-k reconstruction of
+    the snapshots ``cols`` (all of them by default; an index tensor, list or slice)."""
+    V = Vh if cols is None else Vh[:, cols]
+    return (V.to(torch.float64) * s.to(torch.float64)[:, None]).T.to(torch.float32).contiguous()
+
+
+def dmd_coefficients(result: OptDMDResult, t: torch.Tensor) -> tuple[torch.Tensor, float]:
+    """The fitted model at the times ``t`` (inside or beyond the training window) in the coordinates
+    of U: ``(Re(Phi(t) diag(b) modes^T) as (T, n_s) fp32, max|Im| / max|Re|)``.  Phi is formed in
+    complex128 (on the device by dmdx_exp_basis).  The fit does not force conjugate pairs, so the
+    un-projected value has an imaginary part; its relative size says how real the model is."""
+    alpha = result.eigs.to(torch.complex128)
+    tt = torch.as_tensor(t, dtype=torch.float64, device=alpha.device).reshape(-1)
+    phi = _phi(alpha, tt, torch.complex128)
+    Z = (phi * result.amplitudes.to(torch.complex128)) @ result.modes.to(torch.complex128).T
+    re_max = float(Z.real.abs().max()) if Z.numel() else 0.0
+    im_max = float(Z.imag.abs().max()) if Z.numel() else 0.0
+    ratio = im_max / re_max if re_max > 0.0 else (0.0 if im_max == 0.0 else float("inf"))
+    return Z.real.to(torch.float32).contiguous(), ratio
+
+
+# ---------------------------------------------------------------------------
+# one block
+# ---------------------------------------------------------------------------
+def _affine64(Ut, Ct, mean, std):
+    P = Ct.to(torch.float64) @ Ut.to(torch.float64)
+    if std is not None:
+        P = P * std.to(torch.float64)
+    if mean is not None:
+        P = P + mean.to(torch.float64)
+    return P
+
+
+def _expand(kern, Ut, Ct, mean, std, out=None):
+    f = getattr(kern, "expand", None)
+    if f is not None:
+        return f(Ut, Ct, mean, std, out=out)
+    P = _affine64(Ut, Ct, mean, std).to(torch.float32)
+    if out is None:
+        return P
+    out.copy_(P)
+    return out
+
+
+def _expand_score(kern, Ut, Ct, Xt, mean, std, out, want_rows):
+    f = getattr(kern, "expand_score", None)
+    if f is not None:
+        return f(Ut, Ct, Xt, mean, std, out=out, want_rows=want_rows)
+    X = Xt.to(torch.float64)
+    E = X - _affine64(Ut, Ct, mean, std)
+    G = X if mean is None else X - mean.to(torch.float64)
+    cols = torch.stack([(E * E).sum(dim=1), (G * G).sum(dim=1)])
+    if out is not None:
+        out += cols
+        cols = out
+    return cols, ((E * E).sum(dim=0) if want_rows else None)
+
+
+def _vec(v, b, reps, device):
+    """Block b of a list of per-row vectors (or None) as fp32 on ``device``, repeated for every delay."""
+    if v is None:
+        return None
+    x = torch.as_tensor(v[b]).to(device=device, dtype=torch.float32).reshape(-1)
+    return (x.repeat(reps) if reps > 1 else x).contiguous()
+
+
+def _block_rows(Ub, delay, delay_block):
+    """The (k, rows) view of a U block that is expanded, and how often its mean / std repeat."""
+    if delay_block is None:
+        return Ub, delay
+    if not 0 <= delay_block < delay or Ub.shape[1] % delay:
+        raise ValueError(f"delay_block = {delay_block} outside 0 .. {delay - 1}, or a U block whose "
+                         f"{Ub.shape[1]} rows are no multiple of the delay {delay}")
+    mb = Ub.shape[1] // delay
+    return Ub[:, delay_block * mb:(delay_block + 1) * mb], 1
+
+
+# ---------------------------------------------------------------------------
+# lists of row blocks
+# ---------------------------------------------------------------------------
+def expand_blocks(Ublocks, Ct: torch.Tensor, means=None, stds=None, delay_block: int | None = None,
+                  out=None, delay: int = 1, kern=None) -> list[torch.Tensor]:
+    """The fields of every row block: a list of (T, rows) fp32 tensors, ``mean + std * (U c)``.
+
+    ``means`` / ``stds``: lists of per-row vectors of the PHYSICAL rows of every block (None: 0 / 1).
+    ``delay``: the delay embedding U was computed with (d * rows columns per block);
+    ``delay_block = j`` expands the rows of delay j only -- ``delay_block=0`` gives the physical
+    fields at the times of ``Ct`` -- None all d * rows of them.
+    ``out``: a list of (T, rows) fp32 views to write into.
+    Refuses (MemoryError, bytes stated) when the result does not fit the free device memory: use
+    :func:`iter_fields` then."""
+    kern = _kern(kern)
+    Ublocks = list(Ublocks)
+    views = [_block_rows(U, delay, delay_block) for U in Ublocks]
+    T = int(Ct.shape[0])
+    if out is None:
+        need = 4 * T * sum(int(U.shape[1]) for U, _ in views)
+        dev = Ublocks[0].device
+        if dev.type == "cuda":
+            free = torch.cuda.mem_get_info(dev)[0] + max(
+                0, torch.cuda.memory_reserved(dev) - torch.cuda.memory_allocated(dev))
+            if need > free:
+                raise MemoryError(f"expand_blocks: the fields need {need} bytes ({T} snapshots x "
+                                  f"{need // (4 * max(T, 1))} rows, fp32) and {free} bytes of device memory are "
+                                  "free; expand time chunks with iter_fields(..., chunk=)")
+    Cp = _pitched(kern, Ct)
+    res = []
+    for b, (U, reps) in enumerate(views):
+        res.append(_expand(kern, U, Cp, _vec(means, b, reps, U.device), _vec(stds, b, reps, U.device),
+                           out=None if out is None else out[b]))
+    return res
+
+
+def iter_fields(Ublocks, Ct: torch.Tensor, means=None, stds=None, delay_block: int | None = None,
+                delay: int = 1, chunk: int = 256, kern=None):
+    """Time-chunked :func:`expand_blocks`: yields ``(t0, t1, blocks)`` with the fields of the
+    coefficients ``Ct[t0:t1]``; every chunk reuses the buffers of the one before (copy what you keep)."""
+    if chunk < 1:
+        raise ValueError("iter_fields: chunk >= 1")
+    Ublocks = list(Ublocks)
+    bufs = None
+    T = int(Ct.shape[0])
+    for t0 in range(0, T, chunk):
+        t1 = min(T, t0 + chunk)
+        o = None if bufs is None else [B[:t1 - t0] for B in bufs]
+        blocks = expand_blocks(Ublocks, Ct[t0:t1], means, stds, delay_block, out=o, delay=delay, kern=kern)
+        if bufs is None:
+            bufs = blocks
+        yield t0, t1, blocks
+
+
+def score_blocks(Ublocks, Ct: torch.Tensor, Xblocks, means=None, stds=None, delay: int = 1,
+                 comm: Comm | None = None, want_rows: bool = False, kern=None) -> dict:
+    """How well ``mean + std * (U c)`` matches the snapshots, without storing it.
+
+    ``Xblocks``: the (n, rows) snapshot blocks that belong to ``Ublocks`` (any iterable, consumed
+    once in order: a streamed X accumulates block after block); with ``delay`` d > 1 the
+    zero-copy embedded view (n - d + 1, d * rows) of every block is scored, and ``Ct`` has
+    n - d + 1 rows.  Returns per snapshot ``sse``, ``ref`` (= sum_i (x - mean)^2), ``rel_error`` =
+    sqrt(sse / ref) and ``rmse``, the totals ``sse_total``, ``ref_total``, ``rel_error_total``,
+    ``rmse_total``, ``rows`` (global), and with ``want_rows`` the list ``row_rmse`` of per-row RMSE
+    vectors of the local blocks.
+
+    Row shards: ONE ``comm.allreduce_sum_`` of the stacked per-snapshot vectors per call, whatever
+    the number of local blocks (ranks hold different numbers of them)."""
+    kern = _kern(kern)
+    comm = comm or Comm()
+    T = int(Ct.shape[0])
+    Cp = _pitched(kern, Ct)
+    cols, rows_local, row_sse = None, 0, []
+    for b, (U, X) in enumerate(zip(Ublocks, Xblocks, strict=True)):   # (a streamed X that ends early is an error)
+        E = embed_view(X, delay)
+        if E.shape != (T, U.shape[1]):
+            raise ValueError(f"score_blocks: block {b} of X is {tuple(E.shape)} (delay {delay}), U and Ct ask for "
+                             f"{(T, int(U.shape[1]))}")
+        c, r = _expand_score(kern, U, Cp, E, _vec(means, b, delay, U.device), _vec(stds, b, delay, U.device),
+                             cols, want_rows)
+        cols = c
+        rows_local += int(U.shape[1])
+        if want_rows:
+            row_sse.append(r)
+    if cols is None:        # a rank without blocks still takes part in the collective
+        cols = torch.zeros((2, T), dtype=torch.float64, device=Ct.device)
+    flat = torch.cat([cols.reshape(-1), torch.tensor([float(rows_local)], dtype=torch.float64, device=cols.device)])
+    flat = comm.allreduce_sum_(flat, tag="score_allreduce")
+    sse, ref, rows = flat[:T], flat[T:2 * T], float(flat[2 * T])
+    sse_total, ref_total = sse.sum(), ref.sum()
+    res = {
+        "sse": sse, "ref": ref, "rel_error": torch.sqrt(sse / ref), "rmse": torch.sqrt(sse / rows),
+        "sse_total": float(sse_total), "ref_total": float(ref_total),
+        "rel_error_total": float(torch.sqrt(sse_total / ref_total)),
+        "rmse_total": float(torch.sqrt(sse_total / (rows * T))), "rows": int(rows),
+    }
+    if want_rows:
+        res["row_rmse"] = [torch.sqrt(r / T) for r in row_sse]
+    return res
+
+
+# ---------------------------------------------------------------------------
+# the bundle a user holds
+# ---------------------------------------------------------------------------
+@dataclass
+class DmdForecast:
+    """U blocks + pre-processing + a fitted optimized DMD: fields and scores at any times.
+
+    ``Ublocks``: (k, d * rows) blocks of the left singular vectors; ``means`` / ``stds``: per-row
+    vectors of the physical rows of every block, or None; ``delay``: d; ``result``: the
+    :class:`OptDMDResult` fitted on ``reduced_coordinates(s, Vh)``; ``s`` / ``Vh``: the SVD factors
+    (only :meth:`reconstruct_svd` needs them)."""
+
+    Ublocks: list
+    result: OptDMDResult | None = None
+    means: list | None = None
+    stds: list | None = None
+    delay: int = 1
+    s: torch.Tensor | None = None
+    Vh: torch.Tensor | None = None
+    kern: object = None
+
+    def coefficients(self, t) -> tuple[torch.Tensor, float]:
+        if self.result is None:
+            raise ValueError("DmdForecast: no fitted DMD result")
+        Ct, imag = dmd_coefficients(self.result, t)
+        k = int(self.Ublocks[0].shape[0])
+        if Ct.shape[1] != k:
+            raise ValueError(f"DmdForecast: the DMD was fitted on {Ct.shape[1]} coordinates, U has {k} columns")
+        return Ct.to(self.Ublocks[0].device), imag
+
+    def fields(self, t, delay_block: int | None = 0, out=None) -> list[torch.Tensor]:
+        """The model's fields at the times ``t``: (len(t), rows) per block; ``delay_block=0`` (the
+        default) the physical rows, None all d * rows of the embedding."""
+        if self.delay == 1:
+            delay_block = None
+        return expand_blocks(self.Ublocks, self.coefficients(t)[0], self.means, self.stds, delay_block, out=out,
+                             delay=self.delay, kern=self.kern)
+
+    def score(self, Xblocks, t, comm: Comm | None = None, want_rows: bool = False) -> dict:
+        """:func:`score_blocks` of the model at the times ``t`` of the snapshots ``Xblocks`` (with a
+        delay d the blocks hold len(t) + d - 1 snapshots); ``imag_ratio`` is added to the result."""
+        Ct, imag = self.coefficients(t)
+        res = score_blocks(self.Ublocks, Ct, Xblocks, self.means, self.stds, self.delay, comm, want_rows, self.kern)
+        res["imag_ratio"] = imag
+        return res
+
+    def reconstruct_svd(self, n_components: int | None = None, cols=None, delay_block: int | None = 0,
+                        out=None) -> list[torch.Tensor]:
+        """The rank-``n_components`` SVD reconstruction of the decomposed snapshots ``cols``."""
+        if self.s is None or self.Vh is None:
+            raise ValueError("DmdForecast.reconstruct_svd needs s and Vh")
+        k = int(self.s.numel()) if n_components is None else int(n_components)
+        if not 1 <= k <= int(self.s.numel()):
+            raise ValueError(f"n_components = {k} outside 1 .. {int(self.s.numel())}")
+        Ct = svd_coefficients(self.s[:k], self.Vh[:k], cols).to(self.Ublocks[0].device)
+        if self.delay == 1:
+            delay_block = None
+        return expand_blocks([U[:k] for U in self.Ublocks], Ct, self.means, self.stds, delay_block, out=out,
+                             delay=self.delay, kern=self.kern)

@@ -253,6 +253,71 @@ class HipKernels:
         _lib.check(rc, "dmdx_gemm_nn_skinny_f32")
         return Yt
 
+    # -- K12 ----------------------------------------------------------------
+    @property
+    def expand_max_k(self) -> int:
+        return int(self._lib.dmdx_expand_max_k())
+
+    def _expand_args(self, Ut, Ct, mean, std, who):
+        m, k, ldu = _check_mat(Ut, torch.float32, f"{who} U")
+        kc, T, _ = _check_mat(Ct, torch.float32, f"{who} C")
+        if kc != k:
+            raise _lib.DmdxError(f"{who}: C has {kc} rows, U has {k} columns")
+        Ct = self.pitch(Ct)
+        ldc = _check_mat(Ct, torch.float32, f"{who} C")[2]
+        for v, name in ((mean, "mean"), (std, "std")):
+            if v is not None and (v.dtype != torch.float32 or v.shape != (m,) or v.device != Ut.device
+                                  or not v.is_contiguous()):
+                raise _lib.DmdxError(f"{who}: {name} must be a contiguous fp32 vector of length {m} on {Ut.device}")
+        return m, k, ldu, T, Ct, ldc
+
+    def expand(self, Ut: torch.Tensor, Ct: torch.Tensor, mean: torch.Tensor | None = None,
+               std: torch.Tensor | None = None, out: torch.Tensor | None = None) -> torch.Tensor:
+        """Xhat = mean + std * (U C).  Ut: (k, m), Ct: (T, k) fp32, mean / std: (m,) fp32 or None
+        -> Xt: (T, m) fp32, the layout of a snapshot block.
+
+        ``out``: a (T, m) fp32 view to write into (inner stride 1, any row stride >= m)."""
+        m, k, ldu, T, Ct, ldc = self._expand_args(Ut, Ct, mean, std, "expand")
+        if out is not None:
+            mo, To, ldxh = _check_mat(out, torch.float32, "expand out")
+            if (mo, To) != (m, T) or out.device != Ut.device:
+                raise _lib.DmdxError(f"expand: out must be ({T}, {m}) on {Ut.device}, got {tuple(out.shape)}")
+            Xt = out
+        else:
+            Xt, ldxh = torch.empty((T, m), dtype=torch.float32, device=Ut.device), m
+        rc = self._timed("expand", (m, k, T), lambda: self._lib.dmdx_expand_f32(
+            _ptr(Ut), m, k, ldu, _ptr(Ct), ldc, T, _ptr(mean), _ptr(std), _ptr(Xt), ldxh, self._stream()
+        ))
+        _lib.check(rc, "dmdx_expand_f32")
+        return Xt
+
+    def expand_score(self, Ut: torch.Tensor, Ct: torch.Tensor, Xt: torch.Tensor, mean: torch.Tensor | None = None,
+                     std: torch.Tensor | None = None, out: torch.Tensor | None = None, want_rows: bool = False):
+        """Squared error of Xhat = mean + std * (U C) against X, Xhat never stored.  Ut: (k, m),
+        Ct: (T, k), Xt: (T, m) fp32 (the delay view included) -> (cols, rows): ``cols`` a (2, T) fp64
+        tensor, row 0 = sum_i (X - Xhat)^2, row 1 = sum_i (X - mean)^2 per snapshot; ``rows`` the (m,)
+        fp64 sum_t (X - Xhat)^2 per space point, or None.
+
+        ``out``: a contiguous (2, T) fp64 tensor the column sums are ADDED to (row blocks of X)."""
+        m, k, ldu, T, Ct, ldc = self._expand_args(Ut, Ct, mean, std, "expand_score")
+        mx, Tx, ldx = _check_mat(Xt, torch.float32, "expand_score X")
+        if (mx, Tx) != (m, T) or Xt.device != Ut.device:
+            raise _lib.DmdxError(f"expand_score: X must be ({T}, {m}) on {Ut.device}, got {tuple(Xt.shape)}")
+        if out is not None:
+            if out.shape != (2, T) or out.dtype != torch.float64 or not out.is_contiguous() or out.device != Ut.device:
+                raise _lib.DmdxError(f"expand_score: out must be a contiguous (2, {T}) fp64 tensor on {Ut.device}")
+            cols = out
+        else:
+            cols = torch.empty((2, T), dtype=torch.float64, device=Ut.device)
+        rows = torch.empty(m, dtype=torch.float64, device=Ut.device) if want_rows else None
+        ws = self._workspace(Ut.device, self._lib.dmdx_expand_score_workspace_bytes(m, k, T))
+        rc = self._timed("expand_score", (m, k, T), lambda: self._lib.dmdx_expand_score_f32(
+            _ptr(Ut), m, k, ldu, _ptr(Ct), ldc, T, _ptr(mean), _ptr(std), _ptr(Xt), ldx, cols[0].data_ptr(),
+            cols[1].data_ptr(), _ptr(rows), int(out is not None), _ptr(ws), ws.numel(), self._stream()
+        ))
+        _lib.check(rc, "dmdx_expand_score_f32")
+        return cols, rows
+
     # -- K5 -----------------------------------------------------------------
     def row_center_scale_(self, Xt: torch.Tensor, scale: bool):
         """In place: subtract the per-space-point mean over time (and divide by the

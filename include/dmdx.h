@@ -47,7 +47,14 @@
  *     DMDX_E_INVALID otherwise; their outputs and K6 / K7 / K7L / K10 take any leading dimension;
  *   - leading dimensions of K1 / K3 operands: < 2^25 on the single entry points, < 2^24 per block
  *     on the blocks entry points, DMDX_E_UNSUPPORTED beyond; K2: m + 4 ldx < 2^29
- *     (DMDX_E_INVALID beyond).
+ *     (DMDX_E_INVALID beyond);
+ *   - K12 (dmdx_expand_f32, dmdx_expand_score_f32): U, C, mu, sigma and X are only read, inside their
+ *     logical elements (U: m x k, C: k x T, X: m x T with rows > ldx allowed); every logical element of
+ *     Xhat, sse_row and -- with accumulate == 0 -- sse_col / ref_col is written, nothing else.  Xhat, X,
+ *     U, mu and sigma are addressed with 64-bit offsets and one dword per lane: no alignment is asked
+ *     for and none selects another path; a 16-byte aligned C with ldc % 4 == 0 is staged with 16-byte
+ *     loads.  m, T and every leading dimension must be < 2^31 (DMDX_E_INVALID beyond, before anything
+ *     is written).
  *
  * Value contract (tests/test_gpu_value_domain.py holds every fp32 entry point to it)
  *   - NaN / Inf propagate like IEEE arithmetic on the logical operands, nothing more and nothing less:
@@ -63,6 +70,10 @@
  *     the range-finder iterate Z is not finite (svd.py) instead of iterating on NaN.  K5: a NaN in row i
  *     makes mean[i], std[i] and row i NaN and leaves every other row alone, also the three others of
  *     its float4.  The small fp64 solvers (K7, K7L, K10) are only called with finite input;
+ *     K12: U[i, j] hits row i of Xhat, C[j, t] column t, mu[i] / sigma[i] row i; k is padded to a
+ *     multiple of 16 with zeros in U AND in C (0 * 0), so an Inf in the last column of U meets no pad.  In
+ *     the score a non-finite X[i, t] makes exactly sse_col[t], ref_col[t] and sse_row[i] non-finite, and
+ *     a non-finite Xhat[i, t] does the same to sse_col[t] and sse_row[i];
  *   - a CONSTANT row under K5 with scale: mean[i] is the constant exactly, std[i] is exactly 0 and the
  *     row becomes 0 / 0 = NaN, as numpy's (x - mean) / std of the reference's standardize_data does
  *     (slice_tools.py:171-179).  That is the contract, not an accident: the SVD that follows raises
@@ -82,6 +93,9 @@
  *     changes the result.  K5 on integer rows with an integer mean: mean and the centred rows are exact,
  *     std is the fp64 root rounded to fp32, the scaled row is the correctly rounded fp32 quotient (the
  *     library is built without fast-math flags).  K6 / K8 / K9 / K11 are exact below 2^53.
+ *     K12: k a_U a_C < 2^24 gives the integer U C bit for bit, and with integer sigma, mu and X (every
+ *     intermediate below 2^24) Xhat, sse_col, ref_col and sse_row are the integer results; a power-of-two
+ *     factor on U and its inverse on C leave every output bit unchanged (magnitudes as above).
  */
 #ifndef DMDX_H
 #define DMDX_H
@@ -268,6 +282,33 @@ int dmdx_potrf_trtri_f64(const double* A, int64_t n, int64_t lda, double shift, 
 int dmdx_gemm_nt_f64(const double* Q, int64_t ldq, int64_t n, int64_t b1, const double* Mt, int64_t ldm,
                      int64_t b2, double* Y, int64_t ldy, void* stream);
 
+/* ---- K12: full fields from the rank-k factors, Xhat = mu + sigma .* (U C), and their score ------------------
+ * The step from the reduced coordinates back to ERA5 fields: U (m x k, ldu) are the left singular vectors
+ * (np.linalg.svd / randomized_svd, era5_svd.py:251,258), C (k x T, ldc) the coefficients of T snapshots
+ * (diag(s) Vh for the rank-k reconstruction, the optimized-DMD model evaluated at T times for a forecast),
+ * mu / sigma (m floats each, nullable: 0 / 1) undo slice_tools.py:171-179.  1 <= k <= dmdx_expand_max_k() (256).
+ *   Xhat[i, t] = mu[i] + sigma[i] * sum_j U[i, j] C[j, t]        (m x T, ldxh)
+ * One fp32 MFMA chain over k (any order), then sigma * acc + mu in fp32.
+ *
+ * dmdx_expand_score_f32 forms the same Xhat, never stores it, and compares it with X (m x T, ldx; rows > ldx
+ * allowed, the zero-copy delay view):
+ *   sse_col[t] (+)= sum_i (X[i,t] - Xhat[i,t])^2     T doubles, required
+ *   ref_col[t] (+)= sum_i (X[i,t] - mu[i])^2         T doubles, nullable
+ *   sse_row[i]  =  sum_t (X[i,t] - Xhat[i,t])^2      m doubles, nullable, always overwritten
+ * accumulate != 0 adds to sse_col / ref_col (X and U given as row blocks).  Squared residuals are summed in
+ * fp32 over at most DMDX_EXPAND_FP32_ROWS rows (columns: the rows of one workgroup; rows: 16 snapshots) and
+ * in fp64 beyond, through per-workgroup partial slots in the workspace and reduce kernels: no atomics, the
+ * order of every sum depends on (m, T) only, results are bit-wise reproducible.  X is read once. */
+#define DMDX_EXPAND_FP32_ROWS 128
+int dmdx_expand_max_k(void);
+int dmdx_expand_f32(const float* U, int64_t m, int64_t k, int64_t ldu, const float* C, int64_t ldc, int64_t T,
+                    const float* mu, const float* sigma, float* Xhat, int64_t ldxh, void* stream);
+size_t dmdx_expand_score_workspace_bytes(int64_t m, int64_t k, int64_t T);
+int dmdx_expand_score_f32(const float* U, int64_t m, int64_t k, int64_t ldu, const float* C, int64_t ldc, int64_t T,
+                          const float* mu, const float* sigma, const float* X, int64_t ldx,
+                          double* sse_col, double* ref_col, double* sse_row, int accumulate,
+                          void* workspace, size_t workspace_bytes, void* stream);
+
 /* ---- upper triangle of a symmetric fp64 matrix <-> packed row by row ---------------------
  * packed[i (2n - i + 1) / 2 + (j - i)] = A[i][j], j >= i: what the Gram all-reduce of the
  * row-sharded path moves (n (n + 1) / 2 doubles instead of n^2).  unpack writes both triangles. */
@@ -284,7 +325,7 @@ int dmdx_exp_basis(const double* alpha, const double* t, int64_t n, int64_t r, v
 
 /* ---- measurement aid (not on the path): sustained core clock of the Gram launches ----------
  * While dev_counters3 (3 device uint64, caller-zeroed) is set, every workgroup of the batched
- * launches (dmdx_syrk_blocks_f32, dmdx_gemm_tn_blocks_f32) and of dmdx_gemm_nn_skinny_f32 adds its
+ * launches (dmdx_syrk_blocks_f32, dmdx_gemm_tn_blocks_f32), of dmdx_gemm_nn_skinny_f32 and of K12 adds its
  * core-clock cycles (s_memtime), its 100 MHz reference ticks
  * (s_memrealtime) and 1 to it: clock = 100 MHz * [0] / [1].  NULL (the default) switches the
  * stamps off again; bench.py's calibration block is the only caller. */
