@@ -34,16 +34,20 @@
 // the 64 blocks of a group of 512 that land on one XCD (blockIdx % 8 equal)
 // take one patch (xcd_unit).
 //
-// Entry points: dmdx_syrk_f32 / dmdx_gemm_tn_f32 (one pair of operands per launch) and
-// dmdx_syrk_blocks_f32 / dmdx_gemm_tn_blocks_f32 (the sum over up to 16 row blocks per
-// launch, syrk_batch_kernel); all of them run tn_unit, the reduce kernel sums the K-splits.
-// Environment knobs (tuning / diagnosis only): DMDX_TN_MAX_CPS (chunks per unit, default 2048),
-// DMDX_TN_ROUNDS (rounds of 512 workgroups the K-splits aim at), DMDX_TN_ABLATE (timing-only
-// ablations of the single-launch kernel: results are wrong).
+// Entry points: dmdx_syrk_blocks_f32 / dmdx_gemm_tn_blocks_f32 (the sum over up to 16 row blocks per
+// launch) and dmdx_syrk_f32 / dmdx_gemm_tn_f32 (one pair of operands: a batch of one block).  One
+// path for all four: tn_refusal, run_batch, syrk_batch_kernel (body tn_unit), and the reduce kernel
+// that sums the K-splits; dmdx_gemm_tn_blocks_f32 alone also takes the small-l kernel (K3s).
+// Environment knobs (tuning / A-B only, no result changes beyond rounding): DMDX_TN_MAX_CPS (chunks
+// per unit, default 2048), DMDX_TN_ROUNDS (rounds of 512 workgroups the K-splits aim at),
+// DMDX_TN_FORCE_TM, DMDX_TN_NO_TAILFIT, DMDX_NO_K3S, DMDX_K3S_32.  The timing-only ablations of
+// tn_unit (results are wrong) are a compile-time macro of the diagnostic build, DMDX_TN_ABL
+// (`make stamps ABL=2`): the product library has no such switch.
 #include <stdarg.h>
 #include <stdio.h>
 #include <stdlib.h>
 
+#include <algorithm>
 #include <vector>
 
 #include "dmdx_common.h"
@@ -134,14 +138,14 @@ __device__ __host__ inline void decode_tri(int t, int nt, int& ta, int& tb) {
   }
 }
 
-__device__ inline void decode_tile(const TnParams& p, int t, int& ta, int& tb) {
-  if (p.syrk) {
-    decode_tri(t, p.ntr, ta, tb);
+__device__ inline void decode_tile(int syrk, int ntr, int ntc, int t, int& ta, int& tb) {
+  if (syrk) {
+    decode_tri(t, ntr, ta, tb);
   } else {  // SR-row super-rows, column-major inside (same patch idea)
-    int per_sr = SR * p.ntc;
+    int per_sr = SR * ntc;
     int sr = t / per_sr;
     int r0 = sr * SR;
-    int nrows = p.ntr - r0 < SR ? p.ntr - r0 : SR;
+    int nrows = ntr - r0 < SR ? ntr - r0 : SR;
     int tt = t - sr * per_sr;
     tb = tt / nrows;
     ta = r0 + tt % nrows;
@@ -187,7 +191,8 @@ __device__ unsigned long long dmdx_stamp[12];   // [8] unit prologue, [9] partia
 //              bases and leading dimensions); the K-tail chunk goes through registers.
 // DMA = false: everything register-staged with scalar loads (any alignment).
 // ABL: timing-only ablations for diagnosis (results are wrong when ABL != 0):
-//   1 no global->LDS staging, 2 no barrier, 8 no chain fold (none of them changes an address).  Selected by DMDX_TN_ABLATE.
+//   1 no global->LDS staging, 2 no barrier, 8 no chain fold (none of them changes an address), or their sum.  Set for
+//   every unit of a diagnostic build by the macro DMDX_TN_ABL (`make stamps ABL=2`); the product is built with 0.
 // SK ("skinny rows", 0 / 1 / 2 / 3): a (32 SK) x 128 output tile, the four waves side by side (each
 //   32 SK rows x 32 columns = SK x 1 MFMA blocks) -- for D with few rows (Z = X^T Y with l <= 32,
 //   <= 64 or <= 96 columns of Y): a quarter / half / three quarters of the MFMA work of a 128-row
@@ -605,21 +610,13 @@ __device__ __forceinline__ int xcd_unit(int b, int total) {
   return ((g << 9) + 512 <= total) ? (g << 9) + (b & 7) * 64 + ((b & 511) >> 3) : b;
 }
 
-template <bool DMA, int ABL = 0, int SK = 0, int H16 = 0>
-__global__ __launch_bounds__(NTH, 2) void gemm_tn_partial_kernel(TnParams p) {
-  constexpr int TM = SK ? 32 * SK + 16 * H16 : BT;
-  __shared__ __attribute__((aligned(16))) float lds[2 * (TM + BT) * BK];
-  const int pos = xcd_unit(blockIdx.x, gridDim.x);
-  const int split = pos / p.ntiles;
-  const int tile = pos - split * p.ntiles;
-  int ta, tb;
-  decode_tile(p, tile, ta, tb);
-  double* Pt = p.P + ((size_t)split * p.ntiles + tile) * (TM * BT);
-  tn_unit<DMA, ABL, SK, H16>(p, split, ta * TM, tb * BT, Pt, lds);
-}
+#ifndef DMDX_TN_ABL
+#define DMDX_TN_ABL 0   // timing-only ablations of tn_unit: the diagnostic build alone sets it (csrc/Makefile)
+#endif
 
 // D (+)= sum_j A_j^T B_j over a batch of row blocks (TnBatch); p carries what the blocks share
-// (shape of D, tiles, P).  SYRK: A_j == B_j, triangle tiles.
+// (shape of D, tiles, P).  SYRK: A_j == B_j, triangle tiles.  A single product is the batch of one
+// block: unit_begin = {0, units}, slab_begin = {0, nsplit}, no padding.
 template <bool DMA, int SK = 0, int H16 = 0>
 __global__ __launch_bounds__(NTH, 2) void syrk_batch_kernel(TnParams p, TnBatch bt) {
   constexpr int TM = SK ? 32 * SK + 16 * H16 : BT;
@@ -634,7 +631,7 @@ __global__ __launch_bounds__(NTH, 2) void syrk_batch_kernel(TnParams p, TnBatch 
   const int split = pos / p.ntiles;
   const int tile = pos - split * p.ntiles;
   int ta, tb;
-  decode_tile(p, tile, ta, tb);
+  decode_tile(p.syrk, p.ntr, p.ntc, tile, ta, tb);
   p.A = bt.A[j];
   p.B = bt.B[j];
   p.lda = bt.lda[j];
@@ -650,7 +647,7 @@ __global__ __launch_bounds__(NTH, 2) void syrk_batch_kernel(TnParams p, TnBatch 
     c0 = __builtin_amdgcn_s_memtime();
     r0 = __builtin_amdgcn_s_memrealtime();
   }
-  tn_unit<DMA, 0, SK, H16>(p, split, ta * TM, tb * BT, Pt, lds);
+  tn_unit<DMA, DMDX_TN_ABL, SK, H16>(p, split, ta * TM, tb * BT, Pt, lds);
   if (bt.clk != nullptr) {
     const unsigned long long c1 = __builtin_amdgcn_s_memtime(), r1 = __builtin_amdgcn_s_memrealtime();
     if (threadIdx.x == 0) {
@@ -674,17 +671,7 @@ __global__ __launch_bounds__(256) void gemm_tn_reduce_kernel(
   const int sb = blockIdx.x - tile * nsb;
   const int tile_elems = tm * BT;
   int ta, tb;
-  if (syrk) {
-    decode_tri(tile, ntr, ta, tb);
-  } else {
-    int per_sr = SR * ntc;
-    int sr = tile / per_sr;
-    int r0 = sr * SR;
-    int nrows = ntr - r0 < SR ? ntr - r0 : SR;
-    int tt = tile - sr * per_sr;
-    tb = tt / nrows;
-    ta = r0 + tt % nrows;
-  }
+  decode_tile(syrk, ntr, ntc, tile, ta, tb);
   const int row0 = ta * tm, col0 = tb * BT;
   const int tx = threadIdx.x & 31, ty = threadIdx.x >> 5;  // 32 x 8
   const bool diag = syrk && (ta == tb);
@@ -737,8 +724,28 @@ struct Plan {
              // plain product X^T X instead (both triangles computed: half / three quarters of the MFMA
              // work of the 128 x 128 tile, no mirror pass)
   int ntr, ntc, ntiles, nsplit, chunks_total, chunks_per_split;
-  size_t ws_bytes;
 };
+
+// The tail of a launch: its units are equally long and 512 of them are resident, so a launch of
+// r = units / 512 rounds takes ceil(r) of them.  With few rounds, take the split count in (want, hi]
+// that fills the last round best; the first one that fills it to 97 % wins.  Only when the wanted
+// count leaves the last round less than 92 % full (measurements: make_plan, xty_small_plan).
+// units_per_split: tiles x blocks of the launch; a block of no chunk has no units and keeps `want`.
+int64_t fit_last_round(int64_t chunks, int64_t units_per_split, int64_t want, int64_t hi) {
+  if (getenv("DMDX_TN_NO_TAILFIT") != nullptr) return want;
+  auto fill = [&](int64_t w) {
+    const int64_t cps = (chunks + w - 1) / w;
+    const int64_t ns = cps > 0 ? (chunks + cps - 1) / cps : 0;
+    const double r = (double)(units_per_split * ns) / 512.0;
+    return r > 0.0 ? r / (double)(int64_t)(r + 0.999999) : 1.0;
+  };
+  int64_t best = want;
+  double bf = fill(want);
+  if (bf < 0.92)
+    for (int64_t w = want + 1; bf < 0.97 && w <= hi; ++w)
+      if (fill(w) > bf) { bf = fill(w); best = w; }
+  return best;
+}
 
 // share: number of equally sized row blocks that share the launch (batched SYRK)
 Plan make_plan(int64_t K, int64_t nrow, int64_t ncol, int syrk, int share = 1) {
@@ -797,106 +804,40 @@ Plan make_plan(int64_t K, int64_t nrow, int64_t ncol, int syrk, int share = 1) {
   // Only when the wanted count leaves the last round less than 92 % full: measured on 16 cfg4 blocks
   // (n = 3653) l = 70 11.58 -> 11.09 ms, l = 100 15.14 -> 14.24, l = 220 30.07 -> 27.95; on 8 cfg2 blocks
   // (n = 8760, last round 92.4 % full as it is) twice the splits cost 2 % (l = 60 10.60 -> 10.82 ms).
-  if (getenv("DMDX_TN_NO_TAILFIT") == nullptr) {
-    auto fill = [&](int64_t w) {
-      const int64_t cps = (pl.chunks_total + w - 1) / w;
-      const int64_t ns = (pl.chunks_total + cps - 1) / cps;
-      const double r = (double)(per_split * ns) / 512.0;
-      return r / (double)(int64_t)(r + 0.999999);
-    };
-    int64_t best = want;
-    double bf = fill(want);
-    if (bf < 0.92)
-      for (int64_t w = want + 1; bf < 0.97 && w <= maxs && w <= 256 && w <= 2 * want + 2; ++w)
-        if (fill(w) > bf) { bf = fill(w); best = w; }
-    want = best;
-  }
+  want = fit_last_round(pl.chunks_total, per_split, want, std::min({maxs, (int64_t)256, 2 * want + 2}));
   pl.chunks_per_split = (int)((pl.chunks_total + want - 1) / want);
   pl.nsplit = (pl.chunks_total + pl.chunks_per_split - 1) / pl.chunks_per_split;
-  pl.ws_bytes = (size_t)pl.nsplit * pl.ntiles * pl.tm * BT * sizeof(double);
   return pl;
 }
 
-int run_tn(const float* A, int64_t lda, const float* B, int64_t ldb, int64_t K, int64_t nrow,
-           int64_t ncol, int syrk, double* D64, int64_t ld64, float* D32, int64_t ld32,
-           int accumulate, void* ws, size_t ws_bytes, hipStream_t stream) {
-  Plan pl = make_plan(K, nrow, ncol, syrk);
-  if (ws == nullptr || ws_bytes < pl.ws_bytes) {
-    dmdx_set_error("gemm_tn: workspace %zu bytes < required %zu", ws_bytes, pl.ws_bytes);
-    return DMDX_E_WORKSPACE;
-  }
-  TnParams p;
-  p.A = A; p.B = B; p.lda = lda; p.ldb = ldb; p.K = K;
-  p.nrow = (int)nrow; p.ncol = (int)ncol;
-  p.ntr = pl.ntr; p.ntc = pl.ntc; p.ntiles = pl.ntiles; p.syrk = pl.syrk;
-  p.nsplit = pl.nsplit; p.chunks_total = pl.chunks_total;
-  p.chunks_per_split = pl.chunks_per_split;
-  p.P = reinterpret_cast<double*>(ws);
-  // per-lane offsets inside a 128-column panel are 32-bit: elements on the register path,
-  // bytes (+ 4 KiB of slack) on the LDS-DMA path
-  if (lda >= (int64_t(1) << 25) || ldb >= (int64_t(1) << 25)) {
-    dmdx_set_error("gemm_tn: leading dimension %lld / %lld >= 2^25 not supported", (long long)lda, (long long)ldb);
-    return DMDX_E_UNSUPPORTED;
-  }
-  const bool aligned = (lda % 4 == 0) && (ldb % 4 == 0) && dmdx_aligned16(A) && dmdx_aligned16(B) &&
-                       lda < (int64_t(1) << 22) && ldb < (int64_t(1) << 22);
-  dim3 grid((unsigned)((size_t)pl.nsplit * pl.ntiles));
-  int abl = 0;
-  if (const char* e = getenv("DMDX_TN_ABLATE")) abl = atoi(e);
-  if (pl.tm != BT) abl = 0;
-  if (aligned && abl == 1)
-    hipLaunchKernelGGL((gemm_tn_partial_kernel<true, 1>), grid, dim3(NTH), 0, stream, p);
-  else if (aligned && abl == 2)
-    hipLaunchKernelGGL((gemm_tn_partial_kernel<true, 2>), grid, dim3(NTH), 0, stream, p);
-  else if (aligned && abl == 8)
-    hipLaunchKernelGGL((gemm_tn_partial_kernel<true, 8>), grid, dim3(NTH), 0, stream, p);
-  else if (aligned && abl == 11)
-    hipLaunchKernelGGL((gemm_tn_partial_kernel<true, 11>), grid, dim3(NTH), 0, stream, p);
-  else if (pl.tm != BT) {  // skinny tiles (LDS-DMA staging needs 16-byte aligned column starts)
-#define DMDX_TN_CASE(TMV, SKV, HV)                                                                          \
-    case TMV:                                                                                               \
-      if (aligned) hipLaunchKernelGGL((gemm_tn_partial_kernel<true, 0, SKV, HV>), grid, dim3(NTH), 0, stream, p);  \
-      else hipLaunchKernelGGL((gemm_tn_partial_kernel<false, 0, SKV, HV>), grid, dim3(NTH), 0, stream, p);  \
-      break
-    switch (pl.tm) {
-      DMDX_TN_CASE(32, 1, 0); DMDX_TN_CASE(48, 1, 1); DMDX_TN_CASE(64, 2, 0); DMDX_TN_CASE(80, 2, 1);
-      DMDX_TN_CASE(96, 3, 0); DMDX_TN_CASE(112, 3, 1);
-      default: dmdx_set_error("gemm_tn: no kernel for tile height %d", pl.tm); return DMDX_E_INVALID;
+// ---- batched products: D (+)= sum_j A_j^T B_j, blocks in groups of MAXB per launch: the blocks
+// [j0, j0 + group_len) share one
+inline int group_len(int nblocks, int j0) { return std::min(nblocks - j0, MAXB); }
+
+// partial tiles of the largest launch
+size_t batch_ws(const int64_t* K, int nblocks, int64_t nrow, int64_t ncol, int syrk) {
+  size_t need = 0;
+  for (int j0 = 0; j0 < nblocks; j0 += MAXB) {
+    const int nb = group_len(nblocks, j0);
+    size_t slabs = 0;
+    Plan pl{};
+    for (int j = 0; j < nb; ++j) {
+      pl = make_plan(K[j0 + j], nrow, ncol, syrk, nb);
+      slabs += (size_t)pl.nsplit;
     }
-#undef DMDX_TN_CASE
-  } else if (aligned)
-    hipLaunchKernelGGL(gemm_tn_partial_kernel<true>, grid, dim3(NTH), 0, stream, p);
-  else
-    hipLaunchKernelGGL(gemm_tn_partial_kernel<false>, grid, dim3(NTH), 0, stream, p);
-  DMDX_LAUNCH_CHECK();
-  hipLaunchKernelGGL(gemm_tn_reduce_kernel, dim3(pl.ntiles * ((pl.tm + 31) / 32) * 4), dim3(256), 0, stream, p.P,
-                     pl.nsplit, pl.ntiles, pl.ntr, pl.ntc, pl.syrk, (int)nrow, (int)ncol, D64, ld64, D32, ld32,
-                     accumulate, pl.tm);
-  DMDX_LAUNCH_CHECK();
-  return 0;
-}
-
-// ---- batched products: D (+)= sum_j A_j^T B_j, blocks in groups of MAXB per launch
-size_t batch_group_ws(const int64_t* K, int nb, int64_t nrow, int64_t ncol, int syrk) {
-  size_t slabs = 0;
-  Plan pl{};
-  for (int j = 0; j < nb; ++j) {
-    pl = make_plan(K[j], nrow, ncol, syrk, nb);
-    slabs += (size_t)pl.nsplit;
+    need = std::max(need, slabs * (size_t)pl.ntiles * pl.tm * BT * sizeof(double));
   }
-  return slabs * (size_t)pl.ntiles * pl.tm * BT * sizeof(double);
+  return need;
 }
 
+// The one launch path of all four entry points.  Nothing is refused here: the entry points have
+// put the leading dimensions and the workspace (batch_ws) through tn_refusal before the first launch.
+// probe: the launches feed dmdx_set_clock_probe (include/dmdx.h lists which entry points do).
 int run_batch(const float* const* A, const int64_t* lda, const float* const* B, const int64_t* ldb,
               const int64_t* K, int nblocks, int64_t nrow, int64_t ncol, int syrk, double* D64, int64_t ld64,
-              float* D32, int64_t ld32, int accumulate, void* ws, size_t ws_bytes, hipStream_t stream) {
+              float* D32, int64_t ld32, int accumulate, void* ws, hipStream_t stream, bool probe) {
   for (int j0 = 0; j0 < nblocks; j0 += MAXB) {
-    const int nb = nblocks - j0 < MAXB ? nblocks - j0 : MAXB;
-    const size_t need = batch_group_ws(K + j0, nb, nrow, ncol, syrk);
-    if (ws == nullptr || ws_bytes < need) {
-      dmdx_set_error("blocks: workspace %zu bytes < required %zu", ws_bytes, need);
-      return DMDX_E_WORKSPACE;
-    }
+    const int nb = group_len(nblocks, j0);
     TnBatch bt{};
     TnParams p{};
     bool aligned = true;
@@ -904,10 +845,6 @@ int run_batch(const float* const* A, const int64_t* lda, const float* const* B, 
     Plan pl{};
     for (int j = 0; j < nb; ++j) {
       const int64_t la = lda[j0 + j], lb = ldb[j0 + j];
-      if (la >= (int64_t(1) << 24) || lb >= (int64_t(1) << 24)) {
-        dmdx_set_error("blocks: leading dimension >= 2^24 not supported (use smaller row blocks)");
-        return DMDX_E_UNSUPPORTED;
-      }
       pl = make_plan(K[j0 + j], nrow, ncol, syrk, nb);
       bt.A[j] = A[j0 + j];
       bt.B[j] = B[j0 + j];
@@ -928,7 +865,7 @@ int run_batch(const float* const* A, const int64_t* lda, const float* const* B, 
     bt.unit_begin[nb] = units;
     bt.slab_begin[nb] = slabs;
     bt.nblocks = nb;
-    bt.clk = dmdx_clock_probe_ptr;
+    bt.clk = probe ? dmdx_clock_probe_ptr : nullptr;
     p.nrow = (int)nrow;
     p.ncol = (int)ncol;
     p.ntr = pl.ntr; p.ntc = pl.ntc; p.ntiles = pl.ntiles; p.syrk = pl.syrk;
@@ -944,7 +881,7 @@ int run_batch(const float* const* A, const int64_t* lda, const float* const* B, 
       DMDX_TN_CASE(32, 1, 0); DMDX_TN_CASE(48, 1, 1); DMDX_TN_CASE(64, 2, 0); DMDX_TN_CASE(80, 2, 1);
       DMDX_TN_CASE(96, 3, 0); DMDX_TN_CASE(112, 3, 1); DMDX_TN_CASE(128, 0, 0);
 #undef DMDX_TN_CASE
-      default: dmdx_set_error("gemm_tn_blocks: no kernel for tile height %d", pl.tm); return DMDX_E_INVALID;
+      default: dmdx_set_error("gemm_tn: no kernel for tile height %d", pl.tm); return DMDX_E_INVALID;
     }
     DMDX_LAUNCH_CHECK();
     hipLaunchKernelGGL(gemm_tn_reduce_kernel, dim3(pl.ntiles * ((pl.tm + 31) / 32) * 4), dim3(256), 0, stream, p.P, slabs,
@@ -1228,20 +1165,7 @@ void xty_small_plan(const int64_t* K, int nb_, int ntiles, int* chunks, int* cps
     if (want < 1) want = 1;
     // (the tail of the launch, as in make_plan: cfg2 at l = 20 is 69 tiles x 8 blocks x 4 splits = 4.31
     // rounds of 512 that cost 5; 12 splits are 12.94)
-    if (getenv("DMDX_TN_NO_TAILFIT") == nullptr) {
-      auto fill = [&](int64_t w) {
-        const int64_t cps_ = (chunks[j] + w - 1) / w;
-        const int64_t ns = cps_ > 0 ? (chunks[j] + cps_ - 1) / cps_ : 0;
-        const double r = (double)((int64_t)ntiles * nb_ * ns) / 512.0;
-        return r > 0.0 ? r / (double)(int64_t)(r + 0.999999) : 1.0;
-      };
-      int64_t best = want;
-      double bf = fill(want);
-      if (bf < 0.92)
-        for (int64_t w = want + 1; bf < 0.97 && w <= maxs && w <= 4 * want + 2; ++w)
-          if (fill(w) > bf) { bf = fill(w); best = w; }
-      want = best;
-    }
+    want = fit_last_round(chunks[j], (int64_t)ntiles * nb_, want, std::min(maxs, 4 * want + 2));
     cps[j] = (int)((chunks[j] + want - 1) / want);
     // a block of fewer than 64 rows has no full chunk: no units here, all of it goes to the tail launch
     nsplit[j] = cps[j] > 0 ? (chunks[j] + cps[j] - 1) / cps[j] : 0;
@@ -1254,25 +1178,19 @@ size_t xty_small_ws(const int64_t* K, int nblocks, int64_t na) {
   const int ntiles = (int)((na + XT - 1) / XT);
   size_t need = 0;
   for (int j0 = 0; j0 < nblocks; j0 += MAXB) {
-    const int ng = nblocks - j0 < MAXB ? nblocks - j0 : MAXB;
     int ch[MAXB], cp[MAXB], ns[MAXB], units = 0;
-    xty_small_plan(K + j0, ng, ntiles, ch, cp, ns, &units);
-    const size_t g = (size_t)units * XL * XT * sizeof(double);
-    if (g > need) need = g;
+    xty_small_plan(K + j0, group_len(nblocks, j0), ntiles, ch, cp, ns, &units);
+    need = std::max(need, (size_t)units * XL * XT * sizeof(double));
   }
   return need;
 }
 
 int run_xty_small(const float* const* X, const int64_t* ldx, const float* const* Y, const int64_t* ldy,
                   const int64_t* K, int nblocks, int64_t nb, int64_t na, double* D64, int64_t ld64, int accumulate,
-                  void* ws, size_t ws_bytes, hipStream_t stream) {
+                  void* ws, hipStream_t stream) {
   const int ntiles = (int)((na + XT - 1) / XT);
-  if (ws == nullptr || ws_bytes < xty_small_ws(K, nblocks, na)) {
-    dmdx_set_error("gemm_tn_blocks (small-l path): workspace %zu bytes too small", ws_bytes);
-    return DMDX_E_WORKSPACE;
-  }
   for (int j0 = 0; j0 < nblocks; j0 += MAXB) {
-    const int ng = nblocks - j0 < MAXB ? nblocks - j0 : MAXB;
+    const int ng = group_len(nblocks, j0);
     XtyBatch bt{};
     int units = 0;
     xty_small_plan(K + j0, ng, ntiles, bt.chunks, bt.cps, bt.nsplit, &units);
@@ -1304,7 +1222,8 @@ int run_xty_small(const float* const* X, const int64_t* ldx, const float* const*
                        (accumulate || j0 > 0) ? 1 : 0);
     DMDX_LAUNCH_CHECK();
   }
-  // rows past the last full 64-row chunk of every block: the generic path, accumulated on top
+  // rows past the last full 64-row chunk of every block: the generic path, accumulated on top (one split
+  // per block: its partial tiles fit into what batch_ws asks for the whole blocks)
   std::vector<const float*> Xt, Yt;
   std::vector<int64_t> lx, ly, Kt;
   for (int j = 0; j < nblocks; ++j) {
@@ -1318,14 +1237,17 @@ int run_xty_small(const float* const* X, const int64_t* ldx, const float* const*
   }
   if (!Kt.empty())
     return run_batch(Yt.data(), ly.data(), Xt.data(), lx.data(), Kt.data(), (int)Kt.size(), nb, na, 0, D64, ld64, nullptr,
-                     0, 1, ws, ws_bytes, stream);
+                     0, 1, ws, stream, true);
   return 0;
 }
 
-// A call that runs as several launches (row split, groups of 16 blocks, K3s + its tail launch) checks what
-// every one of them will check BEFORE the first one: a refused call leaves the outputs and the workspace
-// untouched.  (The per-launch checks of run_tn / run_batch used to fire between launches: a group of blocks
+// A call that runs as several launches (row split, groups of 16 blocks, K3s + its tail launch) checks
+// everything BEFORE the first one: a refused call leaves the outputs and the workspace untouched, and the
+// launch paths above check nothing.  (Per-launch checks used to fire between launches: a group of blocks
 // behind the first 16 with a larger plan or a too long leading dimension left C half accumulated.)
+// ld_limit: the per-lane offsets inside a 128-column panel are 32-bit: elements on the register path
+// (127 columns: ld < 2^25), bytes (+ 4 KiB of slack) on the LDS-DMA path (taken for ld < 2^22).  The blocks
+// entry points promise less, 2^24 per block; include/dmdx.h states both limits and neither moves here.
 int tn_refusal(const char* who, const int64_t* lda, const int64_t* ldb, int nblocks, int64_t ld_limit,
                const void* ws, size_t ws_bytes, size_t need) {
   for (int j = 0; j < nblocks; ++j)
@@ -1344,6 +1266,47 @@ int tn_refusal(const char* who, const int64_t* lda, const int64_t* ldb, int nblo
   do {                                  \
     if (const int rc_ = (expr)) return rc_; \
   } while (0)
+constexpr int64_t LD_LIMIT_SINGLE = int64_t(1) << 25, LD_LIMIT_BLOCKS = int64_t(1) << 24;
+
+// D rows beyond one 128-row tile (l > 128 columns of Y in Z = X^T Y): the full 128-row tiles in one
+// launch, the remaining rows in a second one with the tile height that pads least (64 / 96) -- when
+// that is less MFMA work than any uniform tile height (l = 220: 128 + 96 = 224 rows instead of
+// 256).  The second launch streams the big operand once more; these products are MFMA-bound by a
+// factor > 3 at such l, so the extra HBM pass is hidden.  Returns the split row, or 0.
+int64_t tn_row_split(int64_t nrow) {
+  if (nrow <= BT) return 0;
+  const int64_t full = nrow / BT * BT, rem = nrow - full;
+  if (rem == 0 || rem > 112) return 0;
+  const int64_t rem_pad = rem <= 32 ? 32 : (rem + 15) / 16 * 16;
+  int64_t best = (nrow + BT - 1) / BT * BT;
+  for (int tm : {112, 96, 80, 64}) {
+    const int64_t padded = (nrow + tm - 1) / tm * tm;
+    if (padded < best) best = padded;
+  }
+  return full + rem_pad < best ? full : 0;
+}
+
+// K3, C (na x nb, column-major) (+)= sum_j A_j^T B_j: workspace and launches, with the row split.
+// column-major C[a + b*ldc] == row-major D[b][a]: D rows <- B columns, D cols <- A columns
+size_t product_ws(const int64_t* K, int nblocks, int64_t na, int64_t nb) {
+  if (const int64_t cut = tn_row_split(nb))
+    return std::max(batch_ws(K, nblocks, cut, na, 0), batch_ws(K, nblocks, nb - cut, na, 0));
+  return batch_ws(K, nblocks, nb, na, 0);
+}
+
+int run_product(const float* const* A, const int64_t* lda, const float* const* B, const int64_t* ldb,
+                const int64_t* K, int nblocks, int64_t na, int64_t nb, double* C64, int64_t ldc, float* C32,
+                int64_t ldc32, int accumulate, void* ws, hipStream_t stream, bool probe) {
+  const int64_t cut = tn_row_split(nb);
+  if (cut == 0)
+    return run_batch(B, ldb, A, lda, K, nblocks, nb, na, 0, C64, ldc, C32, ldc32, accumulate, ws, stream, probe);
+  if (const int rc = run_batch(B, ldb, A, lda, K, nblocks, cut, na, 0, C64, ldc, C32, ldc32, accumulate, ws, stream, probe))
+    return rc;
+  std::vector<const float*> B2((size_t)nblocks);
+  for (int j = 0; j < nblocks; ++j) B2[j] = B[j] + cut * ldb[j];
+  return run_batch(B2.data(), ldb, A, lda, K, nblocks, nb - cut, na, 0, C64 + cut * ldc, ldc,
+                   C32 ? C32 + cut * ldc32 : nullptr, ldc32, accumulate, ws, stream, probe);
+}
 
 }  // namespace
 
@@ -1367,7 +1330,7 @@ int dmdx_set_clock_probe(unsigned long long* dev_counters3) {
 
 size_t dmdx_syrk_workspace_bytes(int64_t m, int64_t n) {
   if (m < 0 || n <= 0) return 0;
-  return make_plan(m, n, n, 1).ws_bytes;
+  return batch_ws(&m, 1, n, n, 1);
 }
 
 int dmdx_syrk_f32(const float* X, int64_t m, int64_t n, int64_t ldx, double* G64, int64_t ldg,
@@ -1377,20 +1340,17 @@ int dmdx_syrk_f32(const float* X, int64_t m, int64_t n, int64_t ldx, double* G64
   DMDX_CHECK_ARG(m >= 1 && n >= 1 && n < (1 << 30), "syrk: bad shape m=%lld n=%lld", (long long)m,
                  (long long)n);
   DMDX_CHECK_ARG(ldx >= 1 && ldg >= n && (!G32 || ldg32 >= n), "syrk: bad leading dimension");
-  return run_tn(X, ldx, X, ldx, m, n, n, 1, G64, ldg, G32, ldg32, accumulate, workspace, workspace_bytes,
-                (hipStream_t)stream);
+  DMDX_REFUSE_BEFORE_LAUNCH(tn_refusal("syrk", &ldx, &ldx, 1, LD_LIMIT_SINGLE, workspace, workspace_bytes,
+                                       dmdx_syrk_workspace_bytes(m, n)));
+  return run_batch(&X, &ldx, &X, &ldx, &m, 1, n, n, 1, G64, ldg, G32, ldg32, accumulate, workspace,
+                   (hipStream_t)stream, false);
 }
 
 size_t dmdx_syrk_blocks_workspace_bytes(const int64_t* m, int nblocks, int64_t n) {
   if (!m || nblocks <= 0 || n <= 0) return 0;
-  size_t need = 0;
-  for (int j0 = 0; j0 < nblocks; j0 += MAXB) {
-    for (int j = j0; j < nblocks && j < j0 + MAXB; ++j)
-      if (m[j] < 1) return 0;
-    const size_t g = batch_group_ws(m + j0, nblocks - j0 < MAXB ? nblocks - j0 : MAXB, n, n, 1);
-    if (g > need) need = g;
-  }
-  return need;
+  for (int j = 0; j < nblocks; ++j)
+    if (m[j] < 1) return 0;
+  return batch_ws(m, nblocks, n, n, 1);
 }
 
 int dmdx_syrk_blocks_f32(const float* const* X, const int64_t* m, const int64_t* ldx, int nblocks, int64_t n,
@@ -1400,37 +1360,15 @@ int dmdx_syrk_blocks_f32(const float* const* X, const int64_t* m, const int64_t*
   DMDX_CHECK_ARG(n >= 1 && n < (1 << 30) && ldg >= n && (!G32 || ldg32 >= n), "syrk_blocks: bad n / ldg");
   for (int j = 0; j < nblocks; ++j)
     DMDX_CHECK_ARG(X[j] && m[j] >= 1 && ldx[j] >= 1, "syrk_blocks: bad block %d", j);
-  DMDX_REFUSE_BEFORE_LAUNCH(tn_refusal("syrk_blocks", ldx, ldx, nblocks, int64_t(1) << 24, workspace, workspace_bytes,
+  DMDX_REFUSE_BEFORE_LAUNCH(tn_refusal("syrk_blocks", ldx, ldx, nblocks, LD_LIMIT_BLOCKS, workspace, workspace_bytes,
                                        dmdx_syrk_blocks_workspace_bytes(m, nblocks, n)));
   return run_batch(X, ldx, X, ldx, m, nblocks, n, n, 1, G64, ldg, G32, ldg32, accumulate, workspace,
-                   workspace_bytes, (hipStream_t)stream);
-}
-
-// D rows beyond one 128-row tile (l > 128 columns of Y in Z = X^T Y): the full 128-row tiles in one
-// launch, the remaining rows in a second one with the tile height that pads least (64 / 96) -- when
-// that is less MFMA work than any uniform tile height (l = 220: 128 + 96 = 224 rows instead of
-// 256).  The second launch streams the big operand once more; these products are MFMA-bound by a
-// factor > 3 at such l, so the extra HBM pass is hidden.  Returns the split row, or 0.
-static int64_t tn_row_split(int64_t nrow) {
-  if (nrow <= BT) return 0;
-  const int64_t full = nrow / BT * BT, rem = nrow - full;
-  if (rem == 0 || rem > 112) return 0;
-  const int64_t rem_pad = rem <= 32 ? 32 : (rem + 15) / 16 * 16;
-  int64_t best = (nrow + BT - 1) / BT * BT;
-  for (int tm : {112, 96, 80, 64}) {
-    const int64_t padded = (nrow + tm - 1) / tm * tm;
-    if (padded < best) best = padded;
-  }
-  return full + rem_pad < best ? full : 0;
+                   (hipStream_t)stream, true);
 }
 
 size_t dmdx_gemm_tn_workspace_bytes(int64_t K, int64_t na, int64_t nb) {
   if (K < 0 || na <= 0 || nb <= 0) return 0;
-  if (const int64_t cut = tn_row_split(nb)) {
-    const size_t w1 = make_plan(K, cut, na, 0).ws_bytes, w2 = make_plan(K, nb - cut, na, 0).ws_bytes;
-    return w1 > w2 ? w1 : w2;
-  }
-  return make_plan(K, nb, na, 0).ws_bytes;
+  return product_ws(&K, 1, na, nb);
 }
 
 int dmdx_gemm_tn_f32(const float* A, int64_t lda, const float* B, int64_t ldb, int64_t K,
@@ -1441,40 +1379,19 @@ int dmdx_gemm_tn_f32(const float* A, int64_t lda, const float* B, int64_t ldb, i
                  "gemm_tn: bad shape");
   DMDX_CHECK_ARG(lda >= 1 && ldb >= 1 && ldc >= na && (!C32 || ldc32 >= na),
                  "gemm_tn: bad leading dimension");
-  // (a product that runs as two launches is refused as a whole: nothing is written before an error)
-  DMDX_REFUSE_BEFORE_LAUNCH(tn_refusal("gemm_tn", &lda, &ldb, 1, int64_t(1) << 25, workspace, workspace_bytes,
+  DMDX_REFUSE_BEFORE_LAUNCH(tn_refusal("gemm_tn", &lda, &ldb, 1, LD_LIMIT_SINGLE, workspace, workspace_bytes,
                                        dmdx_gemm_tn_workspace_bytes(K, na, nb)));
-  // column-major C[a + b*ldc] == row-major D[b][a]: D rows <- B columns, D cols <- A columns
-  if (const int64_t cut = tn_row_split(nb)) {
-    const int rc = run_tn(B, ldb, A, lda, K, cut, na, 0, C64, ldc, C32, ldc32, accumulate, workspace,
-                          workspace_bytes, (hipStream_t)stream);
-    if (rc) return rc;
-    return run_tn(B + cut * ldb, ldb, A, lda, K, nb - cut, na, 0, C64 + cut * ldc, ldc,
-                  C32 ? C32 + cut * ldc32 : nullptr, ldc32, accumulate, workspace, workspace_bytes,
-                  (hipStream_t)stream);
-  }
-  return run_tn(B, ldb, A, lda, K, nb, na, 0, C64, ldc, C32, ldc32, accumulate, workspace, workspace_bytes,
-                (hipStream_t)stream);
+  // (never the small-l kernel: svd._accumulate_tn relies on the generic body here)
+  return run_product(&A, &lda, &B, &ldb, &K, 1, na, nb, C64, ldc, C32, ldc32, accumulate, workspace,
+                     (hipStream_t)stream, false);
 }
 
 size_t dmdx_gemm_tn_blocks_workspace_bytes(const int64_t* K, int nblocks, int64_t na, int64_t nb) {
   if (!K || nblocks <= 0 || na <= 0 || nb <= 0) return 0;
-  size_t need = 0;
-  for (int j0 = 0; j0 < nblocks; j0 += MAXB) {
-    for (int j = j0; j < nblocks && j < j0 + MAXB; ++j)
-      if (K[j] < 1) return 0;
-    const int ng = nblocks - j0 < MAXB ? nblocks - j0 : MAXB;
-    size_t g = batch_group_ws(K + j0, ng, nb, na, 0);
-    if (const int64_t cut = tn_row_split(nb)) {
-      const size_t g1 = batch_group_ws(K + j0, ng, cut, na, 0), g2 = batch_group_ws(K + j0, ng, nb - cut, na, 0);
-      g = g1 > g2 ? g1 : g2;
-    }
-    if (g > need) need = g;
-  }
-  if (nb <= XL && na >= XT) {   // the small-l path (K3s) has its own partial tiles
-    const size_t x = xty_small_ws(K, nblocks, na);
-    if (x > need) need = x;
-  }
+  for (int j = 0; j < nblocks; ++j)
+    if (K[j] < 1) return 0;
+  size_t need = product_ws(K, nblocks, na, nb);
+  if (nb <= XL && na >= XT) need = std::max(need, xty_small_ws(K, nblocks, na));   // K3s has its own partial tiles
   return need;
 }
 
@@ -1487,24 +1404,12 @@ int dmdx_gemm_tn_blocks_f32(const float* const* A, const int64_t* lda, const flo
                  "gemm_tn_blocks: bad shape / ldc");
   for (int j = 0; j < nblocks; ++j)
     DMDX_CHECK_ARG(A[j] && B[j] && K[j] >= 1 && lda[j] >= 1 && ldb[j] >= 1, "gemm_tn_blocks: bad block %d", j);
-  DMDX_REFUSE_BEFORE_LAUNCH(tn_refusal("gemm_tn_blocks", lda, ldb, nblocks, int64_t(1) << 24, workspace, workspace_bytes,
+  DMDX_REFUSE_BEFORE_LAUNCH(tn_refusal("gemm_tn_blocks", lda, ldb, nblocks, LD_LIMIT_BLOCKS, workspace, workspace_bytes,
                                        dmdx_gemm_tn_blocks_workspace_bytes(K, nblocks, na, nb)));
-  // column-major C[a + b*ldc] == row-major D[b][a]: D rows <- B columns, D cols <- A columns
   if (xty_small_ok(A, lda, B, ldb, K, nblocks, nb, na, C32))
-    return run_xty_small(A, lda, B, ldb, K, nblocks, nb, na, C64, ldc, accumulate, workspace, workspace_bytes,
-                         (hipStream_t)stream);
-  if (const int64_t cut = tn_row_split(nb)) {
-    const int rc = run_batch(B, ldb, A, lda, K, nblocks, cut, na, 0, C64, ldc, C32, ldc32, accumulate, workspace,
-                             workspace_bytes, (hipStream_t)stream);
-    if (rc) return rc;
-    std::vector<const float*> B2((size_t)nblocks);
-    for (int j = 0; j < nblocks; ++j) B2[j] = B[j] + cut * ldb[j];
-    return run_batch(B2.data(), ldb, A, lda, K, nblocks, nb - cut, na, 0, C64 + cut * ldc, ldc,
-                     C32 ? C32 + cut * ldc32 : nullptr, ldc32, accumulate, workspace, workspace_bytes,
-                     (hipStream_t)stream);
-  }
-  return run_batch(B, ldb, A, lda, K, nblocks, nb, na, 0, C64, ldc, C32, ldc32, accumulate, workspace,
-                   workspace_bytes, (hipStream_t)stream);
+    return run_xty_small(A, lda, B, ldb, K, nblocks, nb, na, C64, ldc, accumulate, workspace, (hipStream_t)stream);
+  return run_product(A, lda, B, ldb, K, nblocks, na, nb, C64, ldc, C32, ldc32, accumulate, workspace,
+                     (hipStream_t)stream, true);
 }
 
 }  // extern "C"

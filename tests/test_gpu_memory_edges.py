@@ -227,7 +227,7 @@ def _product_case(call, need, inputs, nrows, ncols, ref, bound, variant, rs, ctl
 @pytest.mark.parametrize("K,na,nb", TN_SHAPES)
 def test_gemm_tn_layouts(L, K, na, nb, lay):
     """dmdx_gemm_tn_f32: every tile height, every way into the aligned / unaligned dispatch of
-    run_tn, outputs with ldc > na, a fp32 copy with another ldc32, an output base offset."""
+    run_batch, outputs with ldc > na, a fp32 copy with another ldc32, an output base offset."""
     _, kmod, la, lb = lay
     if kmod is not None:
         K = K // 4 * 4 + kmod

@@ -903,3 +903,40 @@ def test_uncentred_field_keeps_the_chain_bound(L, K):
     r3 = float((np.abs(Cm.cpu().numpy().T - refc) / (f * refc)).max())
     print(f"K = {K}: max err / bound  K1 {r1:.4f}  K3 {r3:.4f}  (bound factor {f:.3e})")
     assert r1 <= 1.0 and r3 <= 1.0
+
+
+# =================================================================== D. a single product is a batch of one
+# The single entry points run the blocks path with one block: same plan, same units, same partial tiles.
+# Gram n: 70 / 96 the plain-product Gram (96-row tile), 130 / 300 two / three tile rows with the mirror;
+# product nb at na = 130: tile heights 32, 48, 64, 80, 96, 112, 128 and the 128 + 96 row split.
+ONE_CASES = [("gram", n) for n in (70, 96, 130, 300)] + [("tn", nb) for nb in (20, 40, 64, 70, 96, 100, 128, 220)]
+
+
+@pytest.mark.parametrize("path", ["dma", "reg"])
+@pytest.mark.parametrize("K", [1029, 4100])
+@pytest.mark.parametrize("kind,n", ONE_CASES)
+def test_single_entry_equals_batch_of_one(L, kind, n, K, path):
+    """dmdx_syrk_f32 / dmdx_gemm_tn_f32 against the blocks entry points with nblocks = 1: the fp64 result and
+    the fp32 copy bit for bit, accumulate = 0 and 1.  K = 1029 / 4100: 33 / 129 chunks (several K-splits, a
+    5- / 4-row tail); ld = K rounded up to a multiple of 4 (LDS-DMA) and the next odd number (registers).
+    The C32 the helpers pass keeps K3s out of the way."""
+    ld = (K + 3) // 4 * 4 if path == "dma" else K | 1
+    rs = np.random.RandomState(K + n)
+    At = _t(rs.standard_normal((K, 130 if kind == "tn" else n)).astype(np.float32), ld)
+    Bt = _t(rs.standard_normal((K, n)).astype(np.float32), ld) if kind == "tn" else None
+    assert (At.data_ptr() % 16 == 0 and ld % 4 == 0) == (path == "dma") and ld >= K
+    if kind == "gram":
+        single, blocks = (lambda out: syrk(L, At, out)), (lambda out: syrk_blocks(L, [At], out))
+    else:
+        single, blocks = (lambda out: gemm_tn(L, At, Bt, out)), (lambda out: gemm_tn_blocks(L, [At], [Bt], out))
+    S64, S32 = single(None)
+    B64, B32 = blocks(None)
+    assert bool(torch.isfinite(S64).all()) and S32 is not None and B32 is not None
+    assert torch.equal(S64, B64), f"{int((S64 != B64).sum())} fp64 entries differ"
+    assert torch.equal(S32, B32), f"{int((S32 != B32).sum())} fp32 entries differ"
+    start = torch.from_numpy(rs.standard_normal(tuple(S64.shape))).to(DEV)
+    A64, A32 = single(start.clone())
+    C64, C32 = blocks(start.clone())
+    assert not torch.equal(A64, S64)
+    assert torch.equal(A64, C64), f"accumulate = 1: {int((A64 != C64).sum())} fp64 entries differ"
+    assert torch.equal(A32, C32), f"accumulate = 1: {int((A32 != C32).sum())} fp32 entries differ"
