@@ -2,6 +2,7 @@ from dmd_era5_amd.era5_svd import (  # noqa: F401
     add_config_attributes,
     combine_svd_results,
     main,
+    project_onto_svd_results,
     reconstruct_from_svd_results,
     retrieve_era5_slice,
     retrieve_svd_results,
@@ -9,4 +10,5 @@ from dmd_era5_amd.era5_svd import (  # noqa: F401
 )
 
 __all__ = ["svd_on_era5", "combine_svd_results", "retrieve_era5_slice", "retrieve_svd_results",
-           "add_config_attributes", "main", "reconstruct_from_svd_results"]
+           "add_config_attributes", "main", "reconstruct_from_svd_results",
+           "project_onto_svd_results"]

@@ -56,6 +56,7 @@ __all__ = [
     "add_config_attributes",
     "main",
     "reconstruct_from_svd_results",
+    "project_onto_svd_results",
 ]
 
 logger = setup_logger("ERA5-SVD", "era5_svd.log")
@@ -256,6 +257,81 @@ def reconstruct_from_svd_results(svd_ds: Dataset, n_components: int | None = Non
         tc = svd_ds.coords["time"]
         row["time"] = Coord("time", np.asarray(tc.values)[tidx])
     return DataArray(X, ("space", "time"), row)
+
+
+def project_onto_svd_results(svd_ds: Dataset, X, n_components: int | None = None, mean=None, std=None,
+                             kern=None) -> DataArray:
+    """The coefficients of snapshots in the basis of an SVD result, ``U[:, :r]^T ((X - mean) / std)``: the
+    counterpart of :func:`reconstruct_from_svd_results` for data that were NOT part of the decomposition
+    (another year on the modes of this one, new data compressed into the stored basis).  For the decomposed
+    snapshots themselves it returns ``diag(s[:r]) V[:r]``.
+
+    ``X``: a ``(space, time)`` array or DataArray on the file's space axis (for a delay embedding: the
+    embedded rows), raw when ``mean`` / ``std`` are given.  ``mean`` / ``std``: per-row vectors; they default
+    to the file's ``X_mean`` / ``X_std`` when it has them (only for a delay embedding d > 1 -- the
+    reference's quirk, ref :400-414) and to None (no centring, no scaling) otherwise.  Returns the
+    ``(components, time)`` DataArray in U's dtype, with the time coordinate of ``X`` if it has one; attrs
+    ``energy_total`` = ||(X - mean) / std||_F^2 and ``captured_total`` = the part of it the r columns hold.
+    fp32 results are formed by K13 on the device in row blocks, X read once; float64 ones (the small-slice
+    fp64 route) take the library's fp64 product."""
+    U = np.asarray(svd_ds["U"].values)
+    k = int(U.shape[1])
+    r = k if n_components is None else int(n_components)
+    if not 1 <= r <= k:
+        raise ValueError(f"n_components = {r} outside 1 .. {k}")
+    Xv = np.asarray(X.values if hasattr(X, "values") else X)
+    M = int(U.shape[0])
+    if Xv.ndim != 2 or Xv.shape[0] != M:
+        raise ValueError(f"X is {Xv.shape}: its space axis must have the {M} rows of U")
+    names = set(svd_ds.data_vars)
+    vecs = []
+    for v, key in ((mean, "X_mean"), (std, "X_std")):
+        if v is None and key in names:
+            v = svd_ds[key]
+        if v is not None:
+            v = np.asarray(v.values if hasattr(v, "values") else v).reshape(-1)
+            if v.shape[0] != M:
+                raise ValueError(f"{key[2:]} has {v.shape[0]} entries, U has {M} rows")
+        vecs.append(v)
+    mu, sd = vecs
+    if sd is not None and (sd == 0).any():
+        raise ValueError(f"{int((sd == 0).sum())} entries of std are zero")
+    T = int(Xv.shape[1])
+    if U.dtype == np.float64:
+        Xs = Xv.astype(np.float64)
+        if mu is not None:
+            Xs = Xs - mu[:, None]
+        if sd is not None:
+            Xs = Xs / sd[:, None]
+        C = U[:, :r].T @ Xs
+        energy = float((Xs * Xs).sum())
+    else:
+        import torch
+
+        from . import forecast
+        from .svd import _kern, split_rows
+
+        kern = _kern(kern)
+        dev = torch.device("cuda" if getattr(kern, "name", "") == "hip" else "cpu")
+        blocks = split_rows(M)
+
+        def f32(a):
+            return torch.from_numpy(np.ascontiguousarray(a, dtype=np.float32))
+
+        res = forecast.project_blocks(
+            (f32(U[a:b, :r].T).to(dev) for a, b in blocks), (f32(Xv[a:b].T).to(dev) for a, b in blocks),
+            None if mu is None else [f32(mu[a:b]) for a, b in blocks],
+            None if sd is None else [f32(sd[a:b]) for a, b in blocks], kern=kern)
+        C = res["Ct"].T.cpu().numpy().astype(U.dtype)
+        energy = res["energy_total"]
+    coords = {"components": Coord("components", np.arange(r))}
+    xc = getattr(X, "coords", None)
+    if xc is not None and "time" in xc:
+        coords["time"] = xc["time"]
+    out = DataArray(np.ascontiguousarray(C), ("components", "time"), coords)
+    out.attrs["energy_total"] = energy
+    out.attrs["captured_total"] = float((C.astype(np.float64) ** 2).sum() / energy) if energy > 0 else float("nan")
+    return out
 
 
 # --------------------------------------------------------------------------------------

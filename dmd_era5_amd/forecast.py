@@ -8,7 +8,11 @@ coordinates ``H = V S``; both stop in the coordinates of ``U``.  This module eva
 with ``c(t)`` either the SVD coefficients ``diag(s) Vh[:, t]`` (the rank-k reconstruction of the
 decomposed snapshots) or the fitted model ``Re(Phi(t) diag(b) modes^T)`` at arbitrary times (the
 forecast), and scores it against real snapshots without materialising the fields: K12
-(``HipKernels.expand`` / ``expand_score``, csrc/expand.hip).
+(``HipKernels.expand`` / ``expand_score``, csrc/expand.hip).  The other direction -- raw snapshots that
+were not part of the decomposition to their coefficients ``c = U^T ((x - mu) / sigma)`` and energy
+``||(x - mu) / sigma||^2`` -- is K13 (``HipKernels.project``, csrc/project.hip): out-of-sample validation
+of the basis, compression of new data, and ``DmdForecast.restart``, which re-fits the amplitudes of a
+fitted model to a new state so that the forecast starts from the latest analysis.
 
 Layout as everywhere in the package (kernels.py): a column-major matrix is held as its row-major
 transpose -- U blocks are ``(k, rows)`` (``SvdResult.Ut``), coefficients ``Ct`` are ``(T, k)``,
@@ -27,7 +31,8 @@ import torch
 from .bopdmd import OptDMDResult, _phi
 from .svd import Comm, _kern, _pitched, embed_view
 
-__all__ = ["svd_coefficients", "dmd_coefficients", "expand_blocks", "iter_fields", "score_blocks", "DmdForecast"]
+__all__ = ["svd_coefficients", "dmd_coefficients", "expand_blocks", "iter_fields", "score_blocks", "project_blocks",
+           "DmdForecast"]
 
 
 # ---------------------------------------------------------------------------
@@ -90,6 +95,25 @@ def _expand_score(kern, Ut, Ct, Xt, mean, std, out, want_rows):
         out += cols
         cols = out
     return cols, ((E * E).sum(dim=0) if want_rows else None)
+
+
+def _project(kern, Ut, Xt, mean, std, out, want_energy=True):
+    f = getattr(kern, "project", None)
+    if f is not None:
+        return f(Ut, Xt, mean, std, out=out, want_energy=want_energy)
+    X = Xt.to(torch.float64)
+    if mean is not None:
+        X = X - mean.to(torch.float64)
+    if std is not None:
+        X = X / std.to(torch.float64)
+    C = X @ Ut.to(torch.float64).T
+    e = (X * X).sum(dim=1) if want_energy else None
+    if out is None:
+        return C, e
+    out[0].add_(C)
+    if want_energy:
+        out[1].add_(e)
+    return out
 
 
 def _vec(v, b, reps, device):
@@ -212,6 +236,61 @@ def score_blocks(Ublocks, Ct: torch.Tensor, Xblocks, means=None, stds=None, dela
     return res
 
 
+def project_blocks(Ublocks, Xblocks, means=None, stds=None, delay: int = 1, comm: Comm | None = None, kern=None,
+                   shape: tuple[int, int] | None = None) -> dict:
+    """The coefficients of raw snapshots in the basis U: ``c_t = U^T ((x_t - mean) / std)``, X read once and
+    no standardised copy made (K13).  The snapshots need not be the ones U was computed from.
+
+    ``Xblocks``: the (n, rows) snapshot blocks that belong to ``Ublocks`` (any iterable, consumed once in
+    order); with ``delay`` d > 1 the zero-copy embedded view (n - d + 1, d * rows) of every block is
+    projected.  ``means`` / ``stds``: lists of per-row vectors of the PHYSICAL rows of every block (None:
+    0 / 1), repeated for every delay; a std with a zero entry is refused (ValueError) before any launch.
+    Returns ``Ct`` (T, k) fp64, per snapshot ``energy`` = ||(x - mean) / std||^2 and ``captured`` =
+    ||c_t||^2 / energy_t, the totals ``captured_total`` = sum ||c||^2 / sum energy and ``energy_total``, and
+    ``rows`` (global).
+
+    ``1 - captured`` is a difference of two sums of m terms each and resolves nothing below ~1e-7: the
+    accurate out-of-sample residual is ``score_blocks(Ublocks, Ct.float(), Xblocks, ...)``, which sums the
+    squared residuals themselves.
+
+    Row shards: ONE ``comm.allreduce_sum_`` of the stacked ``[Ct, energy, rows]`` per call, whatever the
+    number of local blocks.  A rank without blocks still takes part; it cannot know the sizes and states
+    them as ``shape = (T, k)``."""
+    kern = _kern(kern)
+    comm = comm or Comm()
+    if stds is not None:
+        zeros = sum(int((torch.as_tensor(v) == 0).sum()) for v in stds)
+        if zeros:
+            raise ValueError(f"project_blocks: {zeros} entries of std are zero: (x - mean) / std is not defined for "
+                             "those rows (constant rows are kept out of the decomposition)")
+    acc, rows_local, T, k, dev = None, 0, None, None, None
+    for b, (U, X) in enumerate(zip(Ublocks, Xblocks, strict=True)):   # (a streamed X that ends early is an error)
+        E = embed_view(X, delay)
+        if T is None:
+            T, k, dev = int(E.shape[0]), int(U.shape[0]), U.device
+            if shape is not None and tuple(shape) != (T, k):
+                raise ValueError(f"project_blocks: shape = {tuple(shape)} stated, the blocks give {(T, k)}")
+        if E.shape != (T, U.shape[1]) or U.shape[0] != k:
+            raise ValueError(f"project_blocks: block {b} of X is {tuple(E.shape)} (delay {delay}) and of U "
+                             f"{tuple(U.shape)}; {(T, int(U.shape[1]))} and {(k, int(U.shape[1]))} asked for")
+        acc = _project(kern, U, E, _vec(means, b, delay, U.device), _vec(stds, b, delay, U.device), acc)
+        rows_local += int(U.shape[1])
+    if acc is None:        # a rank without blocks still takes part in the collective
+        if shape is None:
+            raise ValueError("project_blocks: no blocks and no shape = (T, k)")
+        T, k = int(shape[0]), int(shape[1])
+        dev = torch.device("cuda" if getattr(kern, "name", "") == "hip" else "cpu")
+        acc = (torch.zeros((T, k), dtype=torch.float64, device=dev), torch.zeros(T, dtype=torch.float64, device=dev))
+    Ct, energy = acc
+    flat = torch.cat([Ct.reshape(-1), energy, torch.tensor([float(rows_local)], dtype=torch.float64, device=Ct.device)])
+    flat = comm.allreduce_sum_(flat, tag="project_allreduce")
+    Ct, energy, rows = flat[:T * k].reshape(T, k), flat[T * k:T * k + T], float(flat[T * k + T])
+    c2 = (Ct * Ct).sum(dim=1)
+    e_total = energy.sum()
+    return {"Ct": Ct, "energy": energy, "captured": c2 / energy, "captured_total": float(c2.sum() / e_total),
+            "energy_total": float(e_total), "rows": int(rows)}
+
+
 # ---------------------------------------------------------------------------
 # the bundle a user holds
 # ---------------------------------------------------------------------------
@@ -271,3 +350,58 @@ class DmdForecast:
             delay_block = None
         return expand_blocks([U[:k] for U in self.Ublocks], Ct, self.means, self.stds, delay_block, out=out,
                              delay=self.delay, kern=self.kern)
+
+    def project(self, Xblocks, comm: Comm | None = None, n_snapshots: int | None = None) -> dict:
+        """:func:`project_blocks` of raw snapshots (with a delay d the blocks hold T + d - 1 of them) on this
+        bundle's U, means and stds.  ``n_snapshots``: T, for a rank without blocks."""
+        shape = None
+        if n_snapshots is not None:
+            k = int(self.Ublocks[0].shape[0]) if len(self.Ublocks) else int(self.result.modes.shape[0])
+            shape = (int(n_snapshots), k)
+        return project_blocks(self.Ublocks, Xblocks, self.means, self.stds, self.delay, comm, self.kern, shape=shape)
+
+    def restart(self, Xblocks, t, comm: Comm | None = None, rcond: float = 1e-12) -> "DmdForecast":
+        """The fitted model re-started from new snapshots: the amplitudes are re-fitted to the coefficients
+        of ``Xblocks`` (raw snapshots at the times ``t``, which need not belong to the training window; one
+        snapshot is enough when k >= r), the eigenvalues and the mode shapes are kept:
+
+                b = argmin_b || Phi(t) diag(b) modes^T - C ||_F      over complex b,   C = project(Xblocks).
+
+        Its normal equations are r x r, ``N = (Phi^H Phi) o (modes^H modes)`` and ``rhs_j = (Phi^H C
+        conj(modes))_jj``, solved in complex128 through the Hermitian eigen-decomposition of N; directions
+        below ``rcond * lambda_max`` (a duplicated eigenvalue, a window too short to tell two apart) are
+        dropped and counted in ``info["restart_dropped"]``.  The phase of b_j moves into ``modes[:, j]``:
+        ``amplitudes`` stays real and >= 0.  Returns a new bundle sharing ``Ublocks``, ``means`` and ``stds``
+        whose result carries the ``rel_error`` of the window fit, ``info["restarted_at"]`` (first and last
+        time of the window), ``info["restart_window"]`` (T) and ``info["captured"]`` (how much of the new
+        snapshots the basis holds)."""
+        if self.result is None:
+            raise ValueError("DmdForecast.restart: no fitted DMD result")
+        res = self.result
+        alpha = res.eigs.to(torch.complex128)
+        tt = torch.as_tensor(t, dtype=torch.float64, device=alpha.device).reshape(-1)
+        W = res.modes.to(torch.complex128)
+        k, r, T = int(W.shape[0]), int(alpha.numel()), int(tt.numel())
+        if T * k < r:
+            raise ValueError(f"DmdForecast.restart: {T} snapshots x {k} coordinates cannot determine {r} amplitudes")
+        proj = project_blocks(self.Ublocks, Xblocks, self.means, self.stds, self.delay, comm, self.kern, shape=(T, k))
+        C = proj["Ct"].to(device=alpha.device, dtype=torch.complex128)
+        phi = _phi(alpha, tt, torch.complex128)
+        N = (phi.conj().T @ phi) * (W.conj().T @ W)
+        rhs = torch.einsum("tj,tc,cj->j", phi.conj(), C, W.conj())
+        lam, Q = torch.linalg.eigh(0.5 * (N + N.conj().T))
+        keep = lam > rcond * lam[-1]
+        Qk = Q[:, keep]
+        b = Qk @ ((Qk.conj().T @ rhs) / lam[keep])
+        amp = b.abs()
+        phase = torch.where(amp > 0, b / torch.where(amp > 0, amp, torch.ones_like(amp)).to(b.dtype),
+                            torch.ones_like(b))
+        fit = (phi * b) @ W.T
+        nc = float(torch.linalg.norm(C))
+        rel = float(torch.linalg.norm(fit - C)) / nc if nc > 0.0 else 0.0
+        info = dict(res.info)
+        info.update(restart_dropped=int(r - int(keep.sum())), restarted_at=(float(tt[0]), float(tt[-1])),
+                    restart_window=T, captured=proj["captured_total"])
+        new = OptDMDResult(eigs=res.eigs, modes=(W * phase).to(res.modes.dtype), amplitudes=amp.to(res.amplitudes.dtype),
+                           rel_error=rel, n_iter=0, converged=True, eigs_std=res.eigs_std, info=info)
+        return DmdForecast(self.Ublocks, new, self.means, self.stds, self.delay, self.s, self.Vh, self.kern)

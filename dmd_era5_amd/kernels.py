@@ -318,6 +318,47 @@ class HipKernels:
         _lib.check(rc, "dmdx_expand_score_f32")
         return cols, rows
 
+    # -- K13 ----------------------------------------------------------------
+    @property
+    def project_max_k(self) -> int:
+        return int(self._lib.dmdx_project_max_k())
+
+    def project(self, Ut: torch.Tensor, Xt: torch.Tensor, mean: torch.Tensor | None = None,
+                std: torch.Tensor | None = None, out=None, want_energy: bool = True):
+        """C = U^T ((X - mean) / std) and the energy sum_i ((x - mean) / std)^2 of every snapshot, X read once
+        and no standardised copy made.  Ut: (k, m), Xt: (T, m) fp32 (the delay view included), mean / std:
+        (m,) fp32 or None -> (Ct (T, k) fp64, energy (T,) fp64 or None).
+
+        ``out``: the pair (Ct, energy) of an earlier call -- contiguous (T, k) / (T,) fp64 -- that this
+        block's sums are ADDED to (row blocks of X and U); its energy is None iff ``want_energy`` is false."""
+        m, k, ldu = _check_mat(Ut, torch.float32, "project U")
+        mx, T, ldx = _check_mat(Xt, torch.float32, "project X")
+        if mx != m or Xt.device != Ut.device:
+            raise _lib.DmdxError(f"project: X must be (T, {m}) on {Ut.device}, got {tuple(Xt.shape)} on {Xt.device}")
+        for v, name in ((mean, "mean"), (std, "std")):
+            if v is not None and (v.dtype != torch.float32 or v.shape != (m,) or v.device != Ut.device
+                                  or not v.is_contiguous()):
+                raise _lib.DmdxError(f"project: {name} must be a contiguous fp32 vector of length {m} on {Ut.device}")
+        if out is not None:
+            Ct, energy = out
+            if Ct.shape != (T, k) or Ct.dtype != torch.float64 or not Ct.is_contiguous() or Ct.device != Ut.device:
+                raise _lib.DmdxError(f"project: out[0] must be a contiguous ({T}, {k}) fp64 tensor on {Ut.device}")
+            if (energy is not None) != bool(want_energy) or (energy is not None and (
+                    energy.shape != (T,) or energy.dtype != torch.float64 or not energy.is_contiguous()
+                    or energy.device != Ut.device)):
+                raise _lib.DmdxError(f"project: out[1] must be a contiguous ({T},) fp64 tensor on {Ut.device} "
+                                     "when the energy is wanted, and None otherwise")
+        else:
+            Ct = torch.empty((T, k), dtype=torch.float64, device=Ut.device)
+            energy = torch.empty(T, dtype=torch.float64, device=Ut.device) if want_energy else None
+        ws = self._workspace(Ut.device, self._lib.dmdx_project_workspace_bytes(m, k, T))
+        rc = self._timed("project", (m, k, T), lambda: self._lib.dmdx_project_f32(
+            _ptr(Ut), m, k, ldu, _ptr(Xt), ldx, T, _ptr(mean), _ptr(std), _ptr(Ct), k, _ptr(energy),
+            int(out is not None), _ptr(ws), ws.numel(), self._stream()
+        ))
+        _lib.check(rc, "dmdx_project_f32")
+        return Ct, energy
+
     # -- K5 -----------------------------------------------------------------
     def row_center_scale_(self, Xt: torch.Tensor, scale: bool):
         """In place: subtract the per-space-point mean over time (and divide by the

@@ -54,7 +54,13 @@
  *     U, mu and sigma are addressed with 64-bit offsets and one dword per lane: no alignment is asked
  *     for and none selects another path; a 16-byte aligned C with ldc % 4 == 0 is staged with 16-byte
  *     loads.  m, T and every leading dimension must be < 2^31 (DMDX_E_INVALID beyond, before anything
- *     is written).
+ *     is written);
+ *   - K13 (dmdx_project_f32): U, X, mu and sigma are only read, inside their logical elements (U: m x k,
+ *     X: m x T with rows > ldx allowed); every logical element of C (k x T, ldc) and -- when given -- of
+ *     energy is written with accumulate == 0 and read and written with accumulate != 0, nothing else.  No
+ *     alignment is asked for: a 16-byte aligned U with ldu % 4 == 0, X with ldx % 4 == 0, mu, sigma each
+ *     select 16-byte loads for that operand, anything else one dword per lane with the same values.  m, T
+ *     and every leading dimension must be < 2^31 (DMDX_E_INVALID beyond, before anything is written).
  *
  * Value contract (tests/test_gpu_value_domain.py holds every fp32 entry point to it)
  *   - NaN / Inf propagate like IEEE arithmetic on the logical operands, nothing more and nothing less:
@@ -74,6 +80,9 @@
  *     multiple of 16 with zeros in U AND in C (0 * 0), so an Inf in the last column of U meets no pad.  In
  *     the score a non-finite X[i, t] makes exactly sse_col[t], ref_col[t] and sse_row[i] non-finite, and
  *     a non-finite Xhat[i, t] does the same to sse_col[t] and sse_row[i];
+ *     K13: X[i, t] hits column t of C and energy[t], U[i, j] row j of C, mu[i] / sigma[i] (sigma[i] = 0
+ *     included: xt = +-Inf or NaN) every energy and every C[j, t] with the class of numpy's fp64
+ *     U^T ((X - mu) / sigma); rows past m, snapshots past T and columns past k are zeros on both sides;
  *   - a CONSTANT row under K5 with scale: mean[i] is the constant exactly, std[i] is exactly 0 and the
  *     row becomes 0 / 0 = NaN, as numpy's (x - mean) / std of the reference's standardize_data does
  *     (slice_tools.py:171-179).  That is the contract, not an accident: the SVD that follows raises
@@ -96,6 +105,11 @@
  *     K12: k a_U a_C < 2^24 gives the integer U C bit for bit, and with integer sigma, mu and X (every
  *     intermediate below 2^24) Xhat, sse_col, ref_col and sse_row are the integer results; a power-of-two
  *     factor on U and its inverse on C leave every output bit unchanged (magnitudes as above).
+ *     K13: xt = fl(fl(X - mu) / sigma) is bit for bit what K5 leaves in place for the same mean and std.  With
+ *     integer U, mu, X, sigma a power of two dividing X - mu and m a_U a_xt < 2^24 (energy: a_xt^2 times the rows
+ *     of a row range < 2^24) C and energy are the integer results bit for bit.  (2^e X, 2^e mu, 2^e sigma) leaves
+ *     every bit of C and energy unchanged, 2^e U gives exactly 2^e C.  Error: one fp32 chain of at most
+ *     DMDX_PROJECT_FP32_ROWS rows per row range, fp64 across: (DMDX_PROJECT_FP32_ROWS + 4) 2^-24 sum |u||xt|.
  */
 #ifndef DMDX_H
 #define DMDX_H
@@ -309,6 +323,26 @@ int dmdx_expand_score_f32(const float* U, int64_t m, int64_t k, int64_t ldu, con
                           double* sse_col, double* ref_col, double* sse_row, int accumulate,
                           void* workspace, size_t workspace_bytes, void* stream);
 
+/* ---- K13: coefficients of raw snapshots in the basis U, and their energy ---------------------------------------
+ * The other direction of K12: snapshots that were not part of the decomposition are standardised as
+ * slice_tools.py:171-179 does (mu / sigma: m floats each, nullable: 0 / 1) and projected on the left singular
+ * vectors U (m x k, ldu; np.linalg.svd / randomized_svd, era5_svd.py:251,258) without a standardised copy of X:
+ *   xt[i, t]   = fl( fl(X[i, t] - mu[i]) / sigma[i] )            what K5 leaves in place for the same mu, sigma
+ *   C[j, t]   (+)= sum_i U[i, j] xt[i, t]                          k x T fp64, ldc
+ *   energy[t] (+)= sum_i xt[i, t]^2                                T doubles, nullable
+ * X: m x T (ldx; rows > ldx allowed, the zero-copy delay view), read once.  1 <= k <= dmdx_project_max_k() (256).
+ * accumulate != 0 adds to C and energy (X and U given as row blocks).  fp32 MFMA products; fp32 sums cover at
+ * most DMDX_PROJECT_FP32_ROWS rows (one row range of the launch), fp64 beyond, through per-unit slots in the
+ * workspace and a reduce kernel: no atomics, the order of every sum depends on (m, k, T) only, results are
+ * bit-wise reproducible.  One call covers fewer than 2^24 (row range, 128-snapshot tile) units
+ * (DMDX_E_UNSUPPORTED beyond: terabytes of X; pass row blocks). */
+#define DMDX_PROJECT_FP32_ROWS 4096
+int dmdx_project_max_k(void);
+size_t dmdx_project_workspace_bytes(int64_t m, int64_t k, int64_t T);
+int dmdx_project_f32(const float* U, int64_t m, int64_t k, int64_t ldu, const float* X, int64_t ldx, int64_t T,
+                     const float* mu, const float* sigma, double* C, int64_t ldc, double* energy, int accumulate,
+                     void* workspace, size_t workspace_bytes, void* stream);
+
 /* ---- upper triangle of a symmetric fp64 matrix <-> packed row by row ---------------------
  * packed[i (2n - i + 1) / 2 + (j - i)] = A[i][j], j >= i: what the Gram all-reduce of the
  * row-sharded path moves (n (n + 1) / 2 doubles instead of n^2).  unpack writes both triangles. */
@@ -325,7 +359,7 @@ int dmdx_exp_basis(const double* alpha, const double* t, int64_t n, int64_t r, v
 
 /* ---- measurement aid (not on the path): sustained core clock of the Gram launches ----------
  * While dev_counters3 (3 device uint64, caller-zeroed) is set, every workgroup of the batched
- * launches (dmdx_syrk_blocks_f32, dmdx_gemm_tn_blocks_f32), of dmdx_gemm_nn_skinny_f32 and of K12 adds its
+ * launches (dmdx_syrk_blocks_f32, dmdx_gemm_tn_blocks_f32), of dmdx_gemm_nn_skinny_f32, of K12 and of K13 adds its
  * core-clock cycles (s_memtime), its 100 MHz reference ticks
  * (s_memrealtime) and 1 to it: clock = 100 MHz * [0] / [1].  NULL (the default) switches the
  * stamps off again; bench.py's calibration block is the only caller. */
