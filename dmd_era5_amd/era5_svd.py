@@ -401,6 +401,94 @@ def lat_band(nlat: int, rank: int, world: int) -> tuple[int, int]:
     return rank * nlat // world, (rank + 1) * nlat // world
 
 
+def _take_step(take) -> int | None:
+    """Step of the snapshot selection if it is an arithmetic progression (1 = contiguous), else None."""
+    n = len(take)
+    if n <= 1:
+        return 1
+    step = int(take[1]) - int(take[0])
+    return step if step >= 1 and np.array_equal(take, int(take[0]) + step * np.arange(n)) else None
+
+
+def _raise_on_fill_codes(found, comm, device, where: str = "the selected slice") -> None:
+    """``found``: (variable name, fill codes met in the selected slice -- int or one-element device
+    tensor) per variable that declares fill codes, the same list on every rank.  The reference hands
+    NaN to LAPACK / sklearn, which raise; here the variable and the count are named before any SVD
+    work.  The counts are summed over the ranks first, so that every rank raises (a rank that
+    raised alone would leave the others waiting in their next collective)."""
+    if not found:
+        return
+    import torch
+
+    counts = torch.stack([c.reshape(()).to(torch.int64) if isinstance(c, torch.Tensor)
+                          else torch.tensor(int(c), dtype=torch.int64, device=device) for _, c in found]).to(device)
+    if comm.exchanges:
+        comm.allreduce_sum_(counts, tag="fill_count_allreduce")
+    totals: dict = {}
+    for (name, _), c in zip(found, counts.tolist()):
+        totals[name] = totals.get(name, 0) + int(c)
+    bad = {k: v for k, v in totals.items() if v}
+    if bad:
+        what = ", ".join(f"variable {k}: {v} missing values (fill codes)" for k, v in bad.items())
+        msg = (f"{what} in {where}; an SVD of data with missing values is not defined -- "
+               "select levels / times without them or fill them before the decomposition")
+        log_and_print(logger, msg, "error")
+        raise ValueError(msg)
+
+
+def _upload_packed_i16(lazy, level_idx, take, step, band, ranges, blocks, device, kern, count_fills):
+    """The packed route of ``_upload_variable``: int16 codes of the file -> pinned int16 staging ->
+    device slab -> one K14 launch per row block (unpack + level / band gather).
+    Only the level range min(level_idx) .. max(level_idx) and the latitude band are read.  Contiguous
+    snapshots are read as one span per slab; with a step the selected snapshots are read one by one
+    into consecutive rows of the staging buffer (a snapshot is megabytes and contiguous in the file),
+    so that what crosses the staging and PCIe is 2 bytes per selected value in either case -- a span
+    with step 3 would move 6, more than the 4 of the host decode.
+    -> (bytes moved, device fill-code counter or None)."""
+    import torch
+
+    packing, n = lazy.packing, len(take)
+    (i0, i1), nlon = band, lazy.shape[3]
+    nlat = i1 - i0
+    l0, l1 = int(np.min(level_idx)), int(np.max(level_idx)) + 1
+    plane = nlat * nlon
+    lds = (l1 - l0) * plane
+    segs = [(int(lv) - l0) * plane for lv in level_idx]
+    everything = (l0, l1, i0, i1) == (0, lazy.shape[1], 0, lazy.shape[2])
+    per = min(n, max(1, SLAB_BYTES // (lds * lazy.dtype.itemsize)))     # snapshots per slab
+    pinned = [torch.empty((per, lds), dtype=torch.int16).pin_memory() for _ in range(2)]
+    events = [None, None]
+    nfill = torch.zeros(1, dtype=torch.int64, device=device) if count_fills else None
+    nbytes = 0
+
+    def read(t0, cnt, out):
+        if everything:
+            lazy.read_slab(t0, t0 + cnt, out)
+        else:
+            lazy.read_box((t0, l0, i0, 0), (cnt, l1 - l0, nlat, nlon), out)
+
+    for it, j0 in enumerate(range(0, n, per)):
+        j1 = min(n, j0 + per)
+        buf = pinned[it & 1]
+        if events[it & 1] is not None:
+            events[it & 1].synchronize()            # the copy that last used this buffer is done
+        view = buf[: j1 - j0].numpy().reshape((j1 - j0, l1 - l0, nlat, nlon))
+        if step == 1:
+            read(int(take[j0]), j1 - j0, view)
+        else:
+            for j in range(j0, j1):
+                read(int(take[j]), 1, view[j - j0:j - j0 + 1])
+        dev = buf[: j1 - j0].to(device, non_blocking=True)
+        events[it & 1] = torch.cuda.Event()
+        events[it & 1].record()
+        nbytes += (j1 - j0) * lds * lazy.dtype.itemsize
+        for (a, b), Xb in zip(ranges, blocks):
+            kern.unpack_i16_(dev.reshape(-1), lds, 1, Xb[j0:j1, : b - a], a, plane, segs, packing.scale_factor,
+                             packing.add_offset, packing.fills, nfill)
+        del dev
+    return nbytes, nfill
+
+
 def _upload_variable(da: DataArray, level_idx, take, device, kern, center, scale, stats, band=None, pad4=False):
     """One variable (time, level, lat, lon) -> centred/scaled row blocks (time, rows) in HBM.
 
@@ -414,7 +502,15 @@ def _upload_variable(da: DataArray, level_idx, take, device, kern, center, scale
     Streams time slabs: file/host -> pinned staging -> device slab -> strided device copy
     into each row block.  Row order inside the variable: level slowest, longitude fastest.
     ``band`` = (i0, i1): only these latitude rows (this rank's shard); file-backed variables
-    are then read as hyperslabs, so a rank touches only its own bytes of the file."""
+    are then read as hyperslabs, so a rank touches only its own bytes of the file.
+
+    A file-backed int16 variable with CF packing stays packed until it is in HBM: the codes of the
+    span ``take[j0] .. take[j1 - 1]`` go through two pinned int16 buffers (half the bytes from the
+    file, over PCIe and in the staging) and one K14 launch per row block unpacks and gathers the
+    selected levels / latitude band; a regular resampling is compacted while it is read -- so
+    neither ``all_levels`` nor a contiguous ``take`` is asked for.  Every other packed case is
+    decoded on the host (same arithmetic) in the slow branch.  A variable that declares fill codes
+    appends (name, number of them in the selection) to ``stats["fills"]``."""
     import torch
 
     from . import svd as dsvd
@@ -440,15 +536,31 @@ def _upload_variable(da: DataArray, level_idx, take, device, kern, center, scale
     # fast path: fp32 file-backed variable, contiguous snapshots, every level: the slab is read
     # straight into one of two pinned staging buffers and copied to the device asynchronously,
     # so the next read overlaps the previous host->device copy
-    direct = lazy is not None and contiguous and all_levels and lazy.dtype == np.float32
+    packing = lazy.packing if lazy is not None else None
+    # (a float32 variable that only declares a fill value -- xarray writes _FillValue = NaN on every float
+    # variable -- keeps this path: the fill value is replaced and the NaN counted on the device)
+    direct = lazy is not None and contiguous and all_levels and lazy.dtype == np.float32 and \
+        (packing is None or not packing.affine)
     on_gpu = device.type == "cuda"
+    step = _take_step(take)
+    declared = bool(packing.fills) if packing is not None else any(
+        k in getattr(da, "encoding", {}) for k in ("_FillValue", "missing_value"))
+    # packed bytes travel and K14 unpacks: what the kernel's own limits allow (anything else is decoded on the host)
+    unpacked = (packing is not None and lazy.dtype == np.int16 and on_gpu and hasattr(kern, "unpack_i16_")
+                and step is not None and n > 0 and m_v > 0 and len(level_idx) <= 64 and len(packing.fills) <= 2
+                and (int(np.max(level_idx)) - int(np.min(level_idx)) + 1) * nlat * nlon < 2 ** 31)
+    if unpacked:
+        nbytes, found = _upload_packed_i16(lazy, level_idx, take, step, (i0, i1), ranges, blocks, device, kern, declared)
+        if declared:
+            stats.setdefault("fills", []).append((da.name, found))
+    nan_count = torch.zeros((), dtype=torch.int64, device=device) if declared and not unpacked else None
     pinned = None
     if direct:
         pinned = [torch.empty((rows, m_v), dtype=torch.float32) for _ in range(2)]
         if on_gpu:
             pinned = [b.pin_memory() for b in pinned]
     events = [None, None]
-    for it, j0 in enumerate(range(0, n, rows)):
+    for it, j0 in enumerate(() if unpacked else range(0, n, rows)):
         j1 = min(n, j0 + rows)
         if direct:
             buf = pinned[it & 1]
@@ -477,15 +589,25 @@ def _upload_variable(da: DataArray, level_idx, take, device, kern, center, scale
                 slab = read(lo, int(idx.max()) + 1)[idx - lo]
             if not all_levels:
                 slab = slab[:, level_idx]
+            if packing is not None:                 # file values -> physical ones (labeled.Packing.decode)
+                slab = packing.decode(slab)
             slab = np.ascontiguousarray(slab.reshape(j1 - j0, m_v), dtype=np.float32)
             nbytes += slab.nbytes
             dev = torch.from_numpy(slab).to(device, non_blocking=False)
+        if nan_count is not None:                   # on the device, behind the upload: no host pass, no host sync
+            if direct:
+                for f in packing.fills:
+                    if f == f:                      # (a NaN fill value is already what it should become)
+                        dev.masked_fill_(dev == np.float32(f), float("nan"))
+            nan_count += torch.isnan(dev).sum()
         for (a, b), Xb in zip(ranges, blocks):
             Xb[j0:j1, : b - a].copy_(dev[:, a:b])
         if direct and on_gpu:
             events[it & 1] = torch.cuda.Event()
             events[it & 1].record()
         del dev
+    if nan_count is not None:
+        stats.setdefault("fills", []).append((da.name, nan_count))
     for (a, b), Xb in zip(ranges, blocks):
         if center:
             mu, sd = kern.row_center_scale_(Xb[:, : b - a], bool(scale))   # (the zero rows stay zero: 0 / 0 otherwise)
@@ -575,13 +697,23 @@ def _device_pipeline(ds: Dataset, parsed_config: dict, comm=None, kern=None, dev
         i0, i1 = band if band else (0, nlat)
         h = max(1, stream_bytes // max(1, 4 * len(take) * nlev * nlon))       # latitude rows per piece
         sub = [(j, min(i1, j + h)) for j in range(i0, i1, h)]
-        means, stds, moved = {}, {}, [0]
+        means, stds, moved, fills = {}, {}, [0], {}
 
         def pieces():
             for vi, name in enumerate(names):
                 for j0, j1 in sub:
                     st = {"mean": [], "std": []}
                     vb, _, nbytes = _upload_variable(ds[name], level_idx, take, device, kern, center, scale, st, (j0, j1))
+                    if st.get("fills"):
+                        # one rank: the piece is refused before it reaches a Gram or a product.  Several
+                        # ranks: the ranks have different numbers of pieces, so there is no common point
+                        # for a collective here; the counts are kept and summed once behind the SVD call,
+                        # which every rank leaves at the same place (its finite checks are made on
+                        # all-reduced quantities)
+                        if not comm.exchanges:
+                            _raise_on_fill_codes(st["fills"], comm, device,
+                                                 f"latitude rows {j0}:{j1} of the selected slice (the first piece with any)")
+                        fills[(vi, j0)] = st["fills"][0]
                     if center:
                         means[(vi, j0)] = torch.cat(st["mean"])
                     if scale:
@@ -593,11 +725,24 @@ def _device_pipeline(ds: Dataset, parsed_config: dict, comm=None, kern=None, dev
         log_and_print(logger, f"Snapshot matrix larger than the HBM: streaming it in {len(names) * len(sub)} pieces of "
                               f"<= {h} latitude rows{shard}")
         log_and_print(logger, f"Performing {parsed_config['svd_type']} SVD...")
-        if parsed_config["svd_type"] == "standard":
-            Ub, s_, Vh_, sinfo = dsvd.svd_snapshots_streaming(pieces, k, rows_global, delay=d, comm=comm, kern=kern)
-        else:
-            Ub, s_, Vh_, sinfo = dsvd.svd_randomized_streaming(pieces, k, rows_global, len(take), delay=d, comm=comm,
-                                                               kern=kern, **_engine_opts(parsed_config))
+        failed = None
+        try:
+            if parsed_config["svd_type"] == "standard":
+                Ub, s_, Vh_, sinfo = dsvd.svd_snapshots_streaming(pieces, k, rows_global, delay=d, comm=comm, kern=kern)
+            else:
+                Ub, s_, Vh_, sinfo = dsvd.svd_randomized_streaming(pieces, k, rows_global, len(take), delay=d, comm=comm,
+                                                                   kern=kern, **_engine_opts(parsed_config))
+        except np.linalg.LinAlgError as e:          # (raised on all-reduced quantities: by every rank or by none)
+            failed = e
+        declared = [nm for nm in names if any(key in getattr(ds[nm], "encoding", {}) for key in ("_FillValue", "missing_value"))]
+        if comm.exchanges and declared:
+            # several ranks: ONE summed check here, where every rank arrives whether the SVD raised or returned
+            local = {}
+            for (vi, _), (nm, c) in sorted(fills.items()):
+                local[nm] = local.get(nm, 0) + int(c)
+            _raise_on_fill_codes([(nm, local.get(nm, 0)) for nm in declared], comm, device)
+        if failed is not None:
+            raise failed
         if sinfo.get("warning"):
             log_and_print(logger, "WARNING: " + sinfo["warning"])
         kk = int(s_.numel())
@@ -647,6 +792,7 @@ def _device_pipeline(ds: Dataset, parsed_config: dict, comm=None, kern=None, dev
         if primer is not None:
             primer.join()
         sync()
+        _raise_on_fill_codes(stats.get("fills"), comm, device)      # missing values: before any SVD work
         dt = _time.perf_counter() - t0
         log_and_print(logger, f"Ingest: {total / 1e9:.3f} GB to HBM in {dt:.2f} s ({total / 1e9 / max(dt, 1e-9):.2f} GB/s, "
                               f"{len(blocks)} row blocks, centre/scale on device){shard}")

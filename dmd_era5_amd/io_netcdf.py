@@ -25,7 +25,7 @@ import os
 import numpy as np
 
 from . import hdf5_lite
-from .labeled import Coord, DataArray, Dataset, LazyArray
+from .labeled import PACKING_ATTRS, Coord, DataArray, Dataset, LazyArray, Packing
 
 _EPOCH = np.datetime64("1970-01-01T00:00:00", "ns")
 TIME_UNITS = "hours since 1970-01-01 00:00:00"
@@ -214,6 +214,27 @@ def open_dataset(path: str) -> Dataset:
         "(set DMDX_HDF5_LIB to the directory holding libhdf5.so).")
 
 
+def _packing_of(attrs: dict, dtype) -> Packing | None:
+    """The CF packing a data variable's attributes describe (what ``xr.open_dataset`` applies by
+    default, ref era5_svd.py:132), or None.  Fill codes an integer variable cannot hold are ignored."""
+    if dtype is None or np.dtype(dtype).kind not in "iuf" or not any(k in attrs for k in PACKING_ATTRS):
+        return None
+    dtype = np.dtype(dtype)
+
+    def numbers(key):
+        a = np.asarray(attrs[key]).reshape(-1) if key in attrs else np.zeros(0)
+        return [v.item() for v in a] if a.dtype.kind in "iuf" else []
+
+    sf, ao = numbers("scale_factor")[:1] or [1.0], numbers("add_offset")[:1] or [0.0]
+    fills = []
+    for v in numbers("_FillValue") + numbers("missing_value"):
+        if dtype.kind == "f":
+            fills.append(float(v))
+        elif float(v).is_integer() and np.iinfo(dtype).min <= int(v) <= np.iinfo(dtype).max:
+            fills.append(int(v))
+    return Packing(sf[0], ao[0], fills)
+
+
 _ROW_COORDS = ("level", "latitude", "longitude", "original_variable", "delay")
 
 
@@ -231,7 +252,7 @@ def _assemble(raw: dict, dimsizes: dict, gattrs: dict) -> Dataset:
             listed.update(_s(attrs["coordinates"]).split())
     if "coordinates" in gattrs:
         listed.update(_s(gattrs["coordinates"]).split())
-    coords, data = {}, {}
+    coords, data, encodings = {}, {}, {}
     for name, (dims, vals, attrs) in raw.items():
         if "units" in attrs and " since " in str(attrs["units"]) and not isinstance(vals, LazyArray):
             vals = _decode_time(vals, attrs["units"].decode() if isinstance(attrs["units"], bytes) else attrs["units"])
@@ -245,11 +266,23 @@ def _assemble(raw: dict, dimsizes: dict, gattrs: dict) -> Dataset:
             is_coord = (dims == (name,)) or (name in _ROW_COORDS and dims == ("space",) and "space" in dimsizes
                                              and "U" in raw)
         attrs = {k: v for k, v in attrs.items() if k != "coordinates"}
+        packing = None if is_coord else _packing_of(attrs, getattr(vals, "dtype", None))
+        if packing is not None:
+            # CF packing is part of what the variable is (xarray: decoded values, the four attributes
+            # move to .encoding).  File-backed variables keep the file's dtype for their slab reads
+            # and carry the record; everything else is decoded here, once
+            if isinstance(vals, LazyArray):
+                vals.packing = packing
+            else:
+                vals = packing.decode(vals)
+            encodings[name] = {k: v for k, v in attrs.items() if k in PACKING_ATTRS}
+            attrs = {k: v for k, v in attrs.items() if k not in PACKING_ATTRS}
         (coords if is_coord else data)[name] = (dims, vals, attrs)
     cds = {k: Coord(d, v) for k, (d, v, _) in coords.items()}
     ds = Dataset(coords=cds, attrs={k: v for k, v in gattrs.items() if k != "coordinates"})
     for k, (d, v, a) in data.items():
         ds[k] = DataArray(v, d, {c: cds[c] for c in cds if set(cds[c].dims) <= set(d)}, a)
+        ds[k].encoding.update(encodings.get(k, {}))
     return ds
 
 
@@ -293,7 +326,7 @@ def _clean_attrs(items) -> dict:
 
 def _read_scipy(path: str) -> Dataset:
     netcdf_file = _safe_netcdf_file()
-    with netcdf_file(path, "r", mmap=False) as f:
+    with netcdf_file(path, "r", mmap=False, maskandscale=False) as f:   # (packing is decoded in _assemble, once)
         raw = {}
         for name, var in f.variables.items():
             attrs = _clean_attrs((k, v) for k, v in var._attributes.items())

@@ -372,6 +372,42 @@ class HipKernels:
         _lib.check(rc, "dmdx_row_center_scale_f32")
         return mean, std
 
+    # -- K14 ----------------------------------------------------------------
+    def unpack_i16_(self, codes: torch.Tensor, lds: int, tstep: int, Xt: torch.Tensor, row0: int, plane: int,
+                    seg_offset, scale_factor: float, add_offset: float, fills=(),
+                    fill_count: torch.Tensor | None = None) -> torch.Tensor:
+        """CF-packed int16 codes -> the snapshots ``Xt`` ((T, rows) fp32 view of a row block), in place.
+        ``codes``: device int16, the time slab as the file holds it (snapshot stride ``lds`` elements,
+        starting at the first snapshot to take); snapshot j of Xt is source snapshot j * tstep; row
+        row0 + r of the variable is element seg_offset[(row0 + r) // plane] + (row0 + r) % plane.
+        ``fills``: up to two fill codes (-> NaN); ``fill_count``: one device int64 that accumulates."""
+        if not codes.is_cuda or codes.dtype != torch.int16 or not codes.is_contiguous():
+            raise _lib.DmdxError("unpack_i16: codes must be a contiguous device int16 tensor")
+        if fill_count is not None and (not fill_count.is_cuda or fill_count.dtype != torch.int64 or fill_count.numel() != 1):
+            raise _lib.DmdxError("unpack_i16: fill_count must be one device int64")
+        rows, T, ldx = _check_mat(Xt, torch.float32, "unpack_i16 X")
+        segs = [int(o) for o in seg_offset]
+        fills = [int(f) for f in fills]
+        if not 1 <= len(segs) <= 64 or len(fills) > 2:
+            raise _lib.DmdxError(f"unpack_i16: {len(segs)} segments (1..64), {len(fills)} fill codes (0..2)")
+        need, plane, row0 = 0, int(plane), int(row0)
+        if T and rows and plane >= 1 and row0 >= 0 and row0 + rows <= len(segs) * plane:
+            last = row0 + rows - 1                       # the last code a snapshot addresses, per segment touched
+            need = (T - 1) * int(tstep) * int(lds) + max(
+                segs[s] + (plane if s < last // plane else last % plane + 1) for s in range(row0 // plane, last // plane + 1))
+        if codes.numel() < need:
+            raise _lib.DmdxError(f"unpack_i16: the call addresses {need} codes, the slab holds {codes.numel()}")
+        import ctypes as C
+
+        table = (C.c_int64 * len(segs))(*segs)
+        f = fills + [0, 0]
+        rc = self._timed("unpack_i16", (rows, T), lambda: self._lib.dmdx_unpack_i16_f32(
+            _ptr(codes), int(lds), T, int(tstep), rows, int(row0), int(plane), len(segs), table, float(scale_factor),
+            float(add_offset), len(fills), f[0], f[1], _ptr(Xt), ldx, _ptr(fill_count), self._stream()
+        ))
+        _lib.check(rc, "dmdx_unpack_i16_f32")
+        return Xt
+
     # -- K6 -----------------------------------------------------------------
     def delay_shift_sum(self, G64: torch.Tensor, d: int, want32: bool = False):
         """Gd[i, j] = sum_{k<d} G[i+k, j+k]."""

@@ -55,13 +55,58 @@ def _as_coords(coords) -> "OrderedDict[str, Coord]":
     return out
 
 
+PACKING_ATTRS = ("scale_factor", "add_offset", "_FillValue", "missing_value")
+
+
+class Packing:
+    """The CF packing of a variable: physical value = code * scale_factor + add_offset, NaN where the
+    code equals ``_FillValue`` / ``missing_value`` (``fills``: at most two distinct codes).
+
+    ``decode`` is the one arithmetic of the package for it (kernel K14 does the same on the device,
+    bit for bit): an fp64 multiply, an fp64 add, one rounding to float32.  float64 variables stay
+    float64; a variable with fill values only keeps its float dtype (integers become float32)."""
+
+    __slots__ = ("scale_factor", "add_offset", "fills")
+
+    def __init__(self, scale_factor=1.0, add_offset=0.0, fills=()):
+        self.scale_factor, self.add_offset = float(scale_factor), float(add_offset)
+        self.fills = tuple(dict.fromkeys(fills))
+
+    @property
+    def affine(self) -> bool:
+        return self.scale_factor != 1.0 or self.add_offset != 0.0
+
+    def out_dtype(self, dtype) -> np.dtype:
+        return np.dtype(np.float64) if np.dtype(dtype) == np.float64 else np.dtype(np.float32)
+
+    def decode(self, q) -> np.ndarray:
+        q = np.asarray(q)
+        out = self.out_dtype(q.dtype)
+        if self.affine or q.dtype.kind != "f":
+            with np.errstate(over="ignore", invalid="ignore"):
+                x = (q.astype(np.float64) * np.float64(self.scale_factor) + np.float64(self.add_offset)).astype(out)
+        else:
+            x = q.astype(out, copy=True)
+        for f in self.fills:
+            x[q == f] = np.nan
+        return x
+
+    def __repr__(self):
+        return f"Packing(scale_factor={self.scale_factor!r}, add_offset={self.add_offset!r}, fills={self.fills!r})"
+
+
 class LazyArray:
     """A file-backed array (like xarray's lazily opened variables): shape / dtype are known,
-    the data are read on first use, or in slabs along the first axis by the streaming ingest."""
+    the data are read on first use, or in slabs along the first axis by the streaming ingest.
 
-    def __init__(self, shape, dtype, read_all, read_slab, read_box=None):
+    ``dtype`` is the FILE's: ``read_slab`` / ``read_box`` deliver what is stored (the ingest moves
+    packed codes as they are).  ``packing`` (a :class:`Packing`, or None) says how stored values
+    become physical ones; ``np.asarray(lazy)`` applies it."""
+
+    def __init__(self, shape, dtype, read_all, read_slab, read_box=None, packing=None):
         self.shape, self.dtype, self.ndim = tuple(shape), np.dtype(dtype), len(shape)
         self._read_all, self.read_slab = read_all, read_slab
+        self.packing = packing
         # read_box(starts, counts, out=None): a hyperslab (one rank's latitude band of a time slab)
         self.read_box = read_box or self._box_from_slab
 
@@ -73,8 +118,14 @@ class LazyArray:
         out[...] = box
         return out
 
+    @property
+    def decoded_dtype(self) -> np.dtype:
+        return self.dtype if self.packing is None else self.packing.out_dtype(self.dtype)
+
     def __array__(self, dtype=None, copy=None):
         a = self._read_all()
+        if self.packing is not None:
+            a = self.packing.decode(a)
         return a.astype(dtype) if dtype is not None else a
 
 
@@ -87,6 +138,9 @@ class DataArray:
         self.coords = _as_coords(coords)
         self.attrs = dict(attrs or {})
         self.name = name
+        # how the variable was stored in the file it came from (xarray's .encoding): the reader puts
+        # the CF packing attributes here after decoding; nothing reads it when writing
+        self.encoding: dict = {}
 
     @property
     def values(self):
@@ -113,6 +167,9 @@ class DataArray:
 
     @property
     def dtype(self):
+        """dtype of ``.values`` (a packed file-backed variable: the decoded one, not the file's)."""
+        if isinstance(self._values, LazyArray):
+            return self._values.decoded_dtype
         return self._values.dtype
 
     @property

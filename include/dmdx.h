@@ -343,6 +343,36 @@ int dmdx_project_f32(const float* U, int64_t m, int64_t k, int64_t ldu, const fl
                      const float* mu, const float* sigma, double* C, int64_t ldc, double* energy, int accumulate,
                      void* workspace, size_t workspace_bytes, void* stream);
 
+/* ---- K14: CF-packed int16 codes -> fp32 snapshots of one row block ---------------------------------------------
+ * What xr.open_dataset's mask_and_scale decoding (reference era5_svd.py:132 through retrieve_era5_slice) does to a
+ * variable stored as int16 with scale_factor / add_offset / _FillValue / missing_value, done in HBM so that the
+ * packed bytes are what crosses the file system, the pinned staging and PCIe.
+ *   S     time slab of codes as it sits in the file: snapshot-major, space contiguous, snapshot stride lds (elements)
+ *   X     the row block's snapshots to write: T columns of `rows` floats, leading dimension ldx (already advanced
+ *         to the first snapshot); output snapshot j is source snapshot j * tstep (tstep >= 1)
+ *   row g = row0 + r of the variable (r < rows) is source element host_seg_offset[g / plane] + g % plane of its
+ *         snapshot: `plane` space points per segment, 1 <= nseg <= 64 segment offsets (>= 0) in a HOST array that
+ *         is copied into the launch -- a level selection, the latitude band of a shard and a block that
+ *         straddles two levels are all one table.  row0 + rows <= nseg * plane < 2^31.
+ *   x = fp32( fp64(q) * scale_factor + add_offset ): an fp64 multiply and an fp64 add (two roundings, not an FMA),
+ *         then one round-to-nearest conversion -- bit for bit numpy's
+ *         (q.astype(float64) * scale_factor + add_offset).astype(float32)
+ *   a code equal to one of the nfill (0, 1 or 2) fill codes fill0 / fill1 becomes the quiet NaN 0x7FC00000 and is
+ *         counted: fill_count (device, nullable) ACCUMULATES, one atomicAdd per workgroup that saw a fill; the
+ *         caller zeroes it once per variable.
+ * Memory: only the logical rows x T elements of X are written (not the ldx - rows behind a column: the zero rows of
+ * a padded block stay zero) and only the addressed codes of S are read (not the snapshots tstep skips).  No
+ * alignment is asked for beyond that of the element types: whatever X, ldx and row0 are, full 8-row chunks are
+ * stored as two aligned 16-byte stores and the ragged ends element by element; a chunk whose 8 codes lie in one
+ * segment at a 16-byte aligned address is read with one 16-byte load, any other as 2-byte loads of exactly the
+ * addressed codes, with identical bits.
+ * A refused call (negative sizes, tstep < 1, nseg outside 1..64, nfill outside 0..2, ldx < rows, plane < 1, rows
+ * outside the segments) returns DMDX_E_INVALID before any launch; T == 0 or rows == 0 returns 0 and writes nothing. */
+int dmdx_unpack_i16_f32(const int16_t* S, int64_t lds, int64_t T, int64_t tstep, int64_t rows, int64_t row0,
+                        int64_t plane, int nseg, const int64_t* host_seg_offset, double scale_factor,
+                        double add_offset, int nfill, int fill0, int fill1, float* X, int64_t ldx,
+                        unsigned long long* fill_count, void* stream);
+
 /* ---- upper triangle of a symmetric fp64 matrix <-> packed row by row ---------------------
  * packed[i (2n - i + 1) / 2 + (j - i)] = A[i][j], j >= i: what the Gram all-reduce of the
  * row-sharded path moves (n (n + 1) / 2 doubles instead of n^2).  unpack writes both triangles. */
