@@ -49,6 +49,7 @@ class OptDMDResult:
     converged: bool
     eigs_std: torch.Tensor | None = None   # bagging only
     info: dict = field(default_factory=dict)
+    trials: list["OptDMDResult"] | None = None   # bopdmd(keep_trials=True): every trial's own fit
 
     def reconstruct(self, t: torch.Tensor) -> torch.Tensor:
         """(len(t), n_s) = Phi(alpha) diag(b) modes^T."""
@@ -418,11 +419,16 @@ def _match(reference: torch.Tensor, values: torch.Tensor) -> torch.Tensor:
 
 
 def bopdmd(H: torch.Tensor, t: torch.Tensor, r: int, num_trials: int = 0, trial_size: float = 0.6,
-           seed: int = 0, **kwargs) -> OptDMDResult:
+           seed: int = 0, keep_trials: bool = False, **kwargs) -> OptDMDResult:
     """Optimized DMD with optional bagging: ``num_trials`` refits on random subsets
     (``trial_size`` of the snapshots, without replacement, kept in time order) started from the
     full-data eigenvalues; the reported eigenvalues are the trial mean, ``eigs_std`` their spread,
-    modes / amplitudes come from the projection of the full data on the averaged eigenvalues."""
+    modes / amplitudes come from the projection of the full data on the averaged eigenvalues.
+
+    ``keep_trials=True`` keeps what the bag knows beyond the eigenvalues: ``trials`` holds the untouched
+    ``optdmd`` result of every trial (an ensemble of models: forecast.ensemble_coefficients,
+    DmdForecast.ensemble_fields / ensemble_score) and ``info["trial_indices"]`` the sorted snapshot indices
+    each was fitted on.  Every other field is the same, bit for bit, as without it."""
     base = optdmd(H, t, r, **kwargs)
     if num_trials <= 0:
         return base
@@ -430,11 +436,14 @@ def bopdmd(H: torch.Tensor, t: torch.Tensor, r: int, num_trials: int = 0, trial_
     m = H.shape[0]
     size = max(2 * r, int(round(trial_size * m))) if trial_size <= 1 else int(trial_size)
     size = min(size, m)
-    trials = []
+    trials, kept, kept_idx = [], [], []
     for _ in range(num_trials):
         idx = torch.from_numpy(np.sort(rs.choice(m, size=size, replace=False))).to(H.device)
         res = optdmd(H[idx], t[idx], r, alpha0=base.eigs, **kwargs)
         trials.append(_match(base.eigs, res.eigs))
+        if keep_trials:
+            kept.append(res)
+            kept_idx.append(idx.cpu())
     A = torch.stack(trials)
     mean = A.mean(dim=0)
     std = torch.sqrt(((A - mean).abs() ** 2).mean(dim=0))
@@ -443,7 +452,10 @@ def bopdmd(H: torch.Tensor, t: torch.Tensor, r: int, num_trials: int = 0, trial_
     amp = torch.linalg.norm(B, dim=1)
     modes = (B / amp[:, None].clamp_min(1e-300).to(cdtype)).T.contiguous()
     order = torch.argsort(-amp)
+    info = {"num_trials": num_trials, "trial_size": size, "base_error": base.rel_error}
+    if keep_trials:
+        info["trial_indices"] = kept_idx
     return OptDMDResult(eigs=mean[order], modes=modes[:, order], amplitudes=amp[order].to(std.dtype),
                         rel_error=float(torch.linalg.norm(R) / torch.linalg.norm(H)),
                         n_iter=base.n_iter, converged=base.converged, eigs_std=std[order],
-                        info={"num_trials": num_trials, "trial_size": size, "base_error": base.rel_error})
+                        info=info, trials=kept if keep_trials else None)

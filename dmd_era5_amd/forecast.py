@@ -12,7 +12,11 @@ forecast), and scores it against real snapshots without materialising the fields
 were not part of the decomposition to their coefficients ``c = U^T ((x - mu) / sigma)`` and energy
 ``||(x - mu) / sigma||^2`` -- is K13 (``HipKernels.project``, csrc/project.hip): out-of-sample validation
 of the basis, compression of new data, and ``DmdForecast.restart``, which re-fits the amplitudes of a
-fitted model to a new state so that the forecast starts from the latest analysis.
+fitted model to a new state so that the forecast starts from the latest analysis.  A bagged fit
+(``bopdmd(keep_trials=True)``) is an ensemble of models: :func:`ensemble_coefficients` turns it into the mean
+coefficients and the scaled member deviations, K12 expands the mean and K15 (``HipKernels.spread`` /
+``spread_score``, csrc/spread.hip) the spread ``|sigma| sqrt(sum_b (U d_b)^2)`` per grid point and lead time
+without storing a member field; ``DmdForecast.ensemble_score`` sets that spread against the error the mean makes.
 
 Layout as everywhere in the package (kernels.py): a column-major matrix is held as its row-major
 transpose -- U blocks are ``(k, rows)`` (``SvdResult.Ut``), coefficients ``Ct`` are ``(T, k)``,
@@ -31,8 +35,8 @@ import torch
 from .bopdmd import OptDMDResult, _phi
 from .svd import Comm, _kern, _pitched, embed_view
 
-__all__ = ["svd_coefficients", "dmd_coefficients", "expand_blocks", "iter_fields", "score_blocks", "project_blocks",
-           "DmdForecast"]
+__all__ = ["svd_coefficients", "dmd_coefficients", "ensemble_coefficients", "expand_blocks", "iter_fields",
+           "score_blocks", "project_blocks", "spread_blocks", "spread_score_blocks", "DmdForecast"]
 
 
 # ---------------------------------------------------------------------------
@@ -50,14 +54,47 @@ def dmd_coefficients(result: OptDMDResult, t: torch.Tensor) -> tuple[torch.Tenso
     of U: ``(Re(Phi(t) diag(b) modes^T) as (T, n_s) fp32, max|Im| / max|Re|)``.  Phi is formed in
     complex128 (on the device by dmdx_exp_basis).  The fit does not force conjugate pairs, so the
     un-projected value has an imaginary part; its relative size says how real the model is."""
+    tt = torch.as_tensor(t, dtype=torch.float64, device=result.eigs.device).reshape(-1)
+    re, ratio = _model64(result, tt)
+    return re.to(torch.float32).contiguous(), ratio
+
+
+def _model64(result: OptDMDResult, tt: torch.Tensor) -> tuple[torch.Tensor, float]:
+    """The arithmetic of :func:`dmd_coefficients` up to its rounding: (Re Z (T, n_s) fp64, imag ratio)."""
     alpha = result.eigs.to(torch.complex128)
-    tt = torch.as_tensor(t, dtype=torch.float64, device=alpha.device).reshape(-1)
-    phi = _phi(alpha, tt, torch.complex128)
+    phi = _phi(alpha, tt.to(alpha.device), torch.complex128)
     Z = (phi * result.amplitudes.to(torch.complex128)) @ result.modes.to(torch.complex128).T
     re_max = float(Z.real.abs().max()) if Z.numel() else 0.0
     im_max = float(Z.imag.abs().max()) if Z.numel() else 0.0
     ratio = im_max / re_max if re_max > 0.0 else (0.0 if im_max == 0.0 else float("inf"))
-    return Z.real.to(torch.float32).contiguous(), ratio
+    return Z.real, ratio
+
+
+def ensemble_coefficients(results, t: torch.Tensor, ddof: int = 1) -> tuple[torch.Tensor, torch.Tensor, float]:
+    """An ensemble of fitted models (``OptDMDResult.trials`` of a bagged fit) at the times ``t``:
+    ``(Cbar (T, k) fp32, Dev (B, T, k) fp32, imag_ratio)``.  Every member is evaluated as
+    :func:`dmd_coefficients` does, in complex128; the mean over the members and the deviations are formed in
+    fp64, the deviations scaled by ``1 / sqrt(B - ddof)`` and both rounded once to fp32, so that
+    ``sum_b (U Dev[b])^2`` is the variance (``ddof`` as numpy's) of the member fields.  ``imag_ratio`` is the
+    largest of the members'."""
+    results = list(results)
+    B = len(results)
+    if B - ddof < 1:
+        raise ValueError(f"ensemble_coefficients: {B} members with ddof = {ddof}: B - ddof must be >= 1")
+    ks = {int(r.modes.shape[0]) for r in results}
+    if len(ks) != 1:
+        raise ValueError(f"ensemble_coefficients: the members have different numbers of coordinates {sorted(ks)}")
+    dev = results[0].eigs.device
+    tt = torch.as_tensor(t, dtype=torch.float64, device=dev).reshape(-1)
+    Z, ratio = [], 0.0
+    for r in results:
+        z, q = _model64(r, tt)
+        Z.append(z.to(dev))
+        ratio = max(ratio, q)
+    Z = torch.stack(Z)                                   # (B, T, k) fp64
+    Cbar = Z.mean(dim=0)
+    Dev = (Z - Cbar) / (B - ddof) ** 0.5
+    return Cbar.to(torch.float32).contiguous(), Dev.to(torch.float32).contiguous(), ratio
 
 
 # ---------------------------------------------------------------------------
@@ -114,6 +151,53 @@ def _project(kern, Ut, Xt, mean, std, out, want_energy=True):
     if want_energy:
         out[1].add_(e)
     return out
+
+
+def _spread64(Ut, Dev):
+    """sum_b (U d_b)^2 as (T, rows) fp64."""
+    P = Dev.to(torch.float64) @ Ut.to(torch.float64)       # (B, T, rows)
+    return (P * P).sum(dim=0)
+
+
+def _spread(kern, Ut, Dev, std, out=None):
+    f = getattr(kern, "spread", None)
+    if f is not None:
+        return f(Ut, Dev, std, out=out)
+    S = torch.sqrt(_spread64(Ut, Dev))
+    if std is not None:
+        S = S * std.to(torch.float64).abs()
+    S = S.to(torch.float32)
+    if out is None:
+        return S
+    out.copy_(S)
+    return out
+
+
+def _spread_score(kern, Ut, Dev, std, out, want_rows):
+    f = getattr(kern, "spread_score", None)
+    if f is not None:
+        return f(Ut, Dev, std, out=out, want_rows=want_rows)
+    V = _spread64(Ut, Dev)
+    if std is not None:
+        V = V * std.to(torch.float64) ** 2
+    var = V.sum(dim=1)
+    if out is not None:
+        out += var
+        var = out
+    return var, (V.sum(dim=0) if want_rows else None)
+
+
+def _pitched_dev(kern, Dev: torch.Tensor) -> torch.Tensor:
+    """The (B, T, k) deviations with every k-vector on a 16-byte boundary, ONCE for all row blocks (the image
+    HipKernels.spread hands to K15 as it is)."""
+    if getattr(kern, "pitch", None) is None:
+        return Dev
+    B, T, k = Dev.shape
+    if Dev.is_contiguous() and k % 4 == 0 and Dev.data_ptr() % 16 == 0:
+        return Dev
+    Dp = torch.zeros((B, T, (k + 3) // 4 * 4), dtype=Dev.dtype, device=Dev.device)
+    Dp[:, :, :k] = Dev
+    return Dp[:, :, :k]
 
 
 def _vec(v, b, reps, device):
@@ -236,6 +320,54 @@ def score_blocks(Ublocks, Ct: torch.Tensor, Xblocks, means=None, stds=None, dela
     return res
 
 
+def spread_blocks(Ublocks, Dev: torch.Tensor, stds=None, delay_block: int | None = None, out=None, delay: int = 1,
+                  kern=None) -> list[torch.Tensor]:
+    """The ensemble spread of every row block: a list of (T, rows) fp32 tensors
+    ``|std| * sqrt(sum_b (U Dev[b])^2)`` -- with ``Dev`` of :func:`ensemble_coefficients` the standard deviation
+    over the members of the fields ``mean + std * (U c_b)``, per grid point and time (K15; no member field is
+    stored).  ``stds``, ``delay``, ``delay_block`` and ``out`` as in :func:`expand_blocks`; a spread has no mean."""
+    kern = _kern(kern)
+    Dp = _pitched_dev(kern, Dev)
+    res = []
+    for b, U in enumerate(Ublocks):
+        Ub, reps = _block_rows(U, delay, delay_block)
+        res.append(_spread(kern, Ub, Dp, _vec(stds, b, reps, Ub.device), out=None if out is None else out[b]))
+    return res
+
+
+def spread_score_blocks(Ublocks, Dev: torch.Tensor, stds=None, delay: int = 1, comm: Comm | None = None,
+                        want_rows: bool = False, kern=None) -> dict:
+    """The ensemble spread summed over the grid, without storing it: per snapshot ``var`` = sum_i S[i, t]^2 and
+    ``spread`` = sqrt(var / rows) (the RMS spread, the counterpart of ``rmse`` of :func:`score_blocks`), the
+    totals ``var_total`` and ``spread_total`` = sqrt(var_total / (rows T)), ``rows`` (global), and with
+    ``want_rows`` the list ``row_spread`` of per-row RMS spread vectors of the local blocks.  With a delay d
+    all d * rows rows of every block are summed, as :func:`score_blocks` scores them.
+
+    Row shards: ONE ``comm.allreduce_sum_`` of the stacked ``[var, rows]`` per call, whatever the number of
+    local blocks.  A rank without blocks still takes part."""
+    kern = _kern(kern)
+    comm = comm or Comm()
+    T = int(Dev.shape[1])
+    Dp = _pitched_dev(kern, Dev)
+    var, rows_local, row_var = None, 0, []
+    for b, U in enumerate(Ublocks):
+        var, r = _spread_score(kern, U, Dp, _vec(stds, b, delay, U.device), var, want_rows)
+        rows_local += int(U.shape[1])
+        if want_rows:
+            row_var.append(r)
+    if var is None:        # a rank without blocks still takes part in the collective
+        var = torch.zeros(T, dtype=torch.float64, device=Dev.device)
+    flat = torch.cat([var, torch.tensor([float(rows_local)], dtype=torch.float64, device=var.device)])
+    flat = comm.allreduce_sum_(flat, tag="spread_allreduce")
+    var, rows = flat[:T], float(flat[T])
+    var_total = var.sum()
+    res = {"var": var, "spread": torch.sqrt(var / rows), "var_total": float(var_total),
+           "spread_total": float(torch.sqrt(var_total / (rows * T))), "rows": int(rows)}
+    if want_rows:
+        res["row_spread"] = [torch.sqrt(r / T) for r in row_var]
+    return res
+
+
 def project_blocks(Ublocks, Xblocks, means=None, stds=None, delay: int = 1, comm: Comm | None = None, kern=None,
                    shape: tuple[int, int] | None = None) -> dict:
     """The coefficients of raw snapshots in the basis U: ``c_t = U^T ((x_t - mean) / std)``, X read once and
@@ -335,6 +467,51 @@ class DmdForecast:
         Ct, imag = self.coefficients(t)
         res = score_blocks(self.Ublocks, Ct, Xblocks, self.means, self.stds, self.delay, comm, want_rows, self.kern)
         res["imag_ratio"] = imag
+        return res
+
+    def ensemble_coefficients(self, t, ddof: int = 1) -> tuple[torch.Tensor, torch.Tensor, float]:
+        """:func:`ensemble_coefficients` of the trials of a bagged fit, on the device of the U blocks."""
+        trials = None if self.result is None else getattr(self.result, "trials", None)
+        if not trials:
+            raise ValueError("DmdForecast: the result holds no trials; fit with bopdmd(..., num_trials > 0, "
+                             "keep_trials=True)")
+        Cbar, Dev, imag = ensemble_coefficients(trials, t, ddof)
+        k = int(self.Ublocks[0].shape[0])
+        if Cbar.shape[1] != k:
+            raise ValueError(f"DmdForecast: the trials were fitted on {Cbar.shape[1]} coordinates, U has {k} columns")
+        dev = self.Ublocks[0].device
+        return Cbar.to(dev), Dev.to(dev), imag
+
+    def ensemble_fields(self, t, delay_block: int | None = 0, out=None) -> tuple[list[torch.Tensor], list[torch.Tensor]]:
+        """``(mean_blocks, spread_blocks)`` of the bagged fit's trials at the times ``t``: the fields of the
+        ensemble-mean coefficients (K12) and the standard deviation (ddof 1) of the member fields per grid
+        point and time (K15), (len(t), rows) per block each.  ``out``: a pair of lists of views to write
+        into."""
+        Cbar, Dev, _ = self.ensemble_coefficients(t)
+        if self.delay == 1:
+            delay_block = None
+        om, osp = (None, None) if out is None else out
+        mean = expand_blocks(self.Ublocks, Cbar, self.means, self.stds, delay_block, out=om, delay=self.delay,
+                             kern=self.kern)
+        spread = spread_blocks(self.Ublocks, Dev, self.stds, delay_block, out=osp, delay=self.delay, kern=self.kern)
+        return mean, spread
+
+    def ensemble_score(self, Xblocks, t, comm: Comm | None = None, want_rows: bool = False) -> dict:
+        """:func:`score_blocks` of the ENSEMBLE MEAN of the trials against the snapshots ``Xblocks`` at the times
+        ``t``, plus the ensemble's ``spread`` / ``spread_total`` (:func:`spread_score_blocks`; ``var``,
+        ``var_total`` and with ``want_rows`` ``row_spread`` too) and how they compare: ``spread_skill`` =
+        spread / rmse per snapshot and ``spread_skill_total``.  A well calibrated ensemble has a ratio near 1;
+        below 1 it is over-confident.  Two launches per block and two collectives."""
+        Cbar, Dev, imag = self.ensemble_coefficients(t)
+        res = score_blocks(self.Ublocks, Cbar, Xblocks, self.means, self.stds, self.delay, comm, want_rows, self.kern)
+        sp = spread_score_blocks(self.Ublocks, Dev, self.stds, self.delay, comm, want_rows, self.kern)
+        res["imag_ratio"] = imag
+        for key in ("var", "spread", "var_total", "spread_total"):
+            res[key] = sp[key]
+        if want_rows:
+            res["row_spread"] = sp["row_spread"]
+        res["spread_skill"] = sp["spread"] / res["rmse"]
+        res["spread_skill_total"] = sp["spread_total"] / res["rmse_total"] if res["rmse_total"] > 0.0 else float("inf")
         return res
 
     def reconstruct_svd(self, n_components: int | None = None, cols=None, delay_block: int | None = 0,

@@ -318,6 +318,76 @@ class HipKernels:
         _lib.check(rc, "dmdx_expand_score_f32")
         return cols, rows
 
+    # -- K15 ----------------------------------------------------------------
+    @property
+    def spread_max_k(self) -> int:
+        return int(self._lib.dmdx_spread_max_k())
+
+    def _spread_args(self, Ut, Dev, std, who):
+        m, k, ldu = _check_mat(Ut, torch.float32, f"{who} U")
+        if not Dev.is_cuda or Dev.dtype != torch.float32 or Dev.dim() != 3 or Dev.device != Ut.device:
+            raise _lib.DmdxError(f"{who}: Dev must be a 3-D (B, T, k) fp32 tensor on {Ut.device}, got {Dev.dtype} "
+                                 f"{tuple(Dev.shape)} on {Dev.device}")
+        B, T, kd = Dev.shape
+        if kd != k or B < 1 or T < 1:
+            raise _lib.DmdxError(f"{who}: Dev is {tuple(Dev.shape)}, U has {k} columns; (B >= 1, T >= 1, {k}) asked for")
+        # the (B T, ldd) row-major image of the k x (B T) column-major D, rows on 16-byte boundaries
+        # (a Dev that already is such an image -- forecast._pitched_dev -- is taken as it is)
+        if (k == 1 or Dev.stride(2) == 1) and Dev.stride(1) >= k and Dev.stride(0) == T * Dev.stride(1):
+            Dt = Dev.as_strided((B * T, k), (Dev.stride(1), 1))
+        else:
+            Dt = Dev.reshape(B * T, k)
+        Dt = self.pitch(Dt)
+        ldd = _check_mat(Dt, torch.float32, f"{who} Dev")[2]
+        if std is not None and (std.dtype != torch.float32 or std.shape != (m,) or std.device != Ut.device
+                                or not std.is_contiguous()):
+            raise _lib.DmdxError(f"{who}: std must be a contiguous fp32 vector of length {m} on {Ut.device}")
+        return m, k, ldu, int(T), int(B), Dt, ldd
+
+    def spread(self, Ut: torch.Tensor, Dev: torch.Tensor, std: torch.Tensor | None = None,
+               out: torch.Tensor | None = None) -> torch.Tensor:
+        """S = |std| * sqrt(sum_b (U d_b)^2): the spread of B member fields whose scaled deviations from the
+        ensemble mean are ``Dev``.  Ut: (k, m), Dev: (B, T, k) fp32, std: (m,) fp32 or None -> St: (T, m)
+        fp32.  No member field is stored.
+
+        ``out``: a (T, m) fp32 view to write into (inner stride 1, any row stride >= m)."""
+        m, k, ldu, T, B, Dt, ldd = self._spread_args(Ut, Dev, std, "spread")
+        if out is not None:
+            mo, To, lds = _check_mat(out, torch.float32, "spread out")
+            if (mo, To) != (m, T) or out.device != Ut.device:
+                raise _lib.DmdxError(f"spread: out must be ({T}, {m}) on {Ut.device}, got {tuple(out.shape)}")
+            St = out
+        else:
+            St, lds = torch.empty((T, m), dtype=torch.float32, device=Ut.device), m
+        rc = self._timed("spread", (m, k, T, B), lambda: self._lib.dmdx_spread_f32(
+            _ptr(Ut), m, k, ldu, _ptr(Dt), ldd, T, B, _ptr(std), _ptr(St), lds, self._stream()
+        ))
+        _lib.check(rc, "dmdx_spread_f32")
+        return St
+
+    def spread_score(self, Ut: torch.Tensor, Dev: torch.Tensor, std: torch.Tensor | None = None,
+                     out: torch.Tensor | None = None, want_rows: bool = False):
+        """The sums of the squared spread, S never stored.  Ut: (k, m), Dev: (B, T, k) fp32 -> (var, rows):
+        ``var`` the (T,) fp64 sum_i S[i, t]^2 per snapshot, ``rows`` the (m,) fp64 sum_t S[i, t]^2 per space
+        point, or None.
+
+        ``out``: a contiguous (T,) fp64 tensor the snapshot sums are ADDED to (row blocks of U)."""
+        m, k, ldu, T, B, Dt, ldd = self._spread_args(Ut, Dev, std, "spread_score")
+        if out is not None:
+            if out.shape != (T,) or out.dtype != torch.float64 or not out.is_contiguous() or out.device != Ut.device:
+                raise _lib.DmdxError(f"spread_score: out must be a contiguous ({T},) fp64 tensor on {Ut.device}")
+            var = out
+        else:
+            var = torch.empty(T, dtype=torch.float64, device=Ut.device)
+        rows = torch.empty(m, dtype=torch.float64, device=Ut.device) if want_rows else None
+        ws = self._workspace(Ut.device, self._lib.dmdx_spread_score_workspace_bytes(m, k, T, B))
+        rc = self._timed("spread_score", (m, k, T, B), lambda: self._lib.dmdx_spread_score_f32(
+            _ptr(Ut), m, k, ldu, _ptr(Dt), ldd, T, B, _ptr(std), _ptr(var), _ptr(rows), int(out is not None),
+            _ptr(ws), ws.numel(), self._stream()
+        ))
+        _lib.check(rc, "dmdx_spread_score_f32")
+        return var, rows
+
     # -- K13 ----------------------------------------------------------------
     @property
     def project_max_k(self) -> int:

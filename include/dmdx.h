@@ -60,7 +60,13 @@
  *     energy is written with accumulate == 0 and read and written with accumulate != 0, nothing else.  No
  *     alignment is asked for: a 16-byte aligned U with ldu % 4 == 0, X with ldx % 4 == 0, mu, sigma each
  *     select 16-byte loads for that operand, anything else one dword per lane with the same values.  m, T
- *     and every leading dimension must be < 2^31 (DMDX_E_INVALID beyond, before anything is written).
+ *     and every leading dimension must be < 2^31 (DMDX_E_INVALID beyond, before anything is written);
+ *   - K15 (dmdx_spread_f32, dmdx_spread_score_f32): U, D and sigma are only read, inside their logical elements
+ *     (U: m x k, D: k x (B T), column b T + t = member b at snapshot t); every logical element of S, var_row and
+ *     -- with accumulate == 0 -- var_col is written, nothing else.  S, U and sigma are addressed with 64-bit
+ *     offsets and one dword per lane: no alignment is asked for and none selects another path; a 16-byte aligned D
+ *     with ldd % 4 == 0 is staged with 16-byte loads, with identical values.  m, T, B T and every leading
+ *     dimension must be < 2^31 (DMDX_E_INVALID beyond, before anything is written).
  *
  * Value contract (tests/test_gpu_value_domain.py holds every fp32 entry point to it)
  *   - NaN / Inf propagate like IEEE arithmetic on the logical operands, nothing more and nothing less:
@@ -110,6 +116,15 @@
  *     of a row range < 2^24) C and energy are the integer results bit for bit.  (2^e X, 2^e mu, 2^e sigma) leaves
  *     every bit of C and energy unchanged, 2^e U gives exactly 2^e C.  Error: one fp32 chain of at most
  *     DMDX_PROJECT_FP32_ROWS rows per row range, fp64 across: (DMDX_PROJECT_FP32_ROWS + 4) 2^-24 sum |u||xt|.
+ *     K15: a non-finite D[j, b T + t] makes exactly column t of S non-finite, and with it var_col[t] and every
+ *     var_row[i]; a non-finite U[i, j] or sigma[i] hits row i of S only (and var_row[i], every var_col).  The class
+ *     is NaN where numpy's fp64 evaluation of |sigma| sqrt(sum_b (U D_b)^2) is NaN and +Inf where it is +Inf; every
+ *     element not involved is bit-identical to the result without the non-finite value.  S is never negative and
+ *     never -0.  k is padded with zeros in U AND in D, as in K12, and the k order of the chain is K12's: with B = 1
+ *     and normal magnitudes sqrt(fl(a^2)) = |a| exactly (the root is correctly rounded: no fast-math), so S is bit
+ *     for bit |Xhat| of dmdx_expand_f32(U, D, mu = NULL, sigma).  Integer U and D with every P_b^2 summed below 2^24
+ *     and sigma a power of two give the integer V, var_col and var_row bit for bit (S = |sigma| sqrt(V) correctly
+ *     rounded); (2^e U, 2^-e D) leaves every output bit unchanged (magnitudes as above).
  */
 #ifndef DMDX_H
 #define DMDX_H
@@ -342,6 +357,32 @@ size_t dmdx_project_workspace_bytes(int64_t m, int64_t k, int64_t T);
 int dmdx_project_f32(const float* U, int64_t m, int64_t k, int64_t ldu, const float* X, int64_t ldx, int64_t T,
                      const float* mu, const float* sigma, double* C, int64_t ldc, double* energy, int accumulate,
                      void* workspace, size_t workspace_bytes, void* stream);
+
+/* ---- K15: ensemble spread of B models in the rank-k coordinates, and its sums --------------------------------
+ * What a bagged optimized-DMD fit (bopdmd(keep_trials=True)) says about its own uncertainty, on the grid.  The
+ * member coefficients c_b(t), b < B, have the mean cbar(t); D (k x (B T), ldd) holds the scaled deviations
+ * d_b(t) = (c_b(t) - cbar(t)) / sqrt(B - ddof) in column b T + t.  U (m x k, ldu) and sigma (m floats, nullable: 1)
+ * as in K12; there is no mu: a spread has no offset.  1 <= k <= dmdx_spread_max_k() (256).
+ *   P_b[i, t] = sum_j U[i, j] D[j, b T + t]           one fp32 MFMA chain over k per member, K12's chain
+ *   V[i, t]   = sum_b P_b[i, t]^2                     fp32, b = 0, 1, ... in this order, one rounding per member
+ *   S[i, t]   = |sigma[i]| * sqrt(V[i, t])            m x T, lds; the sample standard deviation of the B fields
+ * The ensemble-mean field itself is K12 with cbar.  No member field is ever stored.
+ *
+ * dmdx_spread_score_f32 forms the same V and never stores S:
+ *   var_col[t] (+)= sum_i sigma[i]^2 V[i, t]          T doubles, required
+ *   var_row[i]  =  sum_t sigma[i]^2 V[i, t]           m doubles, nullable, always overwritten
+ * accumulate != 0 adds to var_col (U given as row blocks).  fp32 sums cover at most DMDX_SPREAD_FP32_ROWS rows
+ * (columns: the rows of one workgroup; rows: 16 snapshots), fp64 beyond, through per-workgroup partial slots in
+ * the workspace and reduce kernels: no atomics, the order of every sum depends on (m, T, B) only, results are
+ * bit-wise reproducible. */
+#define DMDX_SPREAD_FP32_ROWS 128
+int dmdx_spread_max_k(void);
+int dmdx_spread_f32(const float* U, int64_t m, int64_t k, int64_t ldu, const float* D, int64_t ldd, int64_t T, int64_t B,
+                    const float* sigma, float* S, int64_t lds, void* stream);
+size_t dmdx_spread_score_workspace_bytes(int64_t m, int64_t k, int64_t T, int64_t B);
+int dmdx_spread_score_f32(const float* U, int64_t m, int64_t k, int64_t ldu, const float* D, int64_t ldd, int64_t T, int64_t B,
+                          const float* sigma, double* var_col, double* var_row, int accumulate,
+                          void* workspace, size_t workspace_bytes, void* stream);
 
 /* ---- K14: CF-packed int16 codes -> fp32 snapshots of one row block ---------------------------------------------
  * What xr.open_dataset's mask_and_scale decoding (reference era5_svd.py:132 through retrieve_era5_slice) does to a
