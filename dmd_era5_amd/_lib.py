@@ -70,6 +70,10 @@ SIGNATURES = {
     "dmdx_spread_f32": (C.c_int, [_p, _i64, _i64, _i64, _p, _i64, _i64, _i64, _p, _p, _i64, _p]),
     "dmdx_spread_score_workspace_bytes": (_sz, [_i64, _i64, _i64, _i64]),
     "dmdx_spread_score_f32": (C.c_int, [_p, _i64, _i64, _i64, _p, _i64, _i64, _i64, _p, _p, _p, C.c_int, _p, _sz, _p]),
+    "dmdx_verify_max_k": (C.c_int, []),
+    "dmdx_verify_workspace_bytes": (_sz, [_i64, _i64, _i64]),
+    "dmdx_verify_f32": (C.c_int, [_p, _i64, _i64, _i64, _p, _i64, _i64, _p, _p, _p, _i64, _p, _p, _p, _i64, _p, _i64,
+                                  C.c_int, _p, _sz, _p]),
     "dmdx_unpack_i16_f32": (C.c_int, [_p, _i64, _i64, _i64, _i64, _i64, _i64, C.c_int, _p, C.c_double, C.c_double,
                                       C.c_int, C.c_int, C.c_int, _p, _i64, _p, _p]),
     "dmdx_pack_triu_f64": (C.c_int, [_p, _i64, _i64, _p, _p]),

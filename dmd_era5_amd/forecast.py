@@ -17,6 +17,9 @@ fitted model to a new state so that the forecast starts from the latest analysis
 coefficients and the scaled member deviations, K12 expands the mean and K15 (``HipKernels.spread`` /
 ``spread_score``, csrc/spread.hip) the spread ``|sigma| sqrt(sum_b (U d_b)^2)`` per grid point and lead time
 without storing a member field; ``DmdForecast.ensemble_score`` sets that spread against the error the mean makes.
+What a forecast of gridded fields is published with -- RMSE, bias and anomaly correlation, weighted by the area of
+the grid cells, per variable and level, with masked points left out -- is K16 (``HipKernels.verify``,
+csrc/verify.hip): :func:`area_weights`, :func:`verify_blocks` and ``DmdForecast.verify``.
 
 Layout as everywhere in the package (kernels.py): a column-major matrix is held as its row-major
 transpose -- U blocks are ``(k, rows)`` (``SvdResult.Ut``), coefficients ``Ct`` are ``(T, k)``,
@@ -36,7 +39,8 @@ from .bopdmd import OptDMDResult, _phi
 from .svd import Comm, _kern, _pitched, embed_view
 
 __all__ = ["svd_coefficients", "dmd_coefficients", "ensemble_coefficients", "expand_blocks", "iter_fields",
-           "score_blocks", "project_blocks", "spread_blocks", "spread_score_blocks", "DmdForecast"]
+           "score_blocks", "project_blocks", "spread_blocks", "spread_score_blocks", "area_weights", "verify_blocks",
+           "DmdForecast"]
 
 
 # ---------------------------------------------------------------------------
@@ -132,6 +136,27 @@ def _expand_score(kern, Ut, Ct, Xt, mean, std, out, want_rows):
         out += cols
         cols = out
     return cols, ((E * E).sum(dim=0) if want_rows else None)
+
+
+def _verify(kern, Ut, Ct, Xt, mean, std, weight, clim, out, want_rows):
+    f = getattr(kern, "verify", None)
+    if f is not None:
+        return f(Ut, Ct, Xt, mean, std, weight, clim, out=out, want_rows=want_rows)
+    X = Xt.to(torch.float64)
+    Xh = _affine64(Ut, Ct, mean, std)
+    cl = clim if clim is not None else mean
+    cl = 0.0 if cl is None else cl.to(torch.float64)
+    e, fc, a = Xh - X, Xh - cl, X - cl
+    Q = torch.stack([e * e, e, a, fc * fc, a * a, fc * a])          # (6, T, rows)
+    if weight is None:
+        cols = Q.sum(dim=2)
+    else:                                                           # weight 0 leaves the row out: no 0 * NaN
+        sel = weight != 0
+        cols = (Q[:, :, sel] * weight[sel].to(torch.float64)).sum(dim=2)
+    if out is not None:
+        out += cols
+        cols = out
+    return cols, (Q.sum(dim=1) if want_rows else None)
 
 
 def _project(kern, Ut, Xt, mean, std, out, want_energy=True):
@@ -368,6 +393,141 @@ def spread_score_blocks(Ublocks, Dev: torch.Tensor, stds=None, delay: int = 1, c
     return res
 
 
+def area_weights(latitude_deg) -> torch.Tensor:
+    """The area weight of every row of a regular latitude / longitude grid: ``cos(latitude)``, formed in fp64,
+    clamped at 0 (a latitude a rounding past a pole) and rounded to fp32.  ``latitude_deg``: the latitude of
+    every ROW in degrees (for a (lat, lon) plane ``lat.repeat_interleave(n_lon)``), any array-like.
+    The normalisation is irrelevant: every score of :func:`verify_blocks` divides by the sum of the weights."""
+    lat = torch.as_tensor(latitude_deg, dtype=torch.float64).reshape(-1)
+    return torch.cos(torch.deg2rad(lat)).clamp_(min=0.0).to(torch.float32)
+
+
+def _runs(labels) -> list[tuple[int, int, int]]:
+    """A label vector cut into its runs: [(first row, one past the last row, label)]."""
+    lab = torch.as_tensor(labels).reshape(-1).cpu()
+    if lab.numel() == 0:
+        return []
+    if lab.dtype.is_floating_point or lab.dtype == torch.bool:
+        raise ValueError(f"verify_blocks: group labels must be integers, got {lab.dtype}")
+    cut = (torch.nonzero(lab[1:] != lab[:-1]).reshape(-1) + 1).tolist()
+    edges = [0] + cut + [int(lab.numel())]
+    return [(a, b, int(lab[a])) for a, b in zip(edges[:-1], edges[1:])]
+
+
+def verify_blocks(Ublocks, Ct: torch.Tensor, Xblocks, means=None, stds=None, weights=None, clims=None, groups=None,
+                  delay: int = 1, comm: Comm | None = None, want_rows: bool = False, kern=None,
+                  n_groups: int | None = None) -> dict:
+    """The verification of ``mean + std * (U c)`` (the forecast) against the snapshots ``Xblocks`` (the analysis)
+    on the grid, without storing the fields (K16): weighted RMSE, bias and anomaly correlation per group of rows.
+
+    ``Xblocks``, ``means``, ``stds``, ``delay`` as in :func:`score_blocks`.
+    ``weights``: per block the weight of every PHYSICAL row (:func:`area_weights`; None: 1), repeated for every
+    delay like ``means``.  A row with weight 0 is left out, whatever it holds -- the NaN a ``_FillValue`` became,
+    the land points of a sea-surface field.  A negative or non-finite weight is a ValueError before any launch.
+    ``clims``: per block the climatology of every physical row (None: the mean, and 0 without one); anomalies are
+    taken against it.  With ``clims`` = the initial analysis the anomaly ``x - clim`` is the error of the
+    persistence forecast: ``sqrt(S4 / W)`` is its RMSE and ``skill_vs_clim`` = 1 - S0 / S4 the skill against it.
+    ``groups``: per block an integer label vector (0 .. G - 1) over the physical rows -- one variable at one level
+    is one group.  The labels need not be sorted; a group may come in several runs and may be absent from a block
+    or a rank (every run is one launch on a row range).  None: one group.  ``n_groups``: G, for ranks that do not
+    see the largest label (all ranks must agree); by default the largest local label + 1.
+
+    With e = forecast - analysis, f = forecast - clim, a = analysis - clim, the sums S0 .. S5 = sum w (e^2, e, a,
+    f^2, a^2, f a) over the rows of a group and W = the sum of its weights, returns per group and snapshot (G, T)
+      ``rmse`` = sqrt(S0 / W), ``bias`` = S1 / W, ``acc`` = S5 / sqrt(S3 S4), ``activity`` = sqrt(S3 / S4),
+      ``acc_centred`` = (S5 - Sf S2 / W) / sqrt((S3 - Sf^2 / W) (S4 - S2^2 / W)) with Sf = S1 + S2 (the weighted
+      means of f and a removed), ``skill_vs_clim`` = 1 - S0 / S4,
+    the same over all snapshots as ``*_total`` (G,), the raw ``sums`` (G, 6, T), ``weight`` (G,) (W: the fp64 sum
+    of the weights that are not 0, times the delay), ``rows`` and ``masked_rows`` (G,) (rows of the embedding, as
+    :func:`score_blocks` counts them), and with ``want_rows`` the lists ``row_rmse``, ``row_bias``, ``row_acc`` of
+    per-row vectors of the local blocks: the scores over time of every grid point (unweighted: a weight per row
+    cancels).
+
+    Row shards: ONE ``comm.allreduce_sum_`` of the stacked ``[sums, W, rows, masked]`` per call, whatever the
+    number of local blocks and groups.  A rank without blocks still takes part."""
+    kern = _kern(kern)
+    comm = comm or Comm()
+    T = int(Ct.shape[0])
+    if weights is not None:
+        weights = list(weights)
+        for b, v in enumerate(weights):
+            x = torch.as_tensor(v).to(torch.float64)
+            bad = int((~torch.isfinite(x) | (x < 0)).sum())
+            if bad:
+                raise ValueError(f"verify_blocks: {bad} weights of block {b} are negative or not finite (a row is left "
+                                 "out with the weight 0)")
+    runs = None
+    if groups is not None:
+        runs = [_runs(g) for g in groups]
+        labels = [g for r in runs for _, _, g in r]
+        if labels and min(labels) < 0:
+            raise ValueError("verify_blocks: group labels must be >= 0")
+        G = max(labels) + 1 if labels else 1
+        if n_groups is not None:
+            if G > n_groups and labels:
+                raise ValueError(f"verify_blocks: label {G - 1} with n_groups = {n_groups}")
+            G = int(n_groups)
+    else:
+        G = 1 if n_groups is None else int(n_groups)
+    Cp = _pitched(kern, Ct)
+    acc, meta, row_sums = None, torch.zeros((3, G), dtype=torch.float64), []
+    for b, (U, X) in enumerate(zip(Ublocks, Xblocks, strict=True)):   # (a streamed X that ends early is an error)
+        E = embed_view(X, delay)
+        if E.shape != (T, U.shape[1]) or U.shape[1] % delay:
+            raise ValueError(f"verify_blocks: block {b} of X is {tuple(E.shape)} (delay {delay}), U and Ct ask for "
+                             f"{(T, int(U.shape[1]))}")
+        mb = int(U.shape[1]) // delay
+        if acc is None:
+            acc = torch.zeros((G, 6, T), dtype=torch.float64, device=U.device)
+        mean, std, w, clim = (_vec(v, b, delay, U.device) for v in (means, stds, weights, clims))
+        for name, v in (("means", mean), ("stds", std), ("weights", w), ("clims", clim)):
+            if v is not None and v.numel() != delay * mb:
+                raise ValueError(f"verify_blocks: {name}[{b}] has {v.numel() // delay} entries, the block {mb} rows")
+        if runs is None:
+            pieces = [(0, delay * mb, 0)]
+        else:
+            if sum(e - s for s, e, _ in runs[b]) != mb:
+                raise ValueError(f"verify_blocks: groups[{b}] has {sum(e - s for s, e, _ in runs[b])} labels, the block "
+                                 f"{mb} rows")
+            pieces = [(j * mb + s, j * mb + e, g) for s, e, g in runs[b] for j in range(delay)]
+        wcpu = None if w is None else w[:mb].to(device="cpu", dtype=torch.float64)
+        for s, e, g in ([(0, mb, 0)] if runs is None else runs[b]):
+            ww = None if wcpu is None else wcpu[s:e]
+            meta[0, g] += delay * (float(e - s) if ww is None else float(ww.sum()))
+            meta[1, g] += delay * (e - s)
+            meta[2, g] += 0 if ww is None else delay * int((ww == 0).sum())
+        R = torch.zeros((6, delay * mb), dtype=torch.float64, device=U.device) if want_rows else None
+        for s, e, g in pieces:
+            cut = (lambda v: None if v is None else v[s:e])
+            _, r = _verify(kern, U[:, s:e], Cp, E[:, s:e], cut(mean), cut(std), cut(w), cut(clim), acc[g], want_rows)
+            if want_rows:
+                R[:, s:e] = r
+        if want_rows:
+            row_sums.append(R)
+    if acc is None:        # a rank without blocks still takes part in the collective
+        acc = torch.zeros((G, 6, T), dtype=torch.float64, device=Ct.device)
+    flat = torch.cat([acc.reshape(-1), meta.reshape(-1).to(acc.device)])
+    flat = comm.allreduce_sum_(flat, tag="verify_allreduce")
+    sums = flat[:G * 6 * T].reshape(G, 6, T)
+    W, rows, masked = flat[G * 6 * T:].reshape(3, G)
+
+    def scores(S, Wn):
+        S0, S1, S2, S3, S4, S5 = (S[:, q] for q in range(6))
+        Sf = S1 + S2
+        return {"rmse": torch.sqrt(S0 / Wn), "bias": S1 / Wn, "acc": S5 / torch.sqrt(S3 * S4),
+                "acc_centred": (S5 - Sf * S2 / Wn) / torch.sqrt((S3 - Sf * Sf / Wn) * (S4 - S2 * S2 / Wn)),
+                "activity": torch.sqrt(S3 / S4), "skill_vs_clim": 1.0 - S0 / S4}
+
+    res = scores(sums, W[:, None])
+    res.update({f"{key}_total": v for key, v in scores(sums.sum(dim=2), W * T).items()})
+    res.update(sums=sums, weight=W, rows=rows.to(torch.int64), masked_rows=masked.to(torch.int64))
+    if want_rows:
+        res["row_rmse"] = [torch.sqrt(R[0] / T) for R in row_sums]
+        res["row_bias"] = [R[1] / T for R in row_sums]
+        res["row_acc"] = [R[5] / torch.sqrt(R[3] * R[4]) for R in row_sums]
+    return res
+
+
 def project_blocks(Ublocks, Xblocks, means=None, stds=None, delay: int = 1, comm: Comm | None = None, kern=None,
                    shape: tuple[int, int] | None = None) -> dict:
     """The coefficients of raw snapshots in the basis U: ``c_t = U^T ((x_t - mean) / std)``, X read once and
@@ -466,6 +626,21 @@ class DmdForecast:
         delay d the blocks hold len(t) + d - 1 snapshots); ``imag_ratio`` is added to the result."""
         Ct, imag = self.coefficients(t)
         res = score_blocks(self.Ublocks, Ct, Xblocks, self.means, self.stds, self.delay, comm, want_rows, self.kern)
+        res["imag_ratio"] = imag
+        return res
+
+    def verify(self, Xblocks, t, weights=None, clims=None, groups=None, comm: Comm | None = None,
+               want_rows: bool = False, ensemble: bool = False, n_groups: int | None = None) -> dict:
+        """:func:`verify_blocks` of the model at the times ``t`` against the snapshots ``Xblocks`` (with a delay d
+        the blocks hold len(t) + d - 1 snapshots): weighted RMSE, bias and anomaly correlation per group.
+        ``ensemble=True`` verifies the ensemble mean of a bagged fit (``Cbar`` of :meth:`ensemble_coefficients`).
+        ``imag_ratio`` is added to the result."""
+        if ensemble:
+            Ct, _, imag = self.ensemble_coefficients(t)
+        else:
+            Ct, imag = self.coefficients(t)
+        res = verify_blocks(self.Ublocks, Ct, Xblocks, self.means, self.stds, weights, clims, groups, self.delay, comm,
+                            want_rows, self.kern, n_groups)
         res["imag_ratio"] = imag
         return res
 

@@ -318,6 +318,45 @@ class HipKernels:
         _lib.check(rc, "dmdx_expand_score_f32")
         return cols, rows
 
+    # -- K16 ----------------------------------------------------------------
+    @property
+    def verify_max_k(self) -> int:
+        return int(self._lib.dmdx_verify_max_k())
+
+    def verify(self, Ut: torch.Tensor, Ct: torch.Tensor, Xt: torch.Tensor, mean: torch.Tensor | None = None,
+               std: torch.Tensor | None = None, weight: torch.Tensor | None = None, clim: torch.Tensor | None = None,
+               out: torch.Tensor | None = None, want_rows: bool = False):
+        """The six weighted sums behind RMSE, bias and ACC of Xhat = mean + std * (U C) against X and a
+        climatology, Xhat never stored.  Ut: (k, m), Ct: (T, k), Xt: (T, m) fp32 (the delay view included),
+        mean / std / weight / clim: (m,) fp32 or None (0 / 1 / 1 / mean) -> (cols, rows): ``cols`` a (6, T) fp64
+        tensor of sum_i w (e^2, e, a, f^2, a^2, f a) with e = Xhat - X, f = Xhat - clim, a = X - clim over the
+        rows with w != 0 (a row with weight 0 is left out whatever it holds); ``rows`` the (6, m) fp64 sums of
+        the same quantities over t, unweighted, or None.
+
+        ``out``: a contiguous (6, T) fp64 tensor the column sums are ADDED to (row blocks, groups of rows)."""
+        m, k, ldu, T, Ct, ldc = self._expand_args(Ut, Ct, mean, std, "verify")
+        mx, Tx, ldx = _check_mat(Xt, torch.float32, "verify X")
+        if (mx, Tx) != (m, T) or Xt.device != Ut.device:
+            raise _lib.DmdxError(f"verify: X must be ({T}, {m}) on {Ut.device}, got {tuple(Xt.shape)}")
+        for v, name in ((weight, "weight"), (clim, "clim")):
+            if v is not None and (v.dtype != torch.float32 or v.shape != (m,) or v.device != Ut.device
+                                  or not v.is_contiguous()):
+                raise _lib.DmdxError(f"verify: {name} must be a contiguous fp32 vector of length {m} on {Ut.device}")
+        if out is not None:
+            if out.shape != (6, T) or out.dtype != torch.float64 or not out.is_contiguous() or out.device != Ut.device:
+                raise _lib.DmdxError(f"verify: out must be a contiguous (6, {T}) fp64 tensor on {Ut.device}")
+            cols = out
+        else:
+            cols = torch.empty((6, T), dtype=torch.float64, device=Ut.device)
+        rows = torch.empty((6, m), dtype=torch.float64, device=Ut.device) if want_rows else None
+        ws = self._workspace(Ut.device, self._lib.dmdx_verify_workspace_bytes(m, k, T))
+        rc = self._timed("verify", (m, k, T), lambda: self._lib.dmdx_verify_f32(
+            _ptr(Ut), m, k, ldu, _ptr(Ct), ldc, T, _ptr(mean), _ptr(std), _ptr(Xt), ldx, _ptr(weight), _ptr(clim),
+            _ptr(cols), T, _ptr(rows), m, int(out is not None), _ptr(ws), ws.numel(), self._stream()
+        ))
+        _lib.check(rc, "dmdx_verify_f32")
+        return cols, rows
+
     # -- K15 ----------------------------------------------------------------
     @property
     def spread_max_k(self) -> int:

@@ -384,6 +384,49 @@ int dmdx_spread_score_f32(const float* U, int64_t m, int64_t k, int64_t ldu, con
                           const float* sigma, double* var_col, double* var_row, int accumulate,
                           void* workspace, size_t workspace_bytes, void* stream);
 
+/* ---- K16: area-weighted verification of Xhat = mu + sigma .* (U C) on the grid --------------------------------
+ * What a forecast of ERA5 fields is judged by: the root-mean-square error, the bias and the anomaly correlation
+ * against a climatology, weighted by the area of the grid cells (cos(latitude) on the regular grid of
+ * era5_svd.py:132), per variable and level.  The operands are K12's -- U (m x k, ldu), C (k x T, ldc), mu / sigma
+ * (m floats each, nullable: 0 / 1), X (m x T, ldx; rows > ldx allowed, the zero-copy delay view) -- and two more:
+ * w (m floats, nullable: 1) the weight of every row, clim (m floats, nullable: mu, and 0 if that is NULL too) the
+ * climatology.  1 <= k <= dmdx_verify_max_k() (256: whatever K12 can expand can be verified).  Per element, fp32:
+ *   xhat = sigma * acc + mu       K12's chain over k (padded with zeros on both sides) and K12's two-step epilogue
+ *   e = fl(xhat - x)   f = fl(xhat - clim[i])   a = fl(x - clim[i])
+ * and the DMDX_VERIFY_NQ = 6 quantities   0: e^2   1: e   2: a   3: f^2   4: a^2   5: f a   (each rounded once):
+ *   col[q * ldcol + t] (+)= sum over the rows i with w[i] != 0 of fl(w[i] * quantity_q[i, t])    ldcol >= T
+ *   row[q * ldrow + i]  =  sum_t quantity_q[i, t]       nullable, ldrow >= m, unweighted, always overwritten
+ * With w == NULL there is no multiply.  RMSE^2 = col0 / W, bias = col1 / W, ACC = col5 / sqrt(col3 col4), the centred
+ * ACC needs col1 + col2 and col2 as well, W = sum of the weights (the host's); with clim = the initial analysis
+ * col4 / W is the squared error of persistence.  The weight is per row, so the host applies it to `row`.
+ * A row with w[i] == 0 is SELECTED out of the column sums, not multiplied in: whatever X, U, mu, sigma or clim hold
+ * in that row (NaN, Inf: the fill values of K14, a land / sea mask), no column sum changes by a bit; its `row` sums
+ * are still the plain sums.  With every w == 0 the column sums are +0.0.
+ * accumulate != 0 adds to col (X and U given as row blocks; a group of rows -- one variable at one level -- is a
+ * pointer offset, the kernel knows no groups); otherwise every logical element of col is written and none read.
+ * Sums as K12's score: fp32 over at most DMDX_VERIFY_FP32_ROWS rows (columns: the rows of one workgroup; rows: 16
+ * snapshots), fp64 beyond, through per-workgroup partial slots in the workspace and reduce kernels: no atomics, the
+ * order of every sum depends on (m, T) only, results are bit-wise reproducible.  The row blocks, the T split and
+ * the order of the sums are K12's: with w == NULL and clim == NULL, col[0] and col[4] are bit for bit sse_col and
+ * ref_col of dmdx_expand_score_f32 on the same operands, and row[0] is its sse_row.
+ * Values: a non-finite X[i, t] with w[i] != 0 makes column t of the sums it enters non-finite and row i of `row`; a
+ * non-finite U[i, j], mu[i], sigma[i] or clim[i] row i and, if w[i] != 0, every column of the sums it enters;
+ * everything else keeps its bits.  Integer U, C, mu, sigma, X, clim with w a power of two and partial sums below
+ * 2^24 give the integer results exactly; (2^e U, 2^-e C) changes no bit, 2^e w scales the column sums by 2^e.
+ * Memory as for K12: only logical elements are read, only logical elements of col / row are written, nothing is
+ * written behind the workspace, no alignment is required.  m, T and the leading dimensions must be < 2^31.  A
+ * refused call (DMDX_E_INVALID: a null U, C, X or col, k outside 1 .. 256, ldu < m, ldc < k, ldx < 1, ldcol < T,
+ * ldrow < m with row given, a size >= 2^31; DMDX_E_WORKSPACE: a null or short workspace) has written nothing. */
+#define DMDX_VERIFY_NQ 6
+#define DMDX_VERIFY_FP32_ROWS 128
+int dmdx_verify_max_k(void);
+size_t dmdx_verify_workspace_bytes(int64_t m, int64_t k, int64_t T);
+int dmdx_verify_f32(const float* U, int64_t m, int64_t k, int64_t ldu, const float* C, int64_t ldc, int64_t T,
+                    const float* mu, const float* sigma, const float* X, int64_t ldx,
+                    const float* w, const float* clim, double* col, int64_t ldcol,
+                    double* row, int64_t ldrow, int accumulate,
+                    void* workspace, size_t workspace_bytes, void* stream);
+
 /* ---- K14: CF-packed int16 codes -> fp32 snapshots of one row block ---------------------------------------------
  * What xr.open_dataset's mask_and_scale decoding (reference era5_svd.py:132 through retrieve_era5_slice) does to a
  * variable stored as int16 with scale_factor / add_offset / _FillValue / missing_value, done in HBM so that the
