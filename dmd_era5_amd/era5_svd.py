@@ -57,6 +57,7 @@ __all__ = [
     "main",
     "reconstruct_from_svd_results",
     "project_onto_svd_results",
+    "write_forecast_slice",
 ]
 
 logger = setup_logger("ERA5-SVD", "era5_svd.log")
@@ -257,6 +258,149 @@ def reconstruct_from_svd_results(svd_ds: Dataset, n_components: int | None = Non
         tc = svd_ds.coords["time"]
         row["time"] = Coord("time", np.asarray(tc.values)[tidx])
     return DataArray(X, ("space", "time"), row)
+
+
+# pinned staging of write_forecast_slice: the codes of one time slab of all variables (2 bytes per value)
+FORECAST_STAGE_BYTES = 256 << 20
+
+
+def write_forecast_slice(path: str, forecast, t, time, variables, levels, latitude, longitude, *, packing=None,
+                         ensemble: bool = False, spread: bool = False, slab: int | None = None,
+                         attrs: dict | None = None) -> dict:
+    """The fields of a :class:`forecast.DmdForecast` at the model times ``t`` as a NETCDF4 file in the schema of the
+    input slice: one ``int16`` variable ``(time, level, latitude, longitude)`` per name with ``scale_factor``,
+    ``add_offset`` (float64) and ``_FillValue`` (int16 -32768), the coordinate variables, and the global attributes
+    ``retrieve_era5_slice`` keys on -- the file is a valid input slice of :func:`main`.  The codes are formed on the
+    device where the field is formed (K17): no fp32 field is stored, and 2 bytes per value cross PCIe and reach the
+    file.
+
+    ``time``: the time coordinate of the file, one entry per entry of ``t`` (datetime64, or numbers stored as they
+    are).  ``variables`` / ``levels`` / ``latitude`` / ``longitude``: the names and coordinates of the grid; the rows
+    of the forecast's U blocks (together) follow ``flatten_era5_variables``' order -- variable, then level, latitude,
+    longitude -- and one variable is one group: one ``scale_factor`` per file variable.  A forecast whose U blocks
+    are delay-embedded writes delay block 0, the physical fields.
+    ``packing``: None chooses ``Packing.for_range`` of every variable's finite values over ALL of ``t`` in a range
+    pass of its own, which forms coefficients and partial extrema only; a dict name -> Packing (or a list in the
+    order of ``variables``) is taken as it is -- the analysis file's own packing: one pass, comparable codes.
+    ``ensemble=True`` writes the ensemble mean of a bagged fit, ``spread=True`` adds the K15 spread of the same
+    times as ``<name>_spread`` variables (always packed by their own range).
+    ``slab``: snapshots per slab of the walk along the time axis -- expand_pack into a device int16 slab, one
+    device-to-host copy of the codes, ``Writer.write_slab``; by default what fits ``FORECAST_STAGE_BYTES`` of
+    (pinned) staging.  ``attrs``: more global attributes (``source_path`` among them, if ``main`` is to accept the
+    file for a configuration).
+
+    Returns ``{"packing": {name: Packing}, "filled": {name: int}, "saturated": {name: int}}`` over the file's
+    variables: the values that were not finite and became ``_FillValue``, and those a given packing clamped."""
+    import torch
+
+    from . import forecast as fc
+    from . import hdf5_lite
+    from .labeled import Packing
+
+    if not hdf5_lite.available():
+        raise RuntimeError("write_forecast_slice writes NETCDF4 / HDF5 and libhdf5 was not found (set DMDX_HDF5_LIB)")
+    if spread and not ensemble:
+        raise ValueError("write_forecast_slice: spread=True needs ensemble=True")
+    variables = _as_str_list(variables)
+    levels, lat, lon = np.atleast_1d(np.asarray(levels)), np.atleast_1d(np.asarray(latitude)), np.atleast_1d(np.asarray(longitude))
+    time = np.atleast_1d(np.asarray(time))
+    tt = torch.as_tensor(t, dtype=torch.float64).reshape(-1)
+    T, plane = int(tt.numel()), int(levels.size * lat.size * lon.size)
+    if time.shape != (T,):
+        raise ValueError(f"write_forecast_slice: {time.shape[0] if time.ndim == 1 else time.shape} time labels for {T} times")
+    nvar, d = len(variables), int(forecast.delay)
+    Ub = list(forecast.Ublocks)
+    rows = [int(U.shape[1]) // d for U in Ub]
+    M = sum(rows)
+    if M != nvar * plane or any(int(U.shape[1]) % d for U in Ub):
+        raise ValueError(f"write_forecast_slice: the U blocks hold {M} physical rows, {nvar} variables x "
+                         f"{levels.size} levels x {lat.size} x {lon.size} points are {nvar * plane}")
+    starts = np.concatenate([[0], np.cumsum(rows)]).astype(np.int64)
+    groups = [torch.from_numpy(np.arange(a, b, dtype=np.int64) // plane) for a, b in zip(starts[:-1], starts[1:])]
+    if isinstance(packing, dict):
+        packing = [packing[v] for v in variables]
+    if ensemble:
+        Ct, Dev, _ = forecast.ensemble_coefficients(tt)
+    else:
+        (Ct, _), Dev = forecast.coefficients(tt), None
+    dev = Ub[0].device
+    kern, dblock = forecast.kern, (0 if d > 1 else None)
+    if slab is None:
+        slab = max(1, min(T, FORECAST_STAGE_BYTES // (2 * M * (2 if spread else 1))))
+    slab = int(slab)
+    if slab < 1:
+        raise ValueError("write_forecast_slice: slab >= 1")
+
+    def spread_of(t0, t1):
+        return fc.spread_blocks(Ub, Dev[:, t0:t1], forecast.stds, dblock, delay=d, kern=kern)
+
+    # the packings: the range pass stores coefficients and extrema only (the spread is a field: slab by slab)
+    if packing is None:
+        state = fc.range_blocks(Ub, Ct, forecast.means, forecast.stds, groups, dblock, d, kern, nvar)
+        packing = [Packing.for_range(lo, hi) for lo, hi in state[0].cpu().tolist()]
+    else:
+        packing = fc._packings(packing, nvar, "write_forecast_slice")
+    spacking = None
+    if spread:
+        state = None
+        for t0 in range(0, T, slab):
+            state = fc.range_field_blocks(spread_of(t0, min(T, t0 + slab)), groups, kern, nvar, state)
+        spacking = [Packing.for_range(lo, hi) for lo, hi in state[0].cpu().tolist()]
+
+    names = [(v, packing[g], False) for g, v in enumerate(variables)]
+    if spread:
+        names += [(f"{v}_spread", spacking[g], True) for g, v in enumerate(variables)]
+    os.makedirs(os.path.dirname(os.path.abspath(path)), exist_ok=True)
+    dims = ("time", "level", "latitude", "longitude")
+    shape = (T, int(levels.size), int(lat.size), int(lon.size))
+    gattrs = {"Conventions": "CF-1.6", "source_path": "dmd_era5_amd forecast", "variables": list(variables),
+              "levels": [int(x) for x in levels.tolist()], "date_downloaded": datetime.now().isoformat(),
+              "forecast_rank": int(Ub[0].shape[0]), "forecast_delay": d}
+    with hdf5_lite.Writer(path) as w:
+        if np.issubdtype(time.dtype, np.datetime64):
+            w.dataset("time", np.round(io_netcdf._encode_time(time)).astype(np.int64), ("time",),
+                      {"units": io_netcdf.TIME_UNITS, "calendar": "proleptic_gregorian"})
+            gattrs["start_datetime"], gattrs["end_datetime"] = (str(x.astype("datetime64[s]")) for x in (time[0], time[-1]))
+            if T > 1:
+                gattrs["hours_delta_time"] = float((time[1] - time[0]) / np.timedelta64(1, "h"))
+        else:
+            w.dataset("time", time, ("time",))
+        for name, vals in (("level", levels), ("latitude", lat), ("longitude", lon)):
+            w.dataset(name, vals, (name,))
+        for name, pk, _ in names:
+            w.create(name, shape, np.int16, dims, {"scale_factor": np.float64(pk.scale_factor),
+                                                   "add_offset": np.float64(pk.add_offset),
+                                                   "_FillValue": np.int16(Packing.FILL_I16)})
+        gattrs.update(attrs or {})
+        w.attrs(None, gattrs)
+
+        nfield = 2 if spread else 1
+        dslab = torch.empty((nfield, slab, M), dtype=torch.int16, device=dev)
+        stage = torch.empty((nfield, slab, M), dtype=torch.int16, pin_memory=(dev.type == "cuda"))
+        counts, scounts = None, None
+        for t0 in range(0, T, slab):
+            t1 = min(T, t0 + slab)
+            n = t1 - t0
+            out = [dslab[0, :n, a:b] for a, b in zip(starts[:-1], starts[1:])]
+            counts = fc.pack_blocks(Ub, Ct[t0:t1], forecast.means, forecast.stds, groups, packing, dblock, d, out, kern,
+                                    nvar, counts=counts)["counts"]
+            if spread:
+                out = [dslab[1, :n, a:b] for a, b in zip(starts[:-1], starts[1:])]
+                scounts = fc.pack_field_blocks(spread_of(t0, t1), groups, spacking, out, kern, nvar, scounts)["counts"]
+            stage[:, :n].copy_(dslab[:, :n])                   # the one device-to-host copy of the slab: the codes
+            host = stage.numpy()
+            for i, (name, _, is_spread) in enumerate(names):
+                g = i % nvar
+                w.write_slab(name, t0, host[int(is_spread), :n, g * plane:(g + 1) * plane].reshape((n,) + shape[1:]))
+    res = {"packing": {}, "filled": {}, "saturated": {}}
+    for c, sel in ((counts, False), (scounts, True)):
+        if c is None:
+            continue
+        c = c.cpu().tolist()
+        for i, (name, pk, is_spread) in enumerate(names):
+            if is_spread == sel:
+                res["packing"][name], res["filled"][name], res["saturated"][name] = pk, int(c[i % nvar][0]), int(c[i % nvar][1])
+    return res
 
 
 def project_onto_svd_results(svd_ds: Dataset, X, n_components: int | None = None, mean=None, std=None,

@@ -19,7 +19,11 @@ coefficients and the scaled member deviations, K12 expands the mean and K15 (``H
 without storing a member field; ``DmdForecast.ensemble_score`` sets that spread against the error the mean makes.
 What a forecast of gridded fields is published with -- RMSE, bias and anomaly correlation, weighted by the area of
 the grid cells, per variable and level, with masked points left out -- is K16 (``HipKernels.verify``,
-csrc/verify.hip): :func:`area_weights`, :func:`verify_blocks` and ``DmdForecast.verify``.
+csrc/verify.hip): :func:`area_weights`, :func:`verify_blocks` and ``DmdForecast.verify``.  And the way out of the
+package: K17 (``HipKernels.expand_range`` / ``expand_pack`` / ``field_range`` / ``pack``, csrc/pack.hip) turns the
+forecast into the CF-packed int16 codes an ERA5 file stores, one ``scale_factor`` / ``add_offset`` per group of rows (a
+variable), where the field is formed and without storing it in fp32: :func:`pack_blocks`, :func:`pack_field_blocks` and
+``DmdForecast.pack``; ``era5_svd.write_forecast_slice`` writes them.
 
 Layout as everywhere in the package (kernels.py): a column-major matrix is held as its row-major
 transpose -- U blocks are ``(k, rows)`` (``SvdResult.Ut``), coefficients ``Ct`` are ``(T, k)``,
@@ -36,11 +40,12 @@ from dataclasses import dataclass
 import torch
 
 from .bopdmd import OptDMDResult, _phi
+from .labeled import Packing
 from .svd import Comm, _kern, _pitched, embed_view
 
 __all__ = ["svd_coefficients", "dmd_coefficients", "ensemble_coefficients", "expand_blocks", "iter_fields",
            "score_blocks", "project_blocks", "spread_blocks", "spread_score_blocks", "area_weights", "verify_blocks",
-           "DmdForecast"]
+           "pack_blocks", "pack_field_blocks", "range_blocks", "range_field_blocks", "DmdForecast"]
 
 
 # ---------------------------------------------------------------------------
@@ -157,6 +162,58 @@ def _verify(kern, Ut, Ct, Xt, mean, std, weight, clim, out, want_rows):
         out += cols
         cols = out
     return cols, (Q.sum(dim=1) if want_rows else None)
+
+
+def _merge_range(P: torch.Tensor, out):
+    """(range (2,) fp32, count (1,) int64) of the fp32 field P, merged into the pair ``out`` of an earlier call."""
+    fin = torch.isfinite(P)
+    inf = torch.tensor(float("inf"), dtype=torch.float32, device=P.device)
+    mn = torch.where(fin, P, inf).amin() if P.numel() else inf
+    mx = torch.where(fin, P, -inf).amax() if P.numel() else -inf
+    cnt = (~fin).sum().reshape(1)
+    if out is None:
+        return torch.stack([mn, mx]), cnt
+    rng, c = out
+    rng[0], rng[1] = torch.minimum(rng[0], mn), torch.maximum(rng[1], mx)
+    c += cnt
+    return rng, c
+
+
+def _encode_host(P: torch.Tensor, packing: Packing, out, counts):
+    q, filled, saturated = packing.encode(P.detach().cpu().numpy(), counts=True)
+    Q = torch.from_numpy(q).to(P.device)
+    if out is not None:
+        out.copy_(Q)
+        Q = out
+    add = torch.tensor([filled, saturated], dtype=torch.int64, device=P.device)
+    if counts is None:
+        return Q, add
+    counts += add
+    return Q, counts
+
+
+def _expand_range(kern, Ut, Ct, mean, std, out):
+    f = getattr(kern, "expand_range", None)
+    if f is not None:
+        return f(Ut, Ct, mean, std, out=out)
+    return _merge_range(_expand(kern, Ut, Ct, mean, std), out)
+
+
+def _expand_pack(kern, Ut, Ct, mean, std, packing, out, counts):
+    f = getattr(kern, "expand_pack", None)
+    if f is not None:
+        return f(Ut, Ct, mean, std, packing, out=out, counts=counts)
+    return _encode_host(_expand(kern, Ut, Ct, mean, std), packing, out, counts)
+
+
+def _field_range(kern, Xt, out):
+    f = getattr(kern, "field_range", None)
+    return f(Xt, out=out) if f is not None else _merge_range(Xt, out)
+
+
+def _field_pack(kern, Xt, packing, out, counts):
+    f = getattr(kern, "pack", None)
+    return f(Xt, packing, out=out, counts=counts) if f is not None else _encode_host(Xt, packing, out, counts)
 
 
 def _project(kern, Ut, Xt, mean, std, out, want_energy=True):
@@ -528,6 +585,173 @@ def verify_blocks(Ublocks, Ct: torch.Tensor, Xblocks, means=None, stds=None, wei
     return res
 
 
+def _group_pieces(groups, rows, reps, n_groups, who):
+    """-> (pieces, G): per block the list of (first row, one past the last row, group) of its launches.  ``rows``:
+    the physical rows of every block, each label vector repeated for the ``reps`` delays of its block."""
+    if groups is None:
+        return [[(0, r * j, 0)] for r, j in zip(rows, reps)], (1 if n_groups is None else int(n_groups))
+    runs = [_runs(g) for g in groups]
+    if len(runs) != len(rows):
+        raise ValueError(f"{who}: {len(runs)} label vectors for {len(rows)} blocks")
+    labels = [g for r in runs for _, _, g in r]
+    if labels and min(labels) < 0:
+        raise ValueError(f"{who}: group labels must be >= 0")
+    G = max(labels) + 1 if labels else 1
+    if n_groups is not None:
+        if G > n_groups and labels:
+            raise ValueError(f"{who}: label {G - 1} with n_groups = {n_groups}")
+        G = int(n_groups)
+    for b, (r, mb) in enumerate(zip(runs, rows)):
+        if sum(e - s for s, e, _ in r) != mb:
+            raise ValueError(f"{who}: groups[{b}] has {sum(e - s for s, e, _ in r)} labels, the block {mb} rows")
+    return [[(j * mb + s, j * mb + e, g) for s, e, g in r for j in range(reps_b)]
+            for r, mb, reps_b in zip(runs, rows, reps)], G
+
+
+def _range_pieces(pieces, G, device, range_fn, state=None):
+    """The range pass over the launches ``pieces``, merged into ``state`` = (range (G, 2) fp32, count (G, 1) int64)
+    device tensors of an earlier pass (time slabs); nothing is synchronised."""
+    if state is None:
+        state = (torch.tensor([[float("inf"), float("-inf")]] * G, dtype=torch.float32, device=device),
+                 torch.zeros((G, 1), dtype=torch.int64, device=device))
+    rng, cnt = state
+    for b, ps in enumerate(pieces):
+        for s, e, g in ps:
+            range_fn(b, s, e, (rng[g], cnt[g]))
+    return state
+
+
+def _packings(packing, G, who):
+    if isinstance(packing, Packing):
+        return [packing] * G
+    packing = list(packing)
+    if len(packing) != G or not all(isinstance(p, Packing) for p in packing):
+        raise ValueError(f"{who}: {len(packing)} packings for {G} groups (a Packing, or a list of one per group)")
+    return packing
+
+
+def _pack_pieces(pieces, G, shapes, device, packing, out, range_fn, pack_fn, who, counts=None):
+    """The two passes of :func:`pack_blocks` / :func:`pack_field_blocks` over the launches ``pieces``.  ``counts``: a
+    (G, 2) int64 device tensor of an earlier call to add to (time slabs); the result then holds its running sums."""
+    rng = None
+    if packing is None:
+        rng = _range_pieces(pieces, G, device, range_fn)[0].cpu()      # the one synchronisation of the range pass
+        packing = [Packing.for_range(lo, hi) for lo, hi in rng.tolist()]
+    else:
+        packing = _packings(packing, G, who)
+    if out is not None:
+        out = list(out)
+        for b, shp in enumerate(shapes):
+            if tuple(out[b].shape) != shp or out[b].dtype != torch.int16:
+                raise ValueError(f"{who}: out[{b}] must be a {shp} int16 tensor, got {out[b].dtype} {tuple(out[b].shape)}")
+    codes = out if out is not None else [torch.empty(shp, dtype=torch.int16, device=device) for shp in shapes]
+    if counts is None:
+        counts = torch.zeros((G, 2), dtype=torch.int64, device=device)
+    for b, ps in enumerate(pieces):
+        for s, e, g in ps:
+            pack_fn(b, s, e, packing[g], codes[b][:, s:e], counts[g])
+    host = counts.cpu()
+    return {"codes": codes, "packing": packing, "range": rng, "filled": host[:, 0].clone(),
+            "saturated": host[:, 1].clone(), "counts": counts}
+
+
+def _expand_setup(kern, Ublocks, Ct, means, stds, groups, delay_block, delay, n_groups, who):
+    views = [_block_rows(U, delay, delay_block) for U in Ublocks]
+    rows = [int(U.shape[1]) // reps for U, reps in views]
+    pieces, G = _group_pieces(groups, rows, [reps for _, reps in views], n_groups, who)
+    Cp = _pitched(kern, Ct)
+    vecs = [(_vec(means, b, reps, U.device), _vec(stds, b, reps, U.device)) for b, (U, reps) in enumerate(views)]
+    for b, ((U, _), (mean, std)) in enumerate(zip(views, vecs)):
+        for name, v in (("means", mean), ("stds", std)):
+            if v is not None and v.numel() != U.shape[1]:
+                raise ValueError(f"{who}: {name}[{b}] does not match the {int(U.shape[1])} rows of the block")
+    cut = (lambda v, s, e: None if v is None else v[s:e])
+    args = (lambda b, s, e: (views[b][0][:, s:e], Cp, cut(vecs[b][0], s, e), cut(vecs[b][1], s, e)))
+    return views, pieces, G, args
+
+
+def range_blocks(Ublocks, Ct: torch.Tensor, means=None, stds=None, groups=None, delay_block: int | None = 0,
+                 delay: int = 1, kern=None, n_groups: int | None = None, state=None):
+    """The range pass of :func:`pack_blocks` on its own: -> ``state`` = (range (G, 2) fp32, count (G, 1) int64) device
+    tensors -- minimum / maximum of the finite values of ``mean + std * (U c)`` and the number of non-finite ones
+    per group, no field stored -- merged into the ``state`` of an earlier call (chunks of the time axis).  Nothing is
+    synchronised; ``Packing.for_range(*state[0][g].tolist())`` is the packing of group g."""
+    kern = _kern(kern)
+    Ublocks = list(Ublocks)
+    _, pieces, G, args = _expand_setup(kern, Ublocks, Ct, means, stds, groups, delay_block, delay, n_groups, "range_blocks")
+    dev = Ublocks[0].device if Ublocks else Ct.device
+    return _range_pieces(pieces, G, dev, lambda b, s, e, o: _expand_range(kern, *args(b, s, e), o), state)
+
+
+def pack_blocks(Ublocks, Ct: torch.Tensor, means=None, stds=None, groups=None, packing=None,
+                delay_block: int | None = 0, delay: int = 1, out=None, kern=None, n_groups: int | None = None,
+                comm: Comm | None = None, counts=None) -> dict:
+    """The fields ``mean + std * (U c)`` of every row block as CF-packed int16 codes, one packing per group of rows,
+    the fp32 fields never stored (K17).
+
+    ``means``, ``stds``, ``delay``, ``delay_block`` as in :func:`expand_blocks` (``delay_block=0``, the default, packs
+    the physical fields).  ``groups`` as in :func:`verify_blocks`: per block an integer label vector over the
+    physical rows -- one variable of the file is one group; a group may come in several runs and may be absent
+    from a block (every run is one launch on a row range).  None: one group.  ``n_groups``: G.
+    ``packing``: None runs a range pass first (the coefficients are expanded twice, nothing is stored) and packs
+    group g with ``Packing.for_range`` of its finite values; a :class:`Packing` or a list of G of them is taken as
+    it is and the range pass is skipped -- the forecast written with the analysis file's own ``scale_factor`` /
+    ``add_offset``: one pass, directly comparable codes, and ``saturated`` says what did not fit.
+    ``out``: per block a (T, rows) int16 view to write into (any row stride: a time slab of a staging buffer).
+
+    Returns ``codes`` (per block a (T, rows) int16 device tensor, or the views of ``out``), ``packing`` (a list of
+    G), ``range`` ((G, 2) fp32 minimum / maximum of the finite values; None with a given packing), ``filled`` and
+    ``saturated`` ((G,) int64: the non-finite values, which became the fill code -32768, and the values the clamp
+    to -32767 .. 32767 caught) and ``counts`` (the (G, 2) int64 device tensor behind the two; handed back in as
+    ``counts=`` by a caller that walks the time axis in slabs, it keeps running sums).
+
+    Row shards: the range of a group is a minimum / maximum over all ranks and ``Comm`` has no such collective:
+    with a ``comm`` of more than one rank pass the ``packing``; ``filled`` / ``saturated`` are this rank's."""
+    kern = _kern(kern)
+    if comm is not None and comm.world_size > 1 and packing is None:
+        raise ValueError("pack_blocks: the range pass is single-process; with a comm of more than one rank pass the "
+                         "packing (a Packing per group)")
+    Ublocks = list(Ublocks)
+    T = int(Ct.shape[0])
+    views, pieces, G, args = _expand_setup(kern, Ublocks, Ct, means, stds, groups, delay_block, delay, n_groups,
+                                           "pack_blocks")
+    dev = Ublocks[0].device if Ublocks else Ct.device
+    shapes = [(T, int(U.shape[1])) for U, _ in views]
+    return _pack_pieces(pieces, G, shapes, dev, packing, out,
+                        lambda b, s, e, o: _expand_range(kern, *args(b, s, e), o),
+                        lambda b, s, e, pk, o, c: _expand_pack(kern, *args(b, s, e), pk, o, c), "pack_blocks", counts)
+
+
+def pack_field_blocks(Xblocks, groups=None, packing=None, out=None, kern=None, n_groups: int | None = None,
+                      counts=None) -> dict:
+    """:func:`pack_blocks` of fields that exist: ``Xblocks`` a list of (T, rows) fp32 tensors -- the K15 spread, an
+    ensemble mean, real snapshots.  ``groups``, ``packing``, ``out``, ``n_groups`` and the result as there."""
+    kern = _kern(kern)
+    Xblocks = list(Xblocks)
+    pieces, G = _group_pieces(groups, [int(X.shape[1]) for X in Xblocks], [1] * len(Xblocks), n_groups,
+                              "pack_field_blocks")
+
+    def range_fn(b, s, e, o):
+        _field_range(kern, Xblocks[b][:, s:e], o)
+
+    def pack_fn(b, s, e, pk, o, c):
+        _field_pack(kern, Xblocks[b][:, s:e], pk, o, c)
+
+    shapes = [tuple(int(n) for n in X.shape) for X in Xblocks]
+    dev = Xblocks[0].device if Xblocks else torch.device("cpu")
+    return _pack_pieces(pieces, G, shapes, dev, packing, out, range_fn, pack_fn, "pack_field_blocks", counts)
+
+
+def range_field_blocks(Xblocks, groups=None, kern=None, n_groups: int | None = None, state=None):
+    """:func:`range_blocks` of fields that exist (``Xblocks`` as in :func:`pack_field_blocks`)."""
+    kern = _kern(kern)
+    Xblocks = list(Xblocks)
+    pieces, G = _group_pieces(groups, [int(X.shape[1]) for X in Xblocks], [1] * len(Xblocks), n_groups,
+                              "range_field_blocks")
+    dev = Xblocks[0].device if Xblocks else torch.device("cpu")
+    return _range_pieces(pieces, G, dev, lambda b, s, e, o: _field_range(kern, Xblocks[b][:, s:e], o), state)
+
+
 def project_blocks(Ublocks, Xblocks, means=None, stds=None, delay: int = 1, comm: Comm | None = None, kern=None,
                    shape: tuple[int, int] | None = None) -> dict:
     """The coefficients of raw snapshots in the basis U: ``c_t = U^T ((x_t - mean) / std)``, X read once and
@@ -642,6 +866,34 @@ class DmdForecast:
         res = verify_blocks(self.Ublocks, Ct, Xblocks, self.means, self.stds, weights, clims, groups, self.delay, comm,
                             want_rows, self.kern, n_groups)
         res["imag_ratio"] = imag
+        return res
+
+    def pack(self, t, groups=None, packing=None, delay_block: int | None = 0, out=None, ensemble: bool = False,
+             spread: bool = False, spread_packing=None, spread_out=None, n_groups: int | None = None,
+             comm: Comm | None = None) -> dict:
+        """:func:`pack_blocks` of the model at the times ``t``: the fields as CF-packed int16 codes, one packing per
+        group, no fp32 field stored.  ``ensemble=True`` packs the ensemble mean of a bagged fit (``Cbar`` of
+        :meth:`ensemble_coefficients`); with ``spread=True`` the K15 spread of the same times is formed and packed too
+        (:func:`pack_field_blocks`, ``spread_packing`` / ``spread_out`` as ``packing`` / ``out``) and returned under
+        ``"spread"``.  ``imag_ratio`` is added to the result."""
+        if spread and not ensemble:
+            raise ValueError("DmdForecast.pack: spread=True needs ensemble=True")
+        if self.delay == 1:
+            delay_block = None
+        if ensemble:
+            Ct, Dev, imag = self.ensemble_coefficients(t)
+        else:
+            Ct, imag = self.coefficients(t)
+        res = pack_blocks(self.Ublocks, Ct, self.means, self.stds, groups, packing, delay_block, self.delay, out,
+                          self.kern, n_groups, comm)
+        res["imag_ratio"] = imag
+        if spread:
+            if comm is not None and comm.world_size > 1 and spread_packing is None:
+                raise ValueError("DmdForecast.pack: with a comm of more than one rank pass spread_packing")
+            S = spread_blocks(self.Ublocks, Dev, self.stds, delay_block, delay=self.delay, kern=self.kern)
+            if groups is not None and delay_block is None and self.delay > 1:
+                groups = [torch.as_tensor(g).reshape(-1).repeat(self.delay) for g in groups]
+            res["spread"] = pack_field_blocks(S, groups, spread_packing, spread_out, self.kern, n_groups)
         return res
 
     def ensemble_coefficients(self, t, ddof: int = 1) -> tuple[torch.Tensor, torch.Tensor, float]:

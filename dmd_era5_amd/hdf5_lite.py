@@ -218,7 +218,9 @@ def _host_lib():
 # ======================================================================================
 class Writer:
     """``with Writer(path) as w: w.dataset(name, array, dims); w.attrs(None, {...})``.
-    A dataset whose name equals its single dimension becomes that dimension's scale."""
+    A dataset whose name equals its single dimension becomes that dimension's scale.
+    ``w.create(name, shape, dtype, dims)`` makes a dataset without data and ``w.write_slab(name, start, array)``
+    fills it along its first axis, in any order: a variable that is produced slab by slab."""
 
     def __init__(self, path: str):
         self.lib, self.hl = _load()
@@ -227,6 +229,7 @@ class Writer:
             raise OSError(f"H5Fcreate failed for {path}")
         self._dsets: dict[str, int] = {}
         self._vardims: dict[str, tuple] = {}
+        self._slabbed: dict[str, tuple] = {}
         self._has_ncproperties = False
 
     def __enter__(self):
@@ -256,6 +259,50 @@ class Writer:
         self._vardims[name] = tuple(dims)
         if attrs:
             self.attrs(name, attrs)
+
+    def create(self, name: str, shape, dtype, dims: tuple, attrs: dict | None = None) -> None:
+        """A contiguous numeric dataset of the full ``shape`` whose data come later (:meth:`write_slab`); its space
+        in the file is allocated, whole, by the first slab that is written."""
+        lib = self.lib
+        shape = tuple(int(n) for n in shape)
+        if not shape or len(shape) != len(tuple(dims)) or min(shape) < 1:
+            raise ValueError(f"create {name}: shape {shape} with dims {tuple(dims)}")
+        tid = _h5type(lib, dtype)
+        sid = lib.H5Screate_simple(len(shape), _dims(*shape), None)
+        did = lib.H5Dcreate2(self.fid, name.encode(), tid, sid, _H5P_DEFAULT, _H5P_DEFAULT, _H5P_DEFAULT)
+        lib.H5Sclose(sid)
+        if did < 0:
+            raise OSError(f"H5Dcreate2 failed for {name}")
+        self._dsets[name] = did
+        self._vardims[name] = tuple(dims)
+        self._slabbed[name] = (shape, np.dtype(dtype))
+        if attrs:
+            self.attrs(name, attrs)
+
+    def write_slab(self, name: str, start: int, arr: np.ndarray) -> None:
+        """``arr`` into ``[start, start + len(arr))`` of the first axis of a dataset made by :meth:`create`."""
+        lib = self.lib
+        if name not in self._slabbed:
+            raise KeyError(f"write_slab: {name} was not made by create()")
+        shape, dtype = self._slabbed[name]
+        arr = np.asarray(arr)
+        if arr.dtype != dtype or arr.shape[1:] != shape[1:] or start < 0 or start + arr.shape[0] > shape[0]:
+            raise ValueError(f"write_slab {name}: {arr.dtype} {arr.shape} at {start} does not fit {dtype} {shape}")
+        if arr.shape[0] == 0:
+            return
+        arr = np.ascontiguousarray(arr)
+        did = self._dsets[name]
+        fsp = lib.H5Dget_space(did)
+        msp = lib.H5Screate_simple(arr.ndim, _dims(*arr.shape), None)
+        try:
+            if lib.H5Sselect_hyperslab(fsp, _H5S_SELECT_SET, _dims(int(start), *([0] * (arr.ndim - 1))), None,
+                                       _dims(*arr.shape), None) < 0:
+                raise OSError(f"H5Sselect_hyperslab failed for {name}")
+            if lib.H5Dwrite(did, _h5type(lib, dtype), msp, fsp, _H5P_DEFAULT, arr.ctypes.data_as(C.c_void_p)) < 0:
+                raise OSError(f"H5Dwrite failed for {name}")
+        finally:
+            lib.H5Sclose(msp)
+            lib.H5Sclose(fsp)
 
     def _vstr_dataset(self, name, arr, dims):
         lib = self.lib

@@ -517,6 +517,95 @@ class HipKernels:
         _lib.check(rc, "dmdx_unpack_i16_f32")
         return Xt
 
+    # -- K17 ----------------------------------------------------------------
+    @property
+    def pack_max_k(self) -> int:
+        return int(self._lib.dmdx_pack_max_k())
+
+    @staticmethod
+    def _range_out(out, device, who):
+        """-> (range (2,) fp32, count (1,) int64, accumulate) of a range call; ``out`` is the pair of an earlier one."""
+        if out is None:
+            return (torch.empty(2, dtype=torch.float32, device=device), torch.empty(1, dtype=torch.int64, device=device), 0)
+        rng, cnt = out
+        if (rng.shape != (2,) or rng.dtype != torch.float32 or not rng.is_contiguous() or rng.device != device
+                or cnt.shape != (1,) or cnt.dtype != torch.int64 or cnt.device != device):
+            raise _lib.DmdxError(f"{who}: out must be the pair ((2,) fp32, (1,) int64) on {device}")
+        return rng, cnt, 1
+
+    @staticmethod
+    def _pack_out(out, counts, m, T, device, who):
+        """-> (Qt (T, m) int16, ldq, counts (2,) int64) of a pack call; a given ``counts`` accumulates."""
+        if out is not None:
+            mo, To, ldq = _check_mat(out, torch.int16, f"{who} out")
+            if (mo, To) != (m, T) or out.device != device:
+                raise _lib.DmdxError(f"{who}: out must be ({T}, {m}) int16 on {device}, got {tuple(out.shape)}")
+            Qt = out
+        else:
+            Qt, ldq = torch.empty((T, m), dtype=torch.int16, device=device), m
+        if counts is None:
+            counts = torch.zeros(2, dtype=torch.int64, device=device)
+        elif counts.shape != (2,) or counts.dtype != torch.int64 or not counts.is_contiguous() or counts.device != device:
+            raise _lib.DmdxError(f"{who}: counts must be a contiguous (2,) int64 tensor on {device}")
+        return Qt, ldq, counts
+
+    def expand_range(self, Ut: torch.Tensor, Ct: torch.Tensor, mean: torch.Tensor | None = None,
+                     std: torch.Tensor | None = None, out=None):
+        """The range of Xhat = mean + std * (U C), Xhat never stored (operands as :meth:`expand`) -> (range, count):
+        ``range`` the (2,) fp32 minimum and maximum of the finite values -- exactly those of ``expand(...)``;
+        (+inf, -inf) without one -- and ``count`` the (1,) int64 number of non-finite ones.
+
+        ``out``: the pair of an earlier call, which this block is MERGED into (row blocks, the runs of a group)."""
+        m, k, ldu, T, Ct, ldc = self._expand_args(Ut, Ct, mean, std, "expand_range")
+        rng, cnt, acc = self._range_out(out, Ut.device, "expand_range")
+        ws = self._workspace(Ut.device, self._lib.dmdx_expand_range_workspace_bytes(m, k, T))
+        rc = self._timed("expand_range", (m, k, T), lambda: self._lib.dmdx_expand_range_f32(
+            _ptr(Ut), m, k, ldu, _ptr(Ct), ldc, T, _ptr(mean), _ptr(std), _ptr(rng), _ptr(cnt), acc, _ptr(ws),
+            ws.numel(), self._stream()
+        ))
+        _lib.check(rc, "dmdx_expand_range_f32")
+        return rng, cnt
+
+    def expand_pack(self, Ut: torch.Tensor, Ct: torch.Tensor, mean: torch.Tensor | None, std: torch.Tensor | None,
+                    packing, out: torch.Tensor | None = None, counts: torch.Tensor | None = None):
+        """``packing.encode`` of Xhat = mean + std * (U C), Xhat never stored (operands as :meth:`expand`; ``packing``
+        a :class:`labeled.Packing`) -> (Qt, counts): ``Qt`` the (T, m) int16 codes, the layout of a time slab of a
+        file, ``counts`` the (2,) int64 [filled, saturated].
+
+        ``out``: a (T, m) int16 view to write into (inner stride 1, any row stride >= m, any 2-byte aligned base);
+        ``counts``: a (2,) int64 tensor that ACCUMULATES (zero it once per variable)."""
+        m, k, ldu, T, Ct, ldc = self._expand_args(Ut, Ct, mean, std, "expand_pack")
+        Qt, ldq, counts = self._pack_out(out, counts, m, T, Ut.device, "expand_pack")
+        sf, ao = float(packing.scale_factor), float(packing.add_offset)
+        rc = self._timed("expand_pack", (m, k, T), lambda: self._lib.dmdx_expand_pack_i16(
+            _ptr(Ut), m, k, ldu, _ptr(Ct), ldc, T, _ptr(mean), _ptr(std), sf, ao, _ptr(Qt), ldq, _ptr(counts),
+            self._stream()
+        ))
+        _lib.check(rc, "dmdx_expand_pack_i16")
+        return Qt, counts
+
+    def field_range(self, Xt: torch.Tensor, out=None):
+        """:meth:`expand_range` of a field that exists.  Xt: (T, m) fp32 (any row stride) -> (range, count)."""
+        m, T, ldx = _check_mat(Xt, torch.float32, "field_range X")
+        rng, cnt, acc = self._range_out(out, Xt.device, "field_range")
+        ws = self._workspace(Xt.device, self._lib.dmdx_range_workspace_bytes(m, T))
+        rc = self._timed("field_range", (m, T), lambda: self._lib.dmdx_range_f32(
+            _ptr(Xt), m, T, ldx, _ptr(rng), _ptr(cnt), acc, _ptr(ws), ws.numel(), self._stream()
+        ))
+        _lib.check(rc, "dmdx_range_f32")
+        return rng, cnt
+
+    def pack(self, Xt: torch.Tensor, packing, out: torch.Tensor | None = None, counts: torch.Tensor | None = None):
+        """:meth:`expand_pack` of a field that exists.  Xt: (T, m) fp32 (any row stride) -> (Qt (T, m) int16, counts)."""
+        m, T, ldx = _check_mat(Xt, torch.float32, "pack X")
+        Qt, ldq, counts = self._pack_out(out, counts, m, T, Xt.device, "pack")
+        sf, ao = float(packing.scale_factor), float(packing.add_offset)
+        rc = self._timed("pack", (m, T), lambda: self._lib.dmdx_pack_f32_i16(
+            _ptr(Xt), m, T, ldx, sf, ao, _ptr(Qt), ldq, _ptr(counts), self._stream()
+        ))
+        _lib.check(rc, "dmdx_pack_f32_i16")
+        return Qt, counts
+
     # -- K6 -----------------------------------------------------------------
     def delay_shift_sum(self, G64: torch.Tensor, d: int, want32: bool = False):
         """Gd[i, j] = sum_{k<d} G[i+k, j+k]."""

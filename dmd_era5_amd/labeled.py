@@ -91,6 +91,40 @@ class Packing:
             x[q == f] = np.nan
         return x
 
+    FILL_I16 = -32768       # the fill code of a packing made by for_range; the live codes are -32767 .. 32767
+    MAX_I16 = 32767
+
+    @classmethod
+    def for_range(cls, vmin, vmax) -> "Packing":
+        """The int16 packing of the values ``vmin .. vmax`` (fp64): ``vmin`` encodes to -32767 and ``vmax`` to 32767,
+        -32768 is the fill code.  A single value packs with scale 1 and itself as the offset; no finite value at
+        all -- the range (+inf, -inf) the kernels return for an all-missing group -- with scale 1 and offset 0."""
+        vmin, vmax = float(vmin), float(vmax)
+        if np.isfinite(vmin) and np.isfinite(vmax) and vmin < vmax:
+            sf, ao = (vmax - vmin) / 65534.0, (vmax + vmin) / 2.0
+        elif np.isfinite(vmin) and vmin == vmax:
+            sf, ao = 1.0, vmin
+        elif vmin == np.inf and vmax == -np.inf:
+            sf, ao = 1.0, 0.0
+        else:
+            raise ValueError(f"Packing.for_range: ({vmin}, {vmax}) is no range")
+        return cls(sf, ao, (cls.FILL_I16,))
+
+    def encode(self, x, counts: bool = False):
+        """float32 values -> int16 codes, the inverse of :meth:`decode` and the one arithmetic of the package for it
+        (kernel K17 does the same on the device, bit for bit): a non-finite value becomes the fill code -32768
+        (*filled*); any other ``rint((float64(x) - add_offset) / scale_factor)`` -- an fp64 subtract, an fp64 divide,
+        round half to even -- clamped to -32767 .. 32767 (*saturated* where the clamp was needed).
+        ``counts=True`` returns ``(codes, filled, saturated)``."""
+        x = np.asarray(x, dtype=np.float32)
+        fin = np.isfinite(x)
+        with np.errstate(over="ignore", invalid="ignore", divide="ignore"):
+            r = np.rint((np.where(fin, x, np.float32(0)).astype(np.float64) - np.float64(self.add_offset))
+                        / np.float64(self.scale_factor))
+        sat = fin & ((r < -self.MAX_I16) | (r > self.MAX_I16))
+        q = np.where(fin, np.clip(r, -self.MAX_I16, self.MAX_I16), self.FILL_I16).astype(np.int16)
+        return (q, int((~fin).sum()), int(sat.sum())) if counts else q
+
     def __repr__(self):
         return f"Packing(scale_factor={self.scale_factor!r}, add_offset={self.add_offset!r}, fills={self.fills!r})"
 

@@ -457,6 +457,55 @@ int dmdx_unpack_i16_f32(const int16_t* S, int64_t lds, int64_t T, int64_t tstep,
                         double add_offset, int nfill, int fill0, int fill1, float* X, int64_t ldx,
                         unsigned long long* fill_count, void* stream);
 
+/* ---- K17: fields -> CF-packed int16 codes, and the value range a packing is chosen from ------------------------
+ * The inverse of K14: what xarray's CF encoder does to a variable written with scale_factor / add_offset / _FillValue
+ * (np.around((x - add_offset) / scale_factor)), done where the field is formed, so that the codes (2 bytes per value)
+ * are what HBM, PCIe and the file system see.  The fill code is -32768, the live codes are -32767 .. 32767.
+ *   code(x) = -32768                                                     x not finite (NaN, +-Inf): counted as FILLED
+ *           = clamp(rint((fp64(x) - add_offset) / scale_factor), -32767, 32767)     an fp64 subtract, an IEEE fp64
+ *             divide (no reciprocal, no FMA), round half to even; an element that needed the clamp counts as SATURATED
+ * -- bit for bit labeled.Packing.encode.  A packing of a range is labeled.Packing.for_range (host, fp64):
+ * scale_factor = (vmax - vmin) / 65534, add_offset = (vmax + vmin) / 2, so that vmin -> -32767 and vmax -> 32767.
+ *
+ * dmdx_expand_range_f32 / dmdx_expand_pack_i16 form Xhat = mu + sigma .* (U C) and never store it.  The operands are
+ * K12's -- U (m x k, ldu), C (k x T, ldc), mu / sigma (m floats each, nullable: 0 / 1), 1 <= k <= dmdx_pack_max_k()
+ * (256) -- and every xhat[i, t] is bit for bit what dmdx_expand_f32 stores for them (K12's chain over k, padded with
+ * zeros on both sides, and K12's two-step epilogue).
+ *   range[0] / range[1]   the minimum / maximum of the finite xhat (2 floats, device): exact, min and max do not round;
+ *                         (+Inf, -Inf) when nothing is finite
+ *   count[0]              the number of non-finite xhat (device)
+ *   accumulate != 0 merges with what range and count hold (row blocks; a group of rows -- one variable -- given as
+ *   several row ranges: a group is a pointer offset and a row count, the kernel knows none); otherwise both are
+ *   written and not read.  Per-workgroup slots in the workspace and a reduce kernel: no atomics, the result depends
+ *   on the values only.
+ *   Q                     the codes, m x T int16, snapshot stride ldq >= m, space contiguous: a time slab of the file,
+ *                         K14's S.  Q needs its 2-byte alignment only and ldq may be odd: the bits do not depend on
+ *                         the base or on ldq.
+ *   counts                (device, 2 x unsigned long long, nullable) ACCUMULATES [filled, saturated]: one atomicAdd per
+ *                         counter and workgroup that saw one; the caller zeroes it once per variable.
+ * dmdx_range_f32 / dmdx_pack_f32_i16: the same two contracts for a field X (m x T, ldx >= 1) that exists -- the K15
+ * spread, an ensemble mean, real snapshots.  Streaming: X is read once, 4 bytes read and 2 written per element.
+ * Memory: only logical elements of U, C, mu, sigma and X are read, only the logical m x T elements of Q are written
+ * (not the ldq - m behind a snapshot), nothing is written behind the workspace, no alignment is asked for beyond that
+ * of the element types.  m, T and the leading dimensions must be < 2^31.  A refused call (DMDX_E_INVALID: a null U, C,
+ * X, Q, range or count, k outside 1 .. 256, ldu < m, ldc < k, ldq < m, ldx < 1, a size >= 2^31, a scale_factor that is
+ * 0 or not finite, an add_offset that is not finite; DMDX_E_WORKSPACE: a null or short workspace) has written nothing.
+ * Values: a non-finite U[i, j], mu[i] or sigma[i] makes the codes of row i the fill code, a non-finite C[j, t] those of
+ * snapshot t, a non-finite X[i, t] that one code; every other code keeps its bits. */
+int dmdx_pack_max_k(void);
+size_t dmdx_expand_range_workspace_bytes(int64_t m, int64_t k, int64_t T);
+int dmdx_expand_range_f32(const float* U, int64_t m, int64_t k, int64_t ldu, const float* C, int64_t ldc, int64_t T,
+                          const float* mu, const float* sigma, float* range, unsigned long long* count,
+                          int accumulate, void* workspace, size_t workspace_bytes, void* stream);
+int dmdx_expand_pack_i16(const float* U, int64_t m, int64_t k, int64_t ldu, const float* C, int64_t ldc, int64_t T,
+                         const float* mu, const float* sigma, double scale_factor, double add_offset,
+                         int16_t* Q, int64_t ldq, unsigned long long* counts, void* stream);
+size_t dmdx_range_workspace_bytes(int64_t m, int64_t T);
+int dmdx_range_f32(const float* X, int64_t m, int64_t T, int64_t ldx, float* range, unsigned long long* count,
+                   int accumulate, void* workspace, size_t workspace_bytes, void* stream);
+int dmdx_pack_f32_i16(const float* X, int64_t m, int64_t T, int64_t ldx, double scale_factor, double add_offset,
+                      int16_t* Q, int64_t ldq, unsigned long long* counts, void* stream);
+
 /* ---- upper triangle of a symmetric fp64 matrix <-> packed row by row ---------------------
  * packed[i (2n - i + 1) / 2 + (j - i)] = A[i][j], j >= i: what the Gram all-reduce of the
  * row-sharded path moves (n (n + 1) / 2 doubles instead of n^2).  unpack writes both triangles. */
