@@ -1,31 +1,28 @@
 // K17: fields -> CF-packed int16 codes on the device, the inverse of K14 (unpack.hip), and the value range a
 // packing is chosen from.  Two pairs of entry points:
 //   dmdx_expand_range_f32 / dmdx_expand_pack_i16   Xhat = mu + sigma .* (U C) formed as K12 forms it and never stored:
-//                                                  one more body on K12's shape (expand.hip, which see for the tile,
-//                                                  the MFMA orientation and the k order; verify.hip is the sibling
-//                                                  this one was written after)
+//                                                  one more body on K12's shape (expand_tile.h, which see for the
+//                                                  tile, the MFMA orientation and the k order; verify.hip is the
+//                                                  sibling this one was written after)
 //   dmdx_range_f32 / dmdx_pack_f32_i16             the same two epilogues on a field that exists: streaming kernels
 //
 // Arithmetic of a code (labeled.Packing.encode, tests/pack_ref.py):
 //   non-finite x -> -32768 (the fill code), counted as filled
 //   r = rint((fp64(x) - add_offset) / scale_factor)     an fp64 subtract, an IEEE fp64 divide, round half to even
 //   r clamped to [-32767, 32767], an element that needed the clamp counted as saturated
-// No reciprocal and no FMA: contraction is off for the file, which also keeps K12's sigma * acc + mu two operations
-// (what the compiler makes of expand.hip, see verify.hip), so that xhat is K12's bit for bit.
+// No reciprocal and no FMA: contraction is off for the file.  xhat is K12's bit for bit: the chain and the two
+// operations of sigma * acc + mu are expand_tile.h's.
 //
 // Range.  min / max of the finite values and the number of non-finite ones: per lane over its tiles, over the wave by
 // shuffles, over the workgroup through LDS, one slot per workgroup in the workspace, a one-workgroup reduce kernel.
 // min and max do not round and an integer sum has no order: no atomics, the result depends on the values only.
 // Counts of the pack kernels ACCUMULATE with one vector atomicAdd per workgroup and counter, as K14's fill count.
-#include "dmdx_common.h"
+#include "expand_tile.h"
 
 #pragma clang fp contract(off)
 
 namespace {
 
-constexpr int RWG = 128;    // rows per workgroup (4 waves x 32)
-constexpr int TT = 32;      // columns of a tile
-constexpr int MAXK = 256;
 constexpr int FILL = -32768;
 constexpr int QMAX = 32767;
 constexpr unsigned kPosInf = 0x7F800000u, kNegInf = 0xFF800000u;
@@ -120,102 +117,45 @@ __global__ __launch_bounds__(256, 2) void expand_pack_kernel(
     const float* __restrict__ mu, const float* __restrict__ sigma, double sf, double ao, int16_t* __restrict__ Q,
     int64_t ldq, int64_t tiles_per_wg, int64_t ntiles, int cvec, float* __restrict__ minmax,
     unsigned long long* __restrict__ nonfin, unsigned long long* __restrict__ counts) {
-  constexpr int KP = 16 * KG;        // padded k
-  constexpr int KS = KP + 4;         // LDS row stride of the [t][k] image
-  constexpr int PPT = KP / 4;        // 16-byte pieces per column of C
-  constexpr int NPIECE = TT * PPT;
-  constexpr int NPT = (NPIECE + 255) / 256;
-  __shared__ __attribute__((aligned(16))) float ctile[2][TT * KS];
+  __shared__ __attribute__((aligned(16))) float ctile[2][Geom<KG>::STAGE];
 
-  const int tid = threadIdx.x;
-  const int lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-  const int li = lane & 31, h = lane >> 5;
-  const int64_t row = (int64_t)blockIdx.x * RWG + wave * 32 + li;
-  const bool rowok = row < m;
-
-  // the wave's U panel: register 4 q + e = U[row][8 q + 4 h + e]; exact zeros past k and past m
+  const Lane L = lane_of(m);
   float ureg[8 * KG];
-#pragma unroll
-  for (int s = 0; s < 8 * KG; ++s) {
-    const int j = 8 * (s >> 2) + 4 * h + (s & 3);
-    ureg[s] = (rowok && j < k) ? U[(int64_t)j * ldu + row] : 0.f;
-  }
-  const float mu_i = (mu != nullptr && rowok) ? mu[row] : 0.f;
-  const float sg_i = (sigma != nullptr && rowok) ? sigma[row] : 1.f;
-
-  f32x4 creg[NPT];
-  auto load_c = [&](int64_t t0) {
-#pragma unroll
-    for (int i = 0; i < NPT; ++i) {
-      const int idx = tid + 256 * i;
-      if (NPIECE % 256 != 0 && idx >= NPIECE) continue;
-      const int tl = idx / PPT, j = 4 * (idx % PPT);
-      const int64_t t = t0 + tl;
-      f32x4 v = {0.f, 0.f, 0.f, 0.f};
-      if (t < T && j < k) {
-        const float* q = C + t * ldc + j;
-        if (cvec && j + 4 <= k) {
-          v = *reinterpret_cast<const f32x4*>(q);
-        } else {
-#pragma unroll
-          for (int e = 0; e < 4; ++e)
-            if (j + e < k) v[e] = q[e];
-        }
-      }
-      creg[i] = v;
-    }
-  };
-  auto store_c = [&](int st) {
-#pragma unroll
-    for (int i = 0; i < NPT; ++i) {
-      const int idx = tid + 256 * i;
-      if (NPIECE % 256 != 0 && idx >= NPIECE) continue;
-      *reinterpret_cast<f32x4*>(&ctile[st][(idx / PPT) * KS + 4 * (idx % PPT)]) = creg[i];
-    }
-  };
+  load_panel<KG>(ureg, U, ldu, k, L);
+  const float mu_i = (mu != nullptr && L.rowok) ? mu[L.row] : 0.f;
+  const float sg_i = (sigma != nullptr && L.rowok) ? sigma[L.row] : 1.f;
 
   const int64_t tile0 = (int64_t)blockIdx.y * tiles_per_wg;
   const int64_t tile1 = tile0 + tiles_per_wg < ntiles ? tile0 + tiles_per_wg : ntiles;
   Tally tally;
   tally_init(tally);
 
-  load_c(tile0 * TT);
-  store_c(0);
+  Stager<KG> cs;
+  cs.load(C, ldc, 0, tile0 * TT, T, k, cvec, L.tid);
+  cs.store(ctile[0], L.tid);
   __syncthreads();
   int cur = 0;
   for (int64_t tile = tile0; tile < tile1; ++tile) {
     const int64_t t0 = tile * TT;
     const bool has_next = tile + 1 < tile1;
-    if (has_next) load_c(t0 + TT);
+    if (has_next) cs.load(C, ldc, 0, t0 + TT, T, k, cvec, L.tid);
 
-    f32x16 acc;
-#pragma unroll
-    for (int r = 0; r < 16; ++r) acc[r] = 0.f;
-    const float* ct = &ctile[cur][li * KS + 4 * h];
-#pragma unroll
-    for (int q = 0; q < 2 * KG; ++q) {
-      const f32x4 a = *reinterpret_cast<const f32x4*>(ct + 8 * q);
-#pragma unroll
-      for (int e = 0; e < 4; ++e) acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a[e], ureg[4 * q + e], acc, 0, 0, 0);
-    }
+    const f32x16 acc = mfma_chain<KG>(ctile[cur], ureg, L);
 
 #pragma unroll
     for (int r = 0; r < 16; ++r) {
-      const int64_t t = t0 + (r & 3) + 8 * (r >> 2) + 4 * h;
-      // K12's epilogue
-      float v = acc[r];
-      if (sigma != nullptr) v *= sg_i;
-      if (mu != nullptr) v += mu_i;
-      if (rowok && t < T) {
+      const int64_t t = t0 + col_of(r, L.h);
+      const float v = affine(acc[r], sigma != nullptr, sg_i, mu != nullptr, mu_i);
+      if (L.rowok && t < T) {
         if constexpr (PACK) {
-          Q[t * ldq + row] = encode_one(tally, v, sf, ao);
+          Q[t * ldq + L.row] = encode_one(tally, v, sf, ao);
         } else {
           range_one(tally, v);
         }
       }
     }
 
-    if (has_next) store_c(cur ^ 1);
+    if (has_next) cs.store(ctile[cur ^ 1], L.tid);
     __syncthreads();
     cur ^= 1;
   }
@@ -290,23 +230,6 @@ __global__ __launch_bounds__(256) void range_reduce_kernel(const float* __restri
   count[0] = cn;
 }
 
-// K12's plan (expand.hip, plan_for): the T axis is split over blockIdx.y until the launch has ~2048 workgroups; a
-// function of the shapes only
-struct Plan {
-  int64_t nrb, ntiles, tiles_per_wg, nsplit;
-};
-Plan plan_for(int64_t m, int64_t T) {
-  Plan p;
-  p.nrb = (m + RWG - 1) / RWG;
-  p.ntiles = (T + TT - 1) / TT;
-  int64_t want = (2048 + p.nrb - 1) / p.nrb;
-  if (want > p.ntiles) want = p.ntiles;
-  if (want < 1) want = 1;
-  p.tiles_per_wg = (p.ntiles + want - 1) / want;
-  p.nsplit = (p.ntiles + p.tiles_per_wg - 1) / p.tiles_per_wg;
-  return p;
-}
-
 // the streaming kernels: 256 rows per workgroup, snapshots over grid.y until the launch has ~4096 workgroups
 struct FieldPlan {
   int64_t gx, gy;
@@ -321,20 +244,8 @@ FieldPlan field_plan_for(int64_t m, int64_t T) {
   return p;
 }
 
-constexpr int64_t DIM_LIMIT = int64_t(1) << 31;
-
 // [<= 15 bytes to a 16-byte boundary][nonfin: n x uint64][minmax: n x 2 fp32]
 inline size_t slots_bytes(int64_t n) { return 16 + (size_t)n * 16; }
-
-int check_expand(const float* U, int64_t m, int64_t k, int64_t ldu, const float* C, int64_t ldc, int64_t T, const char* who) {
-  DMDX_CHECK_ARG(U != nullptr && C != nullptr, "%s: U and C must not be null", who);
-  DMDX_CHECK_ARG(m >= 1 && T >= 1, "%s: m = %lld, T = %lld must be >= 1", who, (long long)m, (long long)T);
-  DMDX_CHECK_ARG(k >= 1 && k <= MAXK, "%s: k = %lld outside 1 .. %d", who, (long long)k, MAXK);
-  DMDX_CHECK_ARG(ldu >= m && ldc >= k, "%s: ldu = %lld < m = %lld or ldc = %lld < k = %lld", who, (long long)ldu,
-                 (long long)m, (long long)ldc, (long long)k);
-  DMDX_CHECK_ARG(m < DIM_LIMIT && T < DIM_LIMIT && ldu < DIM_LIMIT && ldc < DIM_LIMIT, "%s: m, T, ldu, ldc must be < 2^31", who);
-  return 0;
-}
 
 int check_field(const float* X, int64_t m, int64_t T, int64_t ldx, const char* who) {
   DMDX_CHECK_ARG(X != nullptr, "%s: X must not be null", who);
@@ -376,22 +287,12 @@ int launch_expand(const float* U, int64_t m, int k, int64_t ldu, const float* C,
                   const float* sigma, double sf, double ao, int16_t* Q, int64_t ldq, float* minmax,
                   unsigned long long* nonfin, unsigned long long* counts, hipStream_t st, const char* who) {
   const Plan p = plan_for(m, T);
-  const int cvec = dmdx_aligned16(C) && ldc % 4 == 0;
-  const dim3 grid((unsigned)p.nrb, (unsigned)p.nsplit);
-  switch ((k + 15) / 16) {
-#define DMDX_CASE(KG)                                                                                                    \
-  case KG:                                                                                                               \
-    hipLaunchKernelGGL((expand_pack_kernel<KG, PACK>), grid, dim3(256), 0, st, U, m, k, ldu, C, ldc, T, mu, sigma, sf, ao, \
-                       Q, ldq, p.tiles_per_wg, p.ntiles, cvec, minmax, nonfin, counts);                                  \
-    break
-    DMDX_CASE(1); DMDX_CASE(2); DMDX_CASE(3); DMDX_CASE(4); DMDX_CASE(5); DMDX_CASE(6); DMDX_CASE(7); DMDX_CASE(8);
-    DMDX_CASE(9); DMDX_CASE(10); DMDX_CASE(11); DMDX_CASE(12); DMDX_CASE(13); DMDX_CASE(14); DMDX_CASE(15);
-    DMDX_CASE(16);
-#undef DMDX_CASE
-    default:
-      dmdx_set_error("%s: unsupported k %d", who, k);
-      return DMDX_E_INVALID;
-  }
+  const int cvec = cvec_of(C, ldc);
+#define DMDX_LAUNCH(KG)                                                                                                     \
+  hipLaunchKernelGGL((expand_pack_kernel<KG, PACK>), p.grid(), dim3(256), 0, st, U, m, k, ldu, C, ldc, T, mu, sigma, sf, ao, \
+                     Q, ldq, p.tiles_per_wg, p.ntiles, cvec, minmax, nonfin, counts)
+  DMDX_DISPATCH_KG(k, who, DMDX_LAUNCH)
+#undef DMDX_LAUNCH
   DMDX_LAUNCH_CHECK();
   return 0;
 }
@@ -412,7 +313,7 @@ extern "C" int dmdx_expand_range_f32(const float* U, int64_t m, int64_t k, int64
                                      unsigned long long* count, int accumulate, void* workspace, size_t workspace_bytes,
                                      void* stream) {
   const char* who = "dmdx_expand_range_f32";
-  if (int rc = check_expand(U, m, k, ldu, C, ldc, T, who)) return rc;
+  if (int rc = check_common(U, m, k, ldu, C, ldc, T, who)) return rc;
   const Plan p = plan_for(m, T);
   const int64_t n = p.nrb * p.nsplit;
   Slots s;
@@ -431,7 +332,7 @@ extern "C" int dmdx_expand_pack_i16(const float* U, int64_t m, int64_t k, int64_
                                     double add_offset, int16_t* Q, int64_t ldq, unsigned long long* counts,
                                     void* stream) {
   const char* who = "dmdx_expand_pack_i16";
-  if (int rc = check_expand(U, m, k, ldu, C, ldc, T, who)) return rc;
+  if (int rc = check_common(U, m, k, ldu, C, ldc, T, who)) return rc;
   if (int rc = check_packing(scale_factor, add_offset, Q, ldq, m, who)) return rc;
   return launch_expand<true>(U, m, (int)k, ldu, C, ldc, T, mu, sigma, scale_factor, add_offset, Q, ldq, nullptr, nullptr,
                              counts, (hipStream_t)stream, who);

@@ -39,6 +39,12 @@ def _check_mat(t: torch.Tensor, dtype, name: str) -> tuple[int, int, int]:
     return t.shape[1], t.shape[0], ld
 
 
+def _check_vec(v: torch.Tensor | None, m: int, device, who: str, name: str) -> None:
+    """An optional per-row vector: None, or (m,) contiguous fp32 on `device`."""
+    if v is not None and (v.dtype != torch.float32 or v.shape != (m,) or v.device != device or not v.is_contiguous()):
+        raise _lib.DmdxError(f"{who}: {name} must be a contiguous fp32 vector of length {m} on {device}")
+
+
 class HipKernels:
     """The product kernel provider (libdmdx.so on the current CUDA/HIP device)."""
 
@@ -266,9 +272,7 @@ class HipKernels:
         Ct = self.pitch(Ct)
         ldc = _check_mat(Ct, torch.float32, f"{who} C")[2]
         for v, name in ((mean, "mean"), (std, "std")):
-            if v is not None and (v.dtype != torch.float32 or v.shape != (m,) or v.device != Ut.device
-                                  or not v.is_contiguous()):
-                raise _lib.DmdxError(f"{who}: {name} must be a contiguous fp32 vector of length {m} on {Ut.device}")
+            _check_vec(v, m, Ut.device, who, name)
         return m, k, ldu, T, Ct, ldc
 
     def expand(self, Ut: torch.Tensor, Ct: torch.Tensor, mean: torch.Tensor | None = None,
@@ -339,9 +343,7 @@ class HipKernels:
         if (mx, Tx) != (m, T) or Xt.device != Ut.device:
             raise _lib.DmdxError(f"verify: X must be ({T}, {m}) on {Ut.device}, got {tuple(Xt.shape)}")
         for v, name in ((weight, "weight"), (clim, "clim")):
-            if v is not None and (v.dtype != torch.float32 or v.shape != (m,) or v.device != Ut.device
-                                  or not v.is_contiguous()):
-                raise _lib.DmdxError(f"verify: {name} must be a contiguous fp32 vector of length {m} on {Ut.device}")
+            _check_vec(v, m, Ut.device, "verify", name)
         if out is not None:
             if out.shape != (6, T) or out.dtype != torch.float64 or not out.is_contiguous() or out.device != Ut.device:
                 raise _lib.DmdxError(f"verify: out must be a contiguous (6, {T}) fp64 tensor on {Ut.device}")
@@ -378,9 +380,7 @@ class HipKernels:
             Dt = Dev.reshape(B * T, k)
         Dt = self.pitch(Dt)
         ldd = _check_mat(Dt, torch.float32, f"{who} Dev")[2]
-        if std is not None and (std.dtype != torch.float32 or std.shape != (m,) or std.device != Ut.device
-                                or not std.is_contiguous()):
-            raise _lib.DmdxError(f"{who}: std must be a contiguous fp32 vector of length {m} on {Ut.device}")
+        _check_vec(std, m, Ut.device, who, "std")
         return m, k, ldu, int(T), int(B), Dt, ldd
 
     def spread(self, Ut: torch.Tensor, Dev: torch.Tensor, std: torch.Tensor | None = None,
@@ -445,9 +445,7 @@ class HipKernels:
         if mx != m or Xt.device != Ut.device:
             raise _lib.DmdxError(f"project: X must be (T, {m}) on {Ut.device}, got {tuple(Xt.shape)} on {Xt.device}")
         for v, name in ((mean, "mean"), (std, "std")):
-            if v is not None and (v.dtype != torch.float32 or v.shape != (m,) or v.device != Ut.device
-                                  or not v.is_contiguous()):
-                raise _lib.DmdxError(f"project: {name} must be a contiguous fp32 vector of length {m} on {Ut.device}")
+            _check_vec(v, m, Ut.device, "project", name)
         if out is not None:
             Ct, energy = out
             if Ct.shape != (T, k) or Ct.dtype != torch.float64 or not Ct.is_contiguous() or Ct.device != Ut.device:

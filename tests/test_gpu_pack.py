@@ -213,24 +213,27 @@ def test_parity_over_the_shape_edges(L):
 
 
 def test_several_workgroups_and_time_splits(L):
-    """1003 rows = 8 row blocks, 300 snapshots = 10 tiles, one per workgroup: 80 partial slots, the T split."""
-    c = rand_case(np.random.default_rng(1702), 1003, 37, 300, 2)
-    X = check_case(L, c)
-    # a prescribed packing that is too narrow: +-32767 and the exact number of clamped values
-    sf, ao = pr.for_range(240.0, 260.0)
-    c.counts = _cnt(2)
-    assert c.run_pack(L, sf, ao) == 0
-    q, filled, sat = pr.encode(X, sf, ao)
-    assert sat > 1000 and filled == 0 and _cnt_vals(c.counts) == [0, sat]
-    got = c.Q.logical()
-    assert np.array_equal(got, q) and got.min() == -32767 and got.max() == 32767
-    # counts ACCUMULATE; without counts the codes are the same
-    assert c.run_pack(L, sf, ao) == 0 and _cnt_vals(c.counts) == [0, 2 * sat]
-    assert c.run_pack(L, sf, ao, counts=False) == 0 and np.array_equal(c.Q.logical(), q)
-    # a negative scale_factor
-    assert c.run_pack(L, -sf, ao, counts=False) == 0
-    assert np.array_equal(c.Q.logical(), pr.encode(X, -sf, ao)[0])
-    c.Q.check_untouched()
+    """1003 rows = 8 row blocks, 300 snapshots = 10 tiles, one per workgroup: 80 partial slots, the T split.
+    40000 rows = 313 row blocks, 470 snapshots = 15 tiles (the last partial) in 5 splits: three tiles per workgroup,
+    the smallest count at which the prefetch runs and an LDS stage is used a second time."""
+    for shape in ((1003, 37, 300, 2), (40000, 7, 470, 1)):
+        c = rand_case(np.random.default_rng(1702), *shape)
+        X = check_case(L, c)
+        # a prescribed packing that is too narrow: +-32767 and the exact number of clamped values
+        sf, ao = pr.for_range(240.0, 260.0)
+        c.counts = _cnt(2)
+        assert c.run_pack(L, sf, ao) == 0
+        q, filled, sat = pr.encode(X, sf, ao)
+        assert sat > 1000 and filled == 0 and _cnt_vals(c.counts) == [0, sat]
+        got = c.Q.logical()
+        assert np.array_equal(got, q) and got.min() == -32767 and got.max() == 32767
+        # counts ACCUMULATE; without counts the codes are the same
+        assert c.run_pack(L, sf, ao) == 0 and _cnt_vals(c.counts) == [0, 2 * sat]
+        assert c.run_pack(L, sf, ao, counts=False) == 0 and np.array_equal(c.Q.logical(), q)
+        # a negative scale_factor
+        assert c.run_pack(L, -sf, ao, counts=False) == 0
+        assert np.array_equal(c.Q.logical(), pr.encode(X, -sf, ao)[0])
+        c.Q.check_untouched()
 
 
 # ---------------------------------------------------------------- a field that exists

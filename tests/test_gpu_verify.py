@@ -359,8 +359,10 @@ def int_case(rng, m, k, T, layout):
     return c
 
 
-@pytest.mark.parametrize("shape", [(131, 17, 77, 2), (1003, 50, 300, 1), (5000, 7, 33, 0)])
+@pytest.mark.parametrize("shape", [(131, 17, 77, 2), (1003, 50, 300, 1), (5000, 7, 33, 0), (40000, 7, 470, 1)])
 def test_exact_integers(L, shape):
+    """The last shape is the smallest round one at which a workgroup walks three tiles (313 row blocks -> 5 T splits
+    of 15 tiles, the last partial): the prefetch, the other LDS stage and the reuse of a slot parity all run."""
     c = int_case(np.random.default_rng(1608), *shape)
     assert c.run(L) == 0, L.dmdx_last_error()
     col, row = c.sums()
