@@ -84,6 +84,9 @@ SIGNATURES = {
     "dmdx_range_workspace_bytes": (_sz, [_i64, _i64]),
     "dmdx_range_f32": (C.c_int, [_p, _i64, _i64, _i64, _p, _p, C.c_int, _p, _sz, _p]),
     "dmdx_pack_f32_i16": (C.c_int, [_p, _i64, _i64, _i64, C.c_double, C.c_double, _p, _i64, _p, _p]),
+    "dmdx_clim_mean_f32": (C.c_int, [_p, _i64, _i64, _i64, _p, _i64, _p, _i64, _p, _i64, _p]),
+    "dmdx_clim_std_f32": (C.c_int, [_p, _i64, _i64, _i64, _p, _i64, _p, _i64, _p, _i64, C.c_int, _p, _i64, _p]),
+    "dmdx_clim_apply_f32": (C.c_int, [_p, _i64, _i64, _i64, _p, _i64, _p, _i64, _p, _i64, C.c_int, _p, _i64, _p]),
     "dmdx_pack_triu_f64": (C.c_int, [_p, _i64, _i64, _p, _p]),
     "dmdx_unpack_triu_f64": (C.c_int, [_p, _i64, _p, _i64, _p]),
     "dmdx_exp_basis": (C.c_int, [_p, _p, _i64, _i64, _p, _p, C.c_int, _p]),

@@ -1,0 +1,240 @@
+"""Slot climatology of the snapshots and anomalies against it (K18, csrc/clim.hip).
+
+K5 removes the mean of a grid point over ALL of time (the reference's ``standardize_data``).  ERA5 temperature,
+geopotential and wind are dominated by the annual and the diurnal cycle, and a DMD is fitted to what is left once
+they are gone: the anomalies against a climatology that depends on the hour of the day and the time of the year.
+A *slot* is a class of the calendar; this module turns time stamps into slots on the host (:func:`slots_of`, pure
+numpy), and the device forms the mean (and standard deviation) of every row per slot and subtracts / restores it
+(``HipKernels.clim_mean`` / ``clim_std`` / ``clim_apply_``): one read of the resident ``(time, rows)`` blocks for the
+mean, one read and one write for the anomalies, no fp64 copy and no gathered ``mean[slot]`` second X.
+
+    clim = Climatology.fit(Xblocks, times, "month_hour")       # (288, rows) per block
+    clim.remove_(Xblocks, times)                               # X <- X - clim[slot(t)], in place
+    fields = forecast.fields(t, climatology=clim, times=valid) # the model's anomalies back to full fields
+
+Rows are independent: row shards fit and apply their own blocks, no collective is involved.
+"""
+from __future__ import annotations
+
+from dataclasses import dataclass
+
+import numpy as np
+import torch
+
+from .labeled import Coord, DataArray, Dataset
+from .svd import _kern
+
+__all__ = ["KINDS", "slots_of", "Climatology"]
+
+# kind -> number of slots
+KINDS = {"hour": 24, "month_hour": 288, "dayofyear": 366, "dayofyear_hour": 8784}
+_LEAP_CUM = np.array([0, 31, 60, 91, 121, 152, 182, 213, 244, 274, 305, 335], dtype=np.int64)
+
+
+def _calendar(times):
+    """-> (month 0..11, day of the year 0..365 in the LEAP calendar -- Feb 29 is 59, Mar 1 is 60 in every year --,
+    hour 0..23) of datetime64 time stamps."""
+    t = np.atleast_1d(np.asarray(times))
+    if not np.issubdtype(t.dtype, np.datetime64):
+        raise TypeError(f"slots_of: times must be numpy.datetime64, got {t.dtype}")
+    if t.ndim != 1:
+        raise ValueError(f"slots_of: times must be one-dimensional, got {t.shape}")
+    if np.isnat(t).any():
+        raise ValueError("slots_of: times holds NaT")
+    days = t.astype("datetime64[D]")
+    months = t.astype("datetime64[M]")
+    month = months.astype(np.int64) % 12
+    dom = (days - months.astype("datetime64[D]")).astype(np.int64)
+    hour = (t.astype("datetime64[h]") - days.astype("datetime64[h]")).astype(np.int64)
+    return month, _LEAP_CUM[month] + dom, hour
+
+
+def slots_of(times, kind: str, window_days: int = 0):
+    """Time stamps -> the slot lists K18 takes: ``(slot, order, start, S)``.
+
+    ``kind``: ``"hour"`` (24 slots), ``"month_hour"`` (288: month * 24 + hour), ``"dayofyear"`` (366, counted in the
+    leap calendar: Feb 29 is slot 59 and exists in leap years only) or ``"dayofyear_hour"`` (8784: day * 24 + hour).
+    ``slot`` (T,) int32: the snapshot's own class.  ``order`` / ``start`` (int32; ``start`` has S + 1 entries): the
+    CSR list of the members -- slot s owns ``order[start[s]:start[s + 1]]``, ascending in time.
+    ``window_days`` = w > 0 (the two day-of-year kinds only): slot s lists every snapshot whose day of the year is
+    within w days of it, circularly over 366 (with the same hour for ``"dayofyear_hour"``): a smoother climatology
+    from few years, each snapshot in 2 w + 1 slots.  ``slot`` stays the snapshot's own class."""
+    if kind not in KINDS:
+        raise ValueError(f"slots_of: kind = {kind!r}, expected one of {sorted(KINDS)}")
+    w = int(window_days)
+    if w < 0 or (w > 0 and not kind.startswith("dayofyear")):
+        raise ValueError(f"slots_of: window_days = {window_days} needs a day-of-year kind and w >= 0")
+    if 2 * w + 1 > 366:
+        raise ValueError(f"slots_of: a window of +-{w} days covers the year more than once")
+    S = KINDS[kind]
+    month, doy, hour = _calendar(times)
+    T = int(doy.shape[0])
+    per_day = 24 if kind == "dayofyear_hour" else 1
+    if kind == "hour":
+        slot = hour
+    elif kind == "month_hour":
+        slot = month * 24 + hour
+    elif kind == "dayofyear":
+        slot = doy
+    else:
+        slot = doy * 24 + hour
+    if T * (2 * w + 1) >= 2**31:
+        raise ValueError(f"slots_of: {T} snapshots x {2 * w + 1} slots each do not fit an int32 list")
+    if w == 0:
+        key, idx = slot, np.arange(T, dtype=np.int64)
+    else:
+        sub = hour if per_day == 24 else 0
+        off = np.arange(-w, w + 1, dtype=np.int64)
+        key = (((doy[None, :] + off[:, None]) % 366) * per_day + sub).reshape(-1)
+        idx = np.tile(np.arange(T, dtype=np.int64), off.shape[0])
+    stamps = np.atleast_1d(np.asarray(times)).astype("datetime64[ns]").astype(np.int64)
+    perm = np.lexsort((idx, stamps[idx], key))                  # by slot, then time, then index
+    order = idx[perm].astype(np.int32)
+    start = np.searchsorted(key[perm], np.arange(S + 1, dtype=np.int64)).astype(np.int32)
+    return slot.astype(np.int32), order, start, S
+
+
+def _attr_int(v) -> int:
+    return int(np.asarray(v).reshape(-1)[0])
+
+
+def _attr_str(v) -> str:
+    v = np.asarray(v).reshape(-1)[0] if not isinstance(v, (str, bytes)) else v
+    return v.decode() if isinstance(v, bytes) else str(v)
+
+
+@dataclass
+class Climatology:
+    """The slot climatology of a list of row blocks: ``mean`` (and ``sd``) hold one ``(S, rows)`` fp32 tensor per
+    block, ``counts`` (S,) the snapshots every slot was formed from, ``ddof`` the one of ``sd``."""
+
+    kind: str
+    window_days: int
+    mean: list
+    sd: list | None
+    counts: np.ndarray
+    ddof: int = 0
+    kern: object = None
+
+    @property
+    def n_slots(self) -> int:
+        return KINDS[self.kind]
+
+    # -- fit ------------------------------------------------------------------------------------------------------
+    @classmethod
+    def fit(cls, Xblocks, times, kind: str, window_days: int = 0, with_std: bool = False, ddof: int = 0,
+            kern=None) -> "Climatology":
+        """The climatology of the snapshots ``Xblocks`` ((T, rows) fp32 per block, any iterable consumed once) taken
+        at ``times`` (T datetime64 stamps): one read of every block for the mean, one more with ``with_std``."""
+        if ddof not in (0, 1):
+            raise ValueError(f"Climatology.fit: ddof = {ddof}, expected 0 or 1")
+        kern = _kern(kern)
+        _, order, start, S = slots_of(times, kind, window_days)
+        T = int(np.atleast_1d(np.asarray(times)).shape[0])
+        lists, mean, sd = {}, [], []
+        for b, X in enumerate(Xblocks):
+            if X.shape[0] != T:
+                raise ValueError(f"Climatology.fit: block {b} holds {int(X.shape[0])} snapshots, times has {T}")
+            if X.device not in lists:
+                lists[X.device] = (torch.from_numpy(order).to(X.device), torch.from_numpy(start).to(X.device))
+            o, s = lists[X.device]
+            mean.append(kern.clim_mean(X, o, s))
+            if with_std:
+                sd.append(kern.clim_std(X, o, s, mean[-1], ddof=ddof))
+        return cls(kind, int(window_days), mean, sd if with_std else None, np.diff(start.astype(np.int64)), int(ddof), kern)
+
+    # -- apply ----------------------------------------------------------------------------------------------------
+    def _labels(self, times, who: str) -> np.ndarray:
+        slot = slots_of(times, self.kind)[0]
+        empty = np.unique(slot[self.counts[slot] == 0])
+        if empty.size:
+            raise ValueError(f"Climatology.{who}: slot {int(empty[0])} of kind {self.kind!r} was fitted from no snapshot"
+                             f" ({empty.size} unpopulated slots are asked for): its climatology is not defined")
+        return slot
+
+    def _apply(self, Xblocks, times, out, restore: bool, use_sd: bool, who: str) -> list:
+        slot = self._labels(times, who)                           # (raises before any launch)
+        Xblocks = list(Xblocks)
+        if len(Xblocks) != len(self.mean):
+            raise ValueError(f"Climatology.{who}: {len(Xblocks)} blocks, the climatology holds {len(self.mean)}")
+        kern = _kern(self.kern)
+        labels, res = {}, []
+        for b, X in enumerate(Xblocks):
+            if tuple(X.shape) != (slot.shape[0], int(self.mean[b].shape[1])):
+                raise ValueError(f"Climatology.{who}: block {b} is {tuple(X.shape)}, {slot.shape[0]} times and "
+                                 f"{int(self.mean[b].shape[1])} rows asked for")
+            if X.device not in labels:
+                labels[X.device] = torch.from_numpy(slot).to(X.device)
+            sd = self.sd[b] if (use_sd and self.sd is not None) else None
+            res.append(kern.clim_apply_(X, labels[X.device], self.mean[b], sd, restore=restore,
+                                        out=None if out is None else out[b]))
+        return res
+
+    def remove_(self, Xblocks, times, out=None) -> list:
+        """``X <- (X - mean[slot(t)]) [/ sd[slot(t)]]`` for the snapshots taken at ``times``, one launch per block;
+        in place, or into the list ``out`` of (T, rows) fp32 views that do not overlap X.  A time whose slot was
+        fitted from no snapshot is a ValueError before any launch."""
+        return self._apply(Xblocks, times, out, False, True, "remove_")
+
+    def restore_(self, Xblocks, times, out=None) -> list:
+        """The inverse of :meth:`remove_`: ``X <- X [* sd] + mean`` (two roundings)."""
+        return self._apply(Xblocks, times, out, True, True, "restore_")
+
+    def at(self, times) -> list:
+        """The climatology fields of ``times``: per block a (T, rows) fp32 tensor, ``mean[slot(t)]`` -- restore on
+        zeros without the standard deviation."""
+        T = int(np.atleast_1d(np.asarray(times)).shape[0])
+        Z = [torch.zeros((T, int(M.shape[1])), dtype=torch.float32, device=M.device) for M in self.mean]
+        return self._apply(Z, times, None, True, False, "at")
+
+    # -- persistence ----------------------------------------------------------------------------------------------
+    def to_dataset(self, coords=None) -> Dataset:
+        """``clim_mean(slot, space)``, ``clim_std`` if there is one, ``clim_count(slot)`` and the attributes ``kind``,
+        ``window_days``, ``ddof``; ``coords``: the per-row coordinates of the decomposed array (``space`` and what
+        lives on it), taken over as they are.  ``io_netcdf.to_netcdf`` writes it."""
+        S = self.n_slots
+        cds = {"slot": Coord("slot", np.arange(S, dtype=np.int64))}
+        for name, c in (coords or {}).items():
+            c = c if isinstance(c, Coord) else Coord(name, c)
+            if set(c.dims) <= {"space"} or name == "space":
+                cds[name] = c
+        ds = Dataset(coords=cds, attrs={"kind": self.kind, "window_days": int(self.window_days), "ddof": int(self.ddof)})
+        row = {k: v for k, v in cds.items() if k != "slot"}
+
+        def field(blocks):
+            return np.concatenate([B.detach().cpu().numpy() for B in blocks], axis=1)
+
+        ds["clim_mean"] = DataArray(field(self.mean), ("slot", "space"), {"slot": cds["slot"], **row})
+        if self.sd is not None:
+            ds["clim_std"] = DataArray(field(self.sd), ("slot", "space"), {"slot": cds["slot"], **row})
+        ds["clim_count"] = DataArray(np.asarray(self.counts, dtype=np.int64), ("slot",), {"slot": cds["slot"]})
+        return ds
+
+    @classmethod
+    def from_dataset(cls, ds: Dataset, rows=None, device=None, kern=None) -> "Climatology":
+        """The climatology :meth:`to_dataset` stored (``io_netcdf.open_dataset`` of its file).  ``rows``: the row
+        counts of the blocks to cut the fields into (default: one block); ``device``: where they go (default: the
+        GPU for the HIP provider)."""
+        kern = _kern(kern)
+        if device is None:
+            device = torch.device("cuda" if getattr(kern, "name", "") == "hip" else "cpu")
+        kind = _attr_str(ds.attrs["kind"])
+        if kind not in KINDS:
+            raise ValueError(f"Climatology.from_dataset: kind = {kind!r}")
+        mean = np.ascontiguousarray(np.asarray(ds["clim_mean"].values), dtype=np.float32)
+        S, M = mean.shape
+        if S != KINDS[kind]:
+            raise ValueError(f"Climatology.from_dataset: clim_mean holds {S} slots, kind {kind!r} has {KINDS[kind]}")
+        rows = [M] if rows is None else [int(r) for r in rows]
+        if sum(rows) != M:
+            raise ValueError(f"Climatology.from_dataset: rows sum to {sum(rows)}, the file holds {M}")
+        edges = np.concatenate([[0], np.cumsum(rows)]).astype(np.int64)
+
+        def cut(a):
+            return [torch.from_numpy(np.ascontiguousarray(a[:, i:j])).to(device) for i, j in zip(edges[:-1], edges[1:])]
+
+        sd = None
+        if "clim_std" in ds:
+            sd = cut(np.ascontiguousarray(np.asarray(ds["clim_std"].values), dtype=np.float32))
+        counts = np.asarray(ds["clim_count"].values).astype(np.int64).reshape(-1)
+        return cls(kind, _attr_int(ds.attrs["window_days"]), cut(mean), sd, counts, _attr_int(ds.attrs["ddof"]), kern)

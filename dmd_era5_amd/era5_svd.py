@@ -266,7 +266,7 @@ FORECAST_STAGE_BYTES = 256 << 20
 
 def write_forecast_slice(path: str, forecast, t, time, variables, levels, latitude, longitude, *, packing=None,
                          ensemble: bool = False, spread: bool = False, slab: int | None = None,
-                         attrs: dict | None = None) -> dict:
+                         attrs: dict | None = None, climatology=None) -> dict:
     """The fields of a :class:`forecast.DmdForecast` at the model times ``t`` as a NETCDF4 file in the schema of the
     input slice: one ``int16`` variable ``(time, level, latitude, longitude)`` per name with ``scale_factor``,
     ``add_offset`` (float64) and ``_FillValue`` (int16 -32768), the coordinate variables, and the global attributes
@@ -288,6 +288,10 @@ def write_forecast_slice(path: str, forecast, t, time, variables, levels, latitu
     device-to-host copy of the codes, ``Writer.write_slab``; by default what fits ``FORECAST_STAGE_BYTES`` of
     (pinned) staging.  ``attrs``: more global attributes (``source_path`` among them, if ``main`` is to accept the
     file for a configuration).
+    ``climatology``: a :class:`climatology.Climatology` the model was fitted on the anomalies of (``time`` must then
+    be datetime64).  A time slab is expanded to fp32 (K12), the climatology of its times is put back in place (K18) and
+    the slab is packed as a field (K17's streaming pair): one fp32 slab is stored.  The range pass, when no packing is
+    given, runs on the restored fields.  The spread has no offset and is written as without a climatology.
 
     Returns ``{"packing": {name: Packing}, "filled": {name: int}, "saturated": {name: int}}`` over the file's
     variables: the values that were not finite and became ``_FillValue``, and those a given packing clamped."""
@@ -334,8 +338,25 @@ def write_forecast_slice(path: str, forecast, t, time, variables, levels, latitu
     def spread_of(t0, t1):
         return fc.spread_blocks(Ub, Dev[:, t0:t1], forecast.stds, dblock, delay=d, kern=kern)
 
+    if climatology is not None and not np.issubdtype(time.dtype, np.datetime64):
+        raise ValueError("write_forecast_slice: a climatology needs datetime64 time labels")
+    fbuf = []
+
+    def restored(t0, t1):
+        """The full fields of a slab: expand, then the climatology of its times in place (the buffers are reused)."""
+        o = [B[:t1 - t0] for B in fbuf] if fbuf else None
+        F = fc.expand_blocks(Ub, Ct[t0:t1], forecast.means, forecast.stds, dblock, out=o, delay=d, kern=kern)
+        if not fbuf:
+            fbuf.extend(F)
+        return climatology.restore_(F, time[t0:t1])
+
     # the packings: the range pass stores coefficients and extrema only (the spread is a field: slab by slab)
-    if packing is None:
+    if packing is None and climatology is not None:
+        state = None
+        for t0 in range(0, T, slab):
+            state = fc.range_field_blocks(restored(t0, min(T, t0 + slab)), groups, kern, nvar, state)
+        packing = [Packing.for_range(lo, hi) for lo, hi in state[0].cpu().tolist()]
+    elif packing is None:
         state = fc.range_blocks(Ub, Ct, forecast.means, forecast.stds, groups, dblock, d, kern, nvar)
         packing = [Packing.for_range(lo, hi) for lo, hi in state[0].cpu().tolist()]
     else:
@@ -382,8 +403,11 @@ def write_forecast_slice(path: str, forecast, t, time, variables, levels, latitu
             t1 = min(T, t0 + slab)
             n = t1 - t0
             out = [dslab[0, :n, a:b] for a, b in zip(starts[:-1], starts[1:])]
-            counts = fc.pack_blocks(Ub, Ct[t0:t1], forecast.means, forecast.stds, groups, packing, dblock, d, out, kern,
-                                    nvar, counts=counts)["counts"]
+            if climatology is not None:
+                counts = fc.pack_field_blocks(restored(t0, t1), groups, packing, out, kern, nvar, counts)["counts"]
+            else:
+                counts = fc.pack_blocks(Ub, Ct[t0:t1], forecast.means, forecast.stds, groups, packing, dblock, d, out,
+                                        kern, nvar, counts=counts)["counts"]
             if spread:
                 out = [dslab[1, :n, a:b] for a, b in zip(starts[:-1], starts[1:])]
                 scounts = fc.pack_field_blocks(spread_of(t0, t1), groups, spacking, out, kern, nvar, scounts)["counts"]

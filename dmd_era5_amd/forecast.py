@@ -23,7 +23,9 @@ csrc/verify.hip): :func:`area_weights`, :func:`verify_blocks` and ``DmdForecast.
 package: K17 (``HipKernels.expand_range`` / ``expand_pack`` / ``field_range`` / ``pack``, csrc/pack.hip) turns the
 forecast into the CF-packed int16 codes an ERA5 file stores, one ``scale_factor`` / ``add_offset`` per group of rows (a
 variable), where the field is formed and without storing it in fp32: :func:`pack_blocks`, :func:`pack_field_blocks` and
-``DmdForecast.pack``; ``era5_svd.write_forecast_slice`` writes them.
+``DmdForecast.pack``; ``era5_svd.write_forecast_slice`` writes them.  A model fitted on the anomalies against a slot
+climatology (K18, :mod:`climatology`) takes ``climatology=`` / ``times=`` in ``DmdForecast.fields`` and ``verify`` and in
+``write_forecast_slice``: the climatology is put back on the expanded fields, the analysis is anomalised for the scores.
 
 Layout as everywhere in the package (kernels.py): a column-major matrix is held as its row-major
 transpose -- U blocks are ``(k, rows)`` (``SvdResult.Ut``), coefficients ``Ct`` are ``(T, k)``,
@@ -807,6 +809,12 @@ def project_blocks(Ublocks, Xblocks, means=None, stds=None, delay: int = 1, comm
             "energy_total": float(e_total), "rows": int(rows)}
 
 
+def _climatology_args(climatology, times, who: str) -> None:
+    if (climatology is None) != (times is None):
+        raise ValueError(f"{who}: climatology and times go together (the datetime64 stamps say which slot a "
+                         "snapshot takes)")
+
+
 # ---------------------------------------------------------------------------
 # the bundle a user holds
 # ---------------------------------------------------------------------------
@@ -837,13 +845,21 @@ class DmdForecast:
             raise ValueError(f"DmdForecast: the DMD was fitted on {Ct.shape[1]} coordinates, U has {k} columns")
         return Ct.to(self.Ublocks[0].device), imag
 
-    def fields(self, t, delay_block: int | None = 0, out=None) -> list[torch.Tensor]:
+    def fields(self, t, delay_block: int | None = 0, out=None, climatology=None, times=None) -> list[torch.Tensor]:
         """The model's fields at the times ``t``: (len(t), rows) per block; ``delay_block=0`` (the
-        default) the physical rows, None all d * rows of the embedding."""
+        default) the physical rows, None all d * rows of the embedding.
+        ``climatology``: a :class:`climatology.Climatology` the model was fitted on the anomalies of; its fields at
+        ``times`` (the datetime64 stamps of ``t``) are put back in place (K18), so that full fields come out."""
         if self.delay == 1:
             delay_block = None
-        return expand_blocks(self.Ublocks, self.coefficients(t)[0], self.means, self.stds, delay_block, out=out,
-                             delay=self.delay, kern=self.kern)
+        _climatology_args(climatology, times, "DmdForecast.fields")
+        if climatology is not None and delay_block is None and self.delay > 1:
+            raise ValueError("DmdForecast.fields: a climatology lives on the physical rows; pass a delay_block")
+        res = expand_blocks(self.Ublocks, self.coefficients(t)[0], self.means, self.stds, delay_block, out=out,
+                            delay=self.delay, kern=self.kern)
+        if climatology is not None:
+            climatology.restore_(res, times)
+        return res
 
     def score(self, Xblocks, t, comm: Comm | None = None, want_rows: bool = False) -> dict:
         """:func:`score_blocks` of the model at the times ``t`` of the snapshots ``Xblocks`` (with a
@@ -854,11 +870,24 @@ class DmdForecast:
         return res
 
     def verify(self, Xblocks, t, weights=None, clims=None, groups=None, comm: Comm | None = None,
-               want_rows: bool = False, ensemble: bool = False, n_groups: int | None = None) -> dict:
+               want_rows: bool = False, ensemble: bool = False, n_groups: int | None = None, climatology=None,
+               times=None) -> dict:
         """:func:`verify_blocks` of the model at the times ``t`` against the snapshots ``Xblocks`` (with a delay d
         the blocks hold len(t) + d - 1 snapshots): weighted RMSE, bias and anomaly correlation per group.
         ``ensemble=True`` verifies the ensemble mean of a bagged fit (``Cbar`` of :meth:`ensemble_coefficients`).
-        ``imag_ratio`` is added to the result."""
+        ``climatology``: a :class:`climatology.Climatology` the model was fitted on the anomalies of.  The analysis
+        is anomalised against it into a scratch copy per block (``times``: the datetime64 stamps of the snapshots of
+        ``Xblocks``) and ``clims`` becomes zero: forecast and analysis are both anomalies against the time-dependent
+        climatology, which is what the anomaly correlation is defined with.  ``clims`` and ``climatology`` together
+        are refused.  ``imag_ratio`` is added to the result."""
+        _climatology_args(climatology, times, "DmdForecast.verify")
+        if climatology is not None:
+            if clims is not None:
+                raise ValueError("DmdForecast.verify: clims and climatology are two definitions of the anomaly; pass one")
+            Xblocks = list(Xblocks)
+            Xblocks = climatology.remove_(Xblocks, times, out=[torch.empty(tuple(X.shape), dtype=X.dtype, device=X.device)
+                                                               for X in Xblocks])
+            clims = [torch.zeros(int(X.shape[1]), dtype=torch.float32, device=X.device) for X in Xblocks]
         if ensemble:
             Ct, _, imag = self.ensemble_coefficients(t)
         else:

@@ -604,6 +604,90 @@ class HipKernels:
         _lib.check(rc, "dmdx_pack_f32_i16")
         return Qt, counts
 
+    # -- K18 ----------------------------------------------------------------
+    @staticmethod
+    def _clim_list(v: torch.Tensor, device, who: str, name: str, n: int | None = None) -> int:
+        """A device int32 vector of the slot lists (contiguous; ``n`` entries if given) -> its length."""
+        if (not isinstance(v, torch.Tensor) or v.dtype != torch.int32 or v.dim() != 1 or v.device != device
+                or not v.is_contiguous() or (n is not None and v.numel() != n)):
+            raise _lib.DmdxError(f"{who}: {name} must be a contiguous int32 vector"
+                                 f"{'' if n is None else f' of length {n}'} on {device}")
+        return int(v.numel())
+
+    @staticmethod
+    def _clim_field(t, S, m, device, who, name):
+        """An (S, m) fp32 climatology field with a row stride -> its leading dimension."""
+        mm, SS, ld = _check_mat(t, torch.float32, f"{who} {name}")
+        if (mm, SS) != (m, S) or t.device != device:
+            raise _lib.DmdxError(f"{who}: {name} must be ({S}, {m}) fp32 on {device}, got {tuple(t.shape)}")
+        return ld
+
+    def clim_mean(self, Xt: torch.Tensor, order: torch.Tensor, start: torch.Tensor,
+                  out: torch.Tensor | None = None) -> torch.Tensor:
+        """The slot means of the snapshots of a row block.  Xt: (T, m) fp32 (any row stride); ``order`` / ``start``:
+        device int32, the CSR list of :func:`climatology.slots_of` (slot s owns ``order[start[s]:start[s + 1]]``,
+        ``start`` has S + 1 entries) -> mean (S, m) fp32: the fp64 sum over the list, in its order, divided by the
+        number of entries inside [0, T) and rounded once; NaN for a slot without one.  ``out``: an (S, m) fp32 view
+        to write into (inner stride 1)."""
+        m, T, ldx = _check_mat(Xt, torch.float32, "clim_mean X")
+        n_order = self._clim_list(order, Xt.device, "clim_mean", "order")
+        S = self._clim_list(start, Xt.device, "clim_mean", "start") - 1
+        if S < 1:
+            raise _lib.DmdxError("clim_mean: start must hold S + 1 >= 2 offsets")
+        mean = out if out is not None else torch.empty((S, m), dtype=torch.float32, device=Xt.device)
+        ldc = self._clim_field(mean, S, m, Xt.device, "clim_mean", "out")
+        rc = self._timed("clim_mean", (m, T, S), lambda: self._lib.dmdx_clim_mean_f32(
+            _ptr(Xt), m, T, ldx, _ptr(order), n_order, _ptr(start), S, _ptr(mean), ldc, self._stream()
+        ))
+        _lib.check(rc, "dmdx_clim_mean_f32")
+        return mean
+
+    def clim_std(self, Xt: torch.Tensor, order: torch.Tensor, start: torch.Tensor, mean: torch.Tensor, ddof: int = 0,
+                 out: torch.Tensor | None = None) -> torch.Tensor:
+        """The slot standard deviations about ``mean`` ((S, m) fp32 of :meth:`clim_mean`): the fp64 sum of the
+        squared fp64 differences in the order of the list, divided by n_s - ddof, the correctly rounded root, one
+        rounding to fp32; NaN where n_s - ddof <= 0.  Operands and ``out`` as :meth:`clim_mean`."""
+        m, T, ldx = _check_mat(Xt, torch.float32, "clim_std X")
+        n_order = self._clim_list(order, Xt.device, "clim_std", "order")
+        S = self._clim_list(start, Xt.device, "clim_std", "start") - 1
+        if S < 1:
+            raise _lib.DmdxError("clim_std: start must hold S + 1 >= 2 offsets")
+        ldc = self._clim_field(mean, S, m, Xt.device, "clim_std", "mean")
+        sd = out if out is not None else torch.empty((S, m), dtype=torch.float32, device=Xt.device)
+        lds = self._clim_field(sd, S, m, Xt.device, "clim_std", "out")
+        rc = self._timed("clim_std", (m, T, S), lambda: self._lib.dmdx_clim_std_f32(
+            _ptr(Xt), m, T, ldx, _ptr(order), n_order, _ptr(start), S, _ptr(mean), ldc, int(ddof), _ptr(sd), lds,
+            self._stream()
+        ))
+        _lib.check(rc, "dmdx_clim_std_f32")
+        return sd
+
+    def clim_apply_(self, Xt: torch.Tensor, slot: torch.Tensor, mean: torch.Tensor, sd: torch.Tensor | None = None,
+                    restore: bool = False, out: torch.Tensor | None = None) -> torch.Tensor:
+        """Anomalies against a slot climatology, or back: snapshot t of Xt ((T, m) fp32) takes row ``slot[t]``
+        (device int32, T labels) of ``mean`` / ``sd`` ((S, m) fp32): ``(x - mean) [/ sd]``, or with ``restore``
+        ``x [* sd] + mean`` (two roundings).  A label outside 0 .. S - 1 (-1) leaves its snapshot as it is.  In
+        place by default; ``out``: a (T, m) fp32 view that does not overlap Xt.  -> the tensor written."""
+        m, T, ldx = _check_mat(Xt, torch.float32, "clim_apply X")
+        self._clim_list(slot, Xt.device, "clim_apply", "slot", T)
+        if mean.dim() != 2:
+            raise _lib.DmdxError(f"clim_apply: mean must be (S, {m}) fp32, got {tuple(mean.shape)}")
+        S = int(mean.shape[0])
+        ldc = self._clim_field(mean, S, m, Xt.device, "clim_apply", "mean")
+        lds = 0 if sd is None else self._clim_field(sd, S, m, Xt.device, "clim_apply", "sd")
+        Yt, ldy = Xt, ldx
+        if out is not None:
+            mo, To, ldy = _check_mat(out, torch.float32, "clim_apply out")
+            if (mo, To) != (m, T) or out.device != Xt.device:
+                raise _lib.DmdxError(f"clim_apply: out must be ({T}, {m}) fp32 on {Xt.device}, got {tuple(out.shape)}")
+            Yt = out
+        rc = self._timed("clim_apply", (m, T, S), lambda: self._lib.dmdx_clim_apply_f32(
+            _ptr(Xt), m, T, ldx, _ptr(slot), S, _ptr(mean), ldc, _ptr(sd), lds, int(bool(restore)), _ptr(Yt), ldy,
+            self._stream()
+        ))
+        _lib.check(rc, "dmdx_clim_apply_f32")
+        return Yt
+
     # -- K6 -----------------------------------------------------------------
     def delay_shift_sum(self, G64: torch.Tensor, d: int, want32: bool = False):
         """Gd[i, j] = sum_{k<d} G[i+k, j+k]."""

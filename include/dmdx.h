@@ -506,6 +506,49 @@ int dmdx_range_f32(const float* X, int64_t m, int64_t T, int64_t ldx, float* ran
 int dmdx_pack_f32_i16(const float* X, int64_t m, int64_t T, int64_t ldx, double scale_factor, double add_offset,
                       int16_t* Q, int64_t ldq, unsigned long long* counts, void* stream);
 
+/* ---- K18: slot climatology of the snapshots of one row block, and the anomalies against it -------------------------
+ * What everybody who fits a DMD to ERA5 removes first: the mean (and spread) of every grid point per class of the
+ * calendar -- an hour of the day, a (month, hour) pair, a day of the year -- where K5 (slice_tools.py:171-179) knows
+ * the mean over all of time only.  X is a row block as everywhere: T columns (snapshots) of m floats, ldx >= m.
+ *   order, start   (device int32) a CSR list: slot s < S owns the snapshot indices order[a .. b) with
+ *                  a = clamp(start[s], 0, n_order), b = clamp(start[s + 1], a, n_order); start holds S + 1 offsets.  A
+ *                  snapshot may sit in several slots (a window of days around a day of the year) or in none.  An entry
+ *                  outside [0, T) is skipped and NOT counted: the lists are data, a wrong one gives wrong means and never
+ *                  an access outside X.  n_s = the number of counted entries of slot s.
+ *   mean[s ldc + i] = fp32( acc / n_s ),  acc = +0.0 (fp64), acc += fp64(X[i, order[j]]) for j = a .. b - 1 IN THIS ORDER,
+ *                  whatever the launch geometry; an IEEE fp64 divide, then one rounding.  n_s == 0: the quiet NaN
+ *                  0x7FC00000.  mean is S x m (slot-major, ldc >= m).
+ *   sd[s lds + i]  = fp32( sqrt( acc / (n_s - ddof) ) ),  d = fp64(x) - fp64(mean[s ldc + i]), q = d d (rounded), acc += q in
+ *                  the same order; the root is correctly rounded.  ddof is 0 or 1; n_s - ddof <= 0: the same NaN.
+ *   slot           (device int32, T labels) the slot whose climatology snapshot t takes in apply.  A label outside [0, S)
+ *                  (-1 is the documented spelling) leaves the snapshot alone: its column of Y equals its column of X --
+ *                  copied when Y != X, not touched when Y == X.
+ *   apply, restore == 0:  y = fl(x - mean), then y = fl(y / sd) if sd is given (the correctly rounded fp32 divide of K13)
+ *   apply, restore != 0:  y = x, then y = fl(y sd) if sd is given, then y = fl(y + mean): two roundings, never an FMA
+ *                  Y == X with ldy == ldx runs in place; any other overlap of the two address ranges is refused.
+ * No workspace, no allocation, no synchronisation, no atomics: results are bit-wise reproducible.
+ * Memory: only the logical elements of X, mean, sd, order[0 .. n_order), start[0 .. S] and slot[0 .. T) are read, only the
+ * logical S x m elements of mean / sd and m x T elements of Y are written.  No alignment is asked for beyond that of the
+ * element types: a 16-byte aligned X with ldx % 4 == 0 is summed with 16-byte loads (4 rows per lane) when the launch
+ * still fills the chip that way, anything else one dword per lane; apply stores full chunks of Y as aligned 16-byte
+ * stores whatever Y and ldy are and reads X, mean and sd with 16-byte loads where their addresses allow it -- all with
+ * the same bits.
+ * Values: a non-finite X[i, t] reaches row i of the slots that list t (apply: element (i, t)) and nothing else; integer
+ * data with sums below 2^53 and exact quotients come out exactly; 2^e X gives 2^e mean and 2^e sd bit for bit, and in
+ * apply 2^e on X and mean scales Y by 2^e bit for bit (magnitudes as above).
+ * A refused call (DMDX_E_INVALID: a null X, order, start, mean, sd of dmdx_clim_std_f32, slot or Y; S < 1; ldx, ldc, ldy
+ * or -- with sd given -- lds < m; ddof outside 0 .. 1; a negative size; a size >= 2^31; X and Y overlapping other than in
+ * place) has written nothing.  m == 0 or T == 0 returns 0 after the checks; mean and std still fill their S x m output
+ * (with NaN) when T == 0 and m > 0. */
+int dmdx_clim_mean_f32(const float* X, int64_t m, int64_t T, int64_t ldx, const int32_t* order, int64_t n_order,
+                       const int32_t* start, int64_t S, float* mean, int64_t ldc, void* stream);
+int dmdx_clim_std_f32(const float* X, int64_t m, int64_t T, int64_t ldx, const int32_t* order, int64_t n_order,
+                      const int32_t* start, int64_t S, const float* mean, int64_t ldc, int ddof, float* sd, int64_t lds,
+                      void* stream);
+int dmdx_clim_apply_f32(const float* X, int64_t m, int64_t T, int64_t ldx, const int32_t* slot, int64_t S,
+                        const float* mean, int64_t ldc, const float* sd /* nullable */, int64_t lds, int restore,
+                        float* Y, int64_t ldy, void* stream);
+
 /* ---- upper triangle of a symmetric fp64 matrix <-> packed row by row ---------------------
  * packed[i (2n - i + 1) / 2 + (j - i)] = A[i][j], j >= i: what the Gram all-reduce of the
  * row-sharded path moves (n (n + 1) / 2 doubles instead of n^2).  unpack writes both triangles. */

@@ -1,0 +1,415 @@
+"""K18 (dmdx_clim_mean_f32 / dmdx_clim_std_f32 / dmdx_clim_apply_f32) through the ctypes table: values bit for bit
+against tests/clim_ref.py (the host definition; the kernel is never its own reference), the memory contract on
+operands from tests/memguard.py (NaN canaries in pads and guard zones) and every refusal.
+
+Comparisons are made on the integer view.  One class of values has no contractual bits: a NaN that ARITHMETIC
+produces (Inf - Inf, 0 / 0, anything with a NaN operand) carries the sign and payload of the machine that formed it
+-- x86 sets the sign of its default NaN, the device does not -- so where the reference holds a NaN the kernel must
+hold a NaN, and everywhere else the bits must be equal.  The NaN the contract itself names (a slot without a counted
+snapshot, n_s - ddof <= 0) is compared as the bit pattern 0x7FC00000.
+"""
+import numpy as np
+import pytest
+import torch
+
+import clim_ref as cr
+import memguard as mg
+
+pytestmark = pytest.mark.gpu
+
+F32 = torch.float32
+DEV = "cuda"
+E_INVALID = -1000
+QNAN = 0x7FC00000
+T0, S0 = 37, 5
+# (X, mean / sd, Y) base offsets in floats past a 16-byte boundary: every operand sees 0 .. 3, not in step
+OFFSETS = [(0, 0, 0), (1, 2, 3), (2, 3, 1), (3, 1, 2), (0, 1, 0), (1, 0, 0), (0, 0, 2), (3, 3, 3)]
+SHAPES = [(m, pad) for m in (1, 3, 1029, 2053) for pad in (0, 7)]
+
+
+@pytest.fixture(scope="module")
+def L():
+    from dmd_era5_amd.kernels import default_kernels
+
+    return default_kernels()._lib
+
+
+def _stream():
+    return torch.cuda.current_stream().cuda_stream
+
+
+def _bits(a):
+    return np.ascontiguousarray(a, dtype=np.float32).view(np.uint32)
+
+
+def _same(got, want, what=""):
+    got, want = np.asarray(got, dtype=np.float32), np.asarray(want, dtype=np.float32)
+    assert got.shape == want.shape, (what, got.shape, want.shape)
+    ok = (_bits(got) == _bits(want)) | (np.isnan(got) & np.isnan(want))
+    assert ok.all(), f"{what}: {int((~ok).sum())} of {ok.size} elements differ, first at {tuple(np.argwhere(~ok)[0])}"
+
+
+def _i32(a):
+    return torch.from_numpy(np.ascontiguousarray(a, dtype=np.int32)).to(DEV)
+
+
+def _lists():
+    """T = 37, S = 5.  Slot 0 is empty; slot 1 has one snapshot; slot 2 has 19 (more than the unroll of 8), out of
+    order, with an entry = T and an entry = -3 among them (skipped, not counted); slot 3 has 4, one of them (7) also
+    in slot 2; slot 4 has 8 and its end offset lies past n_order (clamped).  Snapshot 36 sits in no slot."""
+    s2 = [7, 0, 30, 12, T0, 3, 22, 9, 35, 1, 18, -3, 27, 4, 14, 33, 6, 20, 11, 25, 16]
+    s3 = [34, 7, 2, 29]
+    s4 = [8, 10, 13, 15, 17, 19, 21, 23]
+    order = np.array([5] + s2 + s3 + s4, dtype=np.int32)
+    start = np.array([0, 0, 1, 1 + len(s2), 1 + len(s2) + len(s3), order.shape[0] + 9], dtype=np.int32)
+    assert cr.counts(order, start, T0).tolist() == [0, 1, 19, 4, 8]
+    return order, start
+
+
+ORDER, START = _lists()
+SLOT = np.full(T0, -1, dtype=np.int32)
+for _s in range(S0):
+    for _t in cr.slot_lists(ORDER, START, _s, T0):
+        SLOT[_t] = _s                                            # (7 -> 3: its last slot)
+SLOT[36], SLOT[24], SLOT[26] = -1, S0, 2**31 - 1                 # three spellings of "no slot"
+SLOT[28] = 0                                                     # a label whose climatology is the NaN of an empty slot
+LEFT_ALONE = [t for t in range(T0) if not 0 <= SLOT[t] < S0]
+
+
+def _data(m, T=T0, seed=0):
+    rs = np.random.RandomState(seed + m)
+    return (250.0 + 30.0 * rs.standard_normal((m, T))).astype(np.float32)
+
+
+def _mean(L, gX, order, start, gM, T=None, n_order=None, S=None, m=None, ldx=None, ldc=None):
+    return L.dmdx_clim_mean_f32(gX.ptr, gX.rows if m is None else m, gX.cols if T is None else T,
+                                gX.ld if ldx is None else ldx, order.data_ptr(),
+                                order.numel() if n_order is None else n_order, start.data_ptr(),
+                                start.numel() - 1 if S is None else S, gM.ptr, gM.ld if ldc is None else ldc, _stream())
+
+
+def _std(L, gX, order, start, gM, ddof, gS, lds=None):
+    return L.dmdx_clim_std_f32(gX.ptr, gX.rows, gX.cols, gX.ld, order.data_ptr(), order.numel(), start.data_ptr(),
+                               start.numel() - 1, gM.ptr, gM.ld, ddof, gS.ptr, gS.ld if lds is None else lds, _stream())
+
+
+def _apply(L, gX, slot, gM, gS, restore, gY, S=S0):
+    return L.dmdx_clim_apply_f32(gX.ptr, gX.rows, gX.cols, gX.ld, slot.data_ptr(), S, gM.ptr, gM.ld,
+                                 None if gS is None else gS.ptr, 0 if gS is None else gS.ld, int(restore), gY.ptr, gY.ld,
+                                 _stream())
+
+
+def _field(m, S, pad, off, host=None):
+    """An (S, m) climatology field: S columns of m floats, ld = m + pad; .logical().T is (S, m)."""
+    g = mg.Guarded(m, S, m + pad, F32, off, DEV)
+    if host is not None:
+        g.fill(np.ascontiguousarray(host.T)).snapshot()
+    return g
+
+
+def _unwritten(g):
+    return bool((g.ibuf == g.canary).all())
+
+
+# ---------------------------------------------------------------- mean / std
+@pytest.mark.parametrize("m,pad", SHAPES)
+def test_mean_and_std_bit_equal_on_every_layout(L, m, pad):
+    X = _data(m)
+    order, start = _i32(ORDER), _i32(START)
+    mu = cr.mean(X, ORDER, START)
+    sds = {ddof: cr.std(X, ORDER, START, mu, ddof) for ddof in (0, 1)}
+    assert np.isfinite(mu[1:]).all() and np.isfinite(sds[1][2:]).all()
+    first = None
+    for ox, om, oy in OFFSETS:
+        gX = mg.Guarded(m, T0, m + pad, F32, ox, DEV).fill(X).snapshot()
+        gM = _field(m, S0, pad, om)
+        assert _mean(L, gX, order, start, gM) == 0, L.dmdx_last_error()
+        got = gM.logical().T
+        gM.check_fully_written("mean")
+        gM.check_untouched("mean")
+        _same(got, mu, f"mean offsets {(ox, om)}")
+        assert (_bits(got[0]) == QNAN).all()                     # the empty slot
+        gM.snapshot()
+        for ddof in (0, 1):
+            gS = _field(m, S0, pad, oy)
+            assert _std(L, gX, order, start, gM, ddof, gS) == 0, L.dmdx_last_error()
+            sd = gS.logical().T
+            gS.check_fully_written("sd")
+            gS.check_untouched("sd")
+            _same(sd, sds[ddof], f"sd ddof {ddof} offsets {(ox, om, oy)}")
+            assert (_bits(sd[0]) == QNAN).all()
+            if ddof == 1:
+                assert (_bits(sd[1]) == QNAN).all()              # n_s = 1 with ddof = 1
+            else:
+                assert (sd[1] == 0).all()
+        for g in (gX, gM):
+            g.check_untouched("input")
+            g.check_unchanged("input")
+        first = got if first is None else first
+        assert np.array_equal(_bits(got), _bits(first))          # aligned and dword paths: the same bits
+
+
+def test_more_slots_than_grid_rows(L):
+    """S = 70 000 > 65 535: grid.y is strided; m = 8, T = 4."""
+    S, m, T = 70000, 8, 4
+    X = _data(m, T, seed=3)
+    cnt = 1 + (np.arange(S) % 3 == 0)
+    start = np.concatenate([[0], np.cumsum(cnt)]).astype(np.int32)
+    order = np.empty(start[-1], dtype=np.int32)
+    order[start[:-1]] = np.arange(S) % 4
+    two = np.nonzero(cnt == 2)[0]
+    order[start[two] + 1] = (two + 1) % 4
+    gX = mg.Guarded(m, T, m, F32, 0, DEV).fill(X).snapshot()
+    gM = _field(m, S, 0, 0)
+    assert _mean(L, gX, _i32(order), _i32(start), gM) == 0, L.dmdx_last_error()
+    gM.check_fully_written("mean")
+    gM.check_untouched("mean")
+    # the definition, vectorised over the slots: +0.0 + x0 [+ x1], an fp64 divide, one rounding
+    acc = X.astype(np.float64).T[order[start[:-1]]]
+    acc[two] += X.astype(np.float64).T[order[start[two] + 1]]
+    want = (acc / cnt[:, None].astype(np.float64)).astype(np.float32)
+    for s in (0, 1, 2, 3, 65534, 65535, 65536, 69999):           # ... which is clim_ref's loop, slot by slot
+        ts = np.array(cr.slot_lists(order, start, s, T), dtype=np.int32)
+        assert np.array_equal(_bits(cr.mean(X, ts, [0, len(ts)])[0]), _bits(want[s]))
+    assert np.array_equal(_bits(gM.logical().T), _bits(want))
+
+
+def test_one_row_and_four_row_geometry_give_equal_bits(L):
+    """m = 1029, T = 2048: with S = 1 a lane owns one row, with S = 2048 four (and the last quad is ragged); slot 0
+    lists all 2048 snapshots in the same (shuffled) order both times."""
+    m, T = 1029, 2048
+    X = _data(m, T, seed=5)
+    rs = np.random.RandomState(9)
+    perm = rs.permutation(T).astype(np.int32)
+    gX = mg.Guarded(m, T, m + 3, F32, 0, DEV).fill(X).snapshot()          # 16-byte aligned, ld % 4 == 0
+    o1, s1 = perm, np.array([0, T], dtype=np.int32)
+    oN = np.concatenate([perm, np.arange(1, 2048, dtype=np.int32)])
+    sN = np.concatenate([[0], T + np.arange(2048)]).astype(np.int32)
+    want = cr.mean(X, o1, s1)
+    want_sd = cr.std(X, o1, s1, want, 1)
+    res = {}
+    for name, (o, s, S) in {"one": (o1, s1, 1), "four": (oN, sN, 2048)}.items():
+        for om in (0, 1):                                        # aligned and dword stores of the result
+            gM, gS = _field(m, S, 3 - om, om), _field(m, S, 0, om)
+            assert _mean(L, gX, _i32(o), _i32(s), gM) == 0, L.dmdx_last_error()
+            assert _std(L, gX, _i32(o), _i32(s), gM, 1, gS) == 0, L.dmdx_last_error()
+            for g in (gM, gS):
+                g.check_fully_written(name)
+                g.check_untouched(name)
+            res[name, om] = (gM.logical().T, gS.logical().T)
+    for key, (mu, sd) in res.items():
+        assert np.array_equal(_bits(mu[0]), _bits(want[0])), key
+        assert np.array_equal(_bits(sd[0]), _bits(want_sd[0])), key
+    mu, sd = res["four", 0]
+    assert np.array_equal(_bits(mu[1:]), _bits(X.T[1:2048]))      # a slot of one snapshot: the snapshot itself
+    assert (_bits(sd[1:]) == QNAN).all()
+    assert np.array_equal(_bits(mu), _bits(res["four", 1][0]))
+    gX.check_untouched("X")
+    gX.check_unchanged("X")
+
+
+def _run_stats(L, X, ddof=0, order=ORDER, start=START):
+    m, T = X.shape
+    S = len(start) - 1
+    gX = mg.Guarded(m, T, m, F32, 0, DEV).fill(X)
+    gM, gS = _field(m, S, 0, 0), _field(m, S, 0, 0)
+    assert _mean(L, gX, _i32(order), _i32(start), gM) == 0, L.dmdx_last_error()
+    assert _std(L, gX, _i32(order), _i32(start), gM, ddof, gS) == 0, L.dmdx_last_error()
+    return gM.logical().T, gS.logical().T
+
+
+def test_values_integers_scaling_and_non_finite(L):
+    m = 37
+    rs = np.random.RandomState(2)
+    n = cr.counts(ORDER, START, T0)
+    # integers, multiples of lcm(1, 19, 4, 8) = 152: every sum and every quotient is an exact integer
+    Xi = (152 * rs.randint(-40, 41, (m, T0))).astype(np.float32)
+    mu, sd = _run_stats(L, Xi)
+    for s in range(1, S0):
+        ts = cr.slot_lists(ORDER, START, s, T0)
+        exact = Xi[:, ts].astype(np.int64).sum(axis=1) // n[s]
+        assert np.array_equal(mu[s].astype(np.int64), exact) and np.array_equal(mu[s], exact.astype(np.float32))
+        ssq = ((Xi[:, ts].astype(np.int64) - exact[:, None]) ** 2).sum(axis=1)
+        assert np.array_equal(_bits(sd[s]), _bits(np.sqrt(ssq.astype(np.float64) / n[s]).astype(np.float32)))
+    _same(mu, cr.mean(Xi, ORDER, START), "integer mean")
+    # 2^e X gives 2^e mean and 2^e sd, bit for bit
+    X = _data(m, seed=11)
+    mu, sd = _run_stats(L, X, 1)
+    for e in (5, -7):
+        mu2, sd2 = _run_stats(L, (X * np.float32(2.0 ** e)).astype(np.float32), 1)
+        _same(mu2, mu * np.float32(2.0 ** e), f"mean 2^{e}")
+        _same(sd2, sd * np.float32(2.0 ** e), f"sd 2^{e}")
+        assert (_bits(mu2[0]) == QNAN).all() and (_bits(sd2[:2]) == QNAN).all()
+    # a NaN at (3, 7) -- snapshot 7 is listed by slots 2 and 3 -- and an Inf at (20, 5) -- slot 1 only --
+    # and a NaN at (9, 36), a snapshot no slot lists
+    Xn = X.copy()
+    Xn[3, 7], Xn[20, 5], Xn[9, 36] = np.nan, np.inf, np.nan
+    mun, sdn = _run_stats(L, Xn, 1)
+    want_mu = cr.mean(Xn, ORDER, START)
+    _same(mun, want_mu, "mean with NaN / Inf")
+    _same(sdn, cr.std(Xn, ORDER, START, want_mu, 1), "sd with NaN / Inf")
+    hit = np.zeros((S0, m), dtype=bool)
+    hit[2, 3] = hit[3, 3] = hit[1, 20] = True
+    assert np.isnan(mun[2, 3]) and np.isnan(mun[3, 3]) and mun[1, 20] == np.inf
+    assert np.array_equal(_bits(mun)[~hit], _bits(mu)[~hit]) and np.array_equal(_bits(sdn)[~hit], _bits(sd)[~hit])
+    assert np.isnan(sdn[2, 3]) and np.isnan(sdn[3, 3]) and np.isnan(sdn[1, 20])
+
+
+# ---------------------------------------------------------------- apply
+@pytest.mark.parametrize("m,pad", SHAPES)
+def test_apply_in_place_and_out_of_place(L, m, pad):
+    X = _data(m, seed=21)
+    mu = cr.mean(X, ORDER, START)                                # row 0 is NaN: the label 0 of snapshot 28 takes it
+    sd = cr.std(X, ORDER, START, mu, 0)
+    sd[3, m // 2] = 0.0                                          # a zero standard deviation: numpy's fp32 x / 0
+    slot = _i32(SLOT)
+    for (ox, om, oy), with_sd, restore in zip(OFFSETS, [False, True] * 4, [False, False, True, True] * 2):
+        want = cr.apply(X, SLOT, mu, sd if with_sd else None, restore)
+        assert np.array_equal(_bits(want[:, LEFT_ALONE]), _bits(X[:, LEFT_ALONE]))
+        gM = _field(m, S0, pad, om, mu)
+        gS = _field(m, S0, pad, (om + 1) % 4, sd) if with_sd else None
+        # out of place: every logical element of Y is written, the snapshots without a slot are copies
+        gX = mg.Guarded(m, T0, m + pad, F32, ox, DEV).fill(X).snapshot()
+        gY = mg.Guarded(m, T0, m + (0 if pad else 7), F32, oy, DEV)
+        assert _apply(L, gX, slot, gM, gS, restore, gY) == 0, L.dmdx_last_error()
+        got = gY.logical()
+        gY.check_untouched("Y")
+        _same(got, want, f"apply out of place {(ox, om, oy, with_sd, restore)}")
+        assert np.array_equal(_bits(got[:, LEFT_ALONE]), _bits(X[:, LEFT_ALONE]))
+        gX.check_untouched("X")
+        gX.check_unchanged("X")
+        # in place: the snapshots without a slot are not touched
+        gZ = mg.Guarded(m, T0, m + pad, F32, oy, DEV).fill(X)
+        assert _apply(L, gZ, slot, gM, gS, restore, gZ) == 0, L.dmdx_last_error()
+        inp = gZ.logical()
+        gZ.check_untouched("X in place")
+        assert np.array_equal(_bits(inp), _bits(got))
+        for g in (gM, gS):
+            if g is not None:
+                g.check_untouched("climatology")
+                g.check_unchanged("climatology")
+
+
+def test_apply_values_round_trip_scaling_overlap(L):
+    m = 41
+    X = _data(m, seed=31)
+    mu = cr.mean(X, ORDER, START)
+    sd = cr.std(X, ORDER, START, mu, 0)
+    slot = _i32(SLOT)
+    gM, gS = _field(m, S0, 0, 0, mu), _field(m, S0, 0, 0, sd)
+    # restore_(remove_(X)) is the numpy composition (two roundings on the way back), not X
+    gX = mg.Guarded(m, T0, m, F32, 0, DEV).fill(X)
+    assert _apply(L, gX, slot, gM, gS, 0, gX) == 0 and _apply(L, gX, slot, gM, gS, 1, gX) == 0
+    back = gX.logical()
+    want = cr.apply(cr.apply(X, SLOT, mu, sd), SLOT, mu, sd, restore=True)
+    _same(back, want, "restore(remove(X))")
+    live = [t for t in range(T0) if 2 <= SLOT[t] < S0]           # (slot 1 has one snapshot: sd = 0, 0 / 0)
+    # against X itself only a bound holds -- four roundings of values below 400: 4 * 2^-24 * 400 = 9.6e-5
+    assert np.abs(back[:, live].astype(np.float64) - X[:, live]).max() <= 1e-4
+    # 2^e on X and mean scales Y by 2^e bit for bit (sd unscaled)
+    for e in (4, -6):
+        f = np.float32(2.0 ** e)
+        gX2 = mg.Guarded(m, T0, m, F32, 1, DEV).fill(X * f)
+        gM2 = _field(m, S0, 0, 0, mu * f)
+        gY, gY2 = mg.Guarded(m, T0, m, F32, 0, DEV), mg.Guarded(m, T0, m, F32, 0, DEV)
+        gX1 = mg.Guarded(m, T0, m, F32, 0, DEV).fill(X)
+        assert _apply(L, gX1, slot, gM, gS, 0, gY) == 0 and _apply(L, gX2, slot, gM2, gS, 0, gY2) == 0
+        _same(gY2.logical(), gY.logical() * f, f"apply 2^{e}")
+    # a partial overlap of X and Y is refused and nothing is written; so is Y == X with another ldy
+    g = mg.Guarded(m, 2 * T0, m, F32, 0, DEV).fill(np.concatenate([X, X], axis=1)).snapshot()
+    st = _stream()
+    for yptr, ldy in ((g.ptr + 16, m), (g.ptr + 4 * (T0 * m - 5), m), (g.ptr, m + 1), (g.ptr - 8, m)):
+        rc = L.dmdx_clim_apply_f32(g.ptr, m, T0, m, slot.data_ptr(), S0, gM.ptr, m, None, 0, 0, yptr, ldy, st)
+        assert rc == E_INVALID and b"overlap" in L.dmdx_last_error()
+    rc = L.dmdx_clim_apply_f32(g.ptr, m, T0, m, slot.data_ptr(), S0, gM.ptr, m, None, 0, 0, g.ptr + 4 * T0 * m, m, st)
+    assert rc == 0                                                # the second half: disjoint, runs
+    g.check_untouched("X | Y")
+    both = g.logical()
+    assert np.array_equal(_bits(both[:, :T0]), _bits(X))
+    _same(both[:, T0:], cr.apply(X, SLOT, mu), "apply into the neighbouring columns")
+
+
+# ---------------------------------------------------------------- refusals and empty shapes
+def test_refusals_write_nothing(L):
+    m = 12
+    X = _data(m)
+    gX = mg.Guarded(m, T0, m + 2, F32, 0, DEV).fill(X).snapshot()
+    order, start, slot = _i32(ORDER), _i32(START), _i32(SLOT)
+    mu = cr.mean(X, ORDER, START)
+    gMin = _field(m, S0, 2, 0, mu)
+    gM, gS, gY = _field(m, S0, 2, 0), _field(m, S0, 2, 0), mg.Guarded(m, T0, m + 2, F32, 0, DEV)
+    st, n, big = _stream(), order.numel(), 2**31
+    xp, op, sp, lp = gX.ptr, order.data_ptr(), start.data_ptr(), slot.data_ptr()
+    ld = m + 2
+    mean_calls = [                                               # (X, m, T, ldx, order, n_order, start, S, mean, ldc)
+        (None, m, T0, ld, op, n, sp, S0, gM.ptr, ld), (xp, m, T0, ld, None, n, sp, S0, gM.ptr, ld),
+        (xp, m, T0, ld, op, n, None, S0, gM.ptr, ld), (xp, m, T0, ld, op, n, sp, S0, None, ld),
+        (xp, m, T0, ld, op, n, sp, 0, gM.ptr, ld), (xp, m, T0, ld, op, n, sp, -1, gM.ptr, ld),
+        (xp, m, T0, m - 1, op, n, sp, S0, gM.ptr, ld), (xp, m, T0, ld, op, n, sp, S0, gM.ptr, m - 1),
+        (xp, m, T0, ld, op, -1, sp, S0, gM.ptr, ld), (xp, m, T0, ld, op, big, sp, S0, gM.ptr, ld),
+        (xp, big, T0, big, op, n, sp, S0, gM.ptr, big), (xp, m, big, ld, op, n, sp, S0, gM.ptr, ld),
+        (xp, m, T0, big, op, n, sp, S0, gM.ptr, ld), (xp, m, T0, ld, op, n, sp, S0, gM.ptr, big),
+        (xp, m, T0, ld, op, n, sp, big, gM.ptr, ld), (xp, -1, T0, ld, op, n, sp, S0, gM.ptr, ld),
+        (xp, m, -1, ld, op, n, sp, S0, gM.ptr, ld),
+    ]
+    for a in mean_calls:
+        assert L.dmdx_clim_mean_f32(*a, st) == E_INVALID, a
+        assert L.dmdx_last_error()
+        assert L.dmdx_clim_std_f32(*a[:8], gMin.ptr if a[8] else None, a[9], 0, gS.ptr, ld, st) == E_INVALID, a
+    for ddof, sd_ptr, lds in ((2, gS.ptr, ld), (-1, gS.ptr, ld), (0, None, ld), (0, gS.ptr, m - 1), (0, gS.ptr, big)):
+        assert L.dmdx_clim_std_f32(xp, m, T0, ld, op, n, sp, S0, gMin.ptr, ld, ddof, sd_ptr, lds, st) == E_INVALID
+    good = dict(X=xp, m=m, T=T0, ldx=ld, slot=lp, S=S0, mean=gMin.ptr, ldc=ld, sd=None, lds=0, restore=0, Y=gY.ptr, ldy=ld)
+    bad = [dict(X=None), dict(slot=None), dict(mean=None), dict(Y=None), dict(S=0), dict(ldx=m - 1), dict(ldc=m - 1),
+           dict(ldy=m - 1), dict(sd=gMin.ptr, lds=m - 1), dict(m=big, ldx=big, ldc=big, ldy=big), dict(T=big),
+           dict(ldx=big), dict(ldc=big), dict(ldy=big), dict(sd=gMin.ptr, lds=big), dict(S=big), dict(m=-1), dict(T=-1)]
+    for change in bad:
+        assert L.dmdx_clim_apply_f32(*{**good, **change}.values(), st) == E_INVALID, change
+    # sizes of zero: the checks, then nothing to do -- but mean / std of no snapshots are S x m NaN
+    assert L.dmdx_clim_mean_f32(xp, 0, T0, ld, op, n, sp, S0, gM.ptr, ld, st) == 0
+    assert L.dmdx_clim_std_f32(xp, 0, T0, ld, op, n, sp, S0, gMin.ptr, ld, 0, gS.ptr, ld, st) == 0
+    assert L.dmdx_clim_apply_f32(*{**good, "m": 0}.values(), st) == 0
+    assert L.dmdx_clim_apply_f32(*{**good, "T": 0}.values(), st) == 0
+    torch.cuda.synchronize()
+    assert _unwritten(gM) and _unwritten(gS) and _unwritten(gY)
+    for g in (gX, gMin):
+        g.check_untouched("input")
+        g.check_unchanged("input")
+    assert L.dmdx_clim_mean_f32(xp, m, 0, ld, op, n, sp, S0, gM.ptr, ld, st) == 0
+    assert L.dmdx_clim_std_f32(xp, m, 0, ld, op, n, sp, S0, gMin.ptr, ld, 0, gS.ptr, ld, st) == 0
+    for g in (gM, gS):
+        g.check_untouched("T = 0")
+        assert (_bits(g.logical()) == QNAN).all()
+
+
+def test_hip_kernels_wrappers(L):
+    """HipKernels.clim_mean / clim_std / clim_apply_ on strided torch views, and their argument checks."""
+    from dmd_era5_amd import _lib
+    from dmd_era5_amd.kernels import default_kernels
+
+    kern = default_kernels()
+    m = 50
+    X = _data(m, seed=41)
+    buf = torch.zeros((T0, m + 6), dtype=F32, device=DEV)
+    Xt = buf[:, 1:1 + m]
+    Xt.copy_(torch.from_numpy(np.ascontiguousarray(X.T)))
+    order, start, slot = _i32(ORDER), _i32(START), _i32(SLOT)
+    mean = kern.clim_mean(Xt, order, start)
+    sd = kern.clim_std(Xt, order, start, mean, ddof=1)
+    mu_ref = cr.mean(X, ORDER, START)
+    _same(mean.cpu().numpy(), mu_ref, "clim_mean")
+    _same(sd.cpu().numpy(), cr.std(X, ORDER, START, mu_ref, 1), "clim_std")
+    wide = torch.full((S0, m + 3), 9.0, dtype=F32, device=DEV)
+    assert kern.clim_mean(Xt, order, start, out=wide[:, :m]).data_ptr() == wide.data_ptr()
+    _same(wide[:, :m].cpu().numpy(), mu_ref, "clim_mean out=")
+    assert bool((wide[:, m:] == 9.0).all())
+    Y = kern.clim_apply_(Xt, slot, mean, out=torch.empty((T0, m), dtype=F32, device=DEV))
+    _same(Y.cpu().numpy().T, cr.apply(X, SLOT, mu_ref), "clim_apply_ out=")
+    assert kern.clim_apply_(Xt, slot, mean, sd, restore=False) is Xt
+    _same(Xt.cpu().numpy().T, cr.apply(X, SLOT, mu_ref, sd.cpu().numpy()), "clim_apply_ in place")
+    assert bool((buf[:, 0] == 0).all()) and bool((buf[:, 1 + m:] == 0).all())
+    for bad in (lambda: kern.clim_mean(Xt, order.long(), start), lambda: kern.clim_mean(Xt.double(), order, start),
+                lambda: kern.clim_apply_(Xt, slot[:-1], mean), lambda: kern.clim_apply_(Xt, slot, mean[:, :-1]),
+                lambda: kern.clim_std(Xt, order, start, mean[:-1]), lambda: kern.clim_mean(Xt.cpu(), order, start),
+                lambda: kern.clim_apply_(Xt, slot, mean, out=Xt[:, 1:])):
+        with pytest.raises(_lib.DmdxError):
+            bad()
