@@ -27,6 +27,7 @@ from __future__ import annotations
 import logging
 import os
 import sys
+from dataclasses import dataclass
 from datetime import datetime
 
 import numpy as np
@@ -657,6 +658,108 @@ def _upload_packed_i16(lazy, level_idx, take, step, band, ranges, blocks, device
     return nbytes, nfill
 
 
+def _scatter_slab(dev, j0, j1, ranges, blocks) -> None:
+    """Rows j0:j1 of every row block from a (j1 - j0, m_v) device slab."""
+    for (a, b), Xb in zip(ranges, blocks):
+        Xb[j0:j1, : b - a].copy_(dev[:, a:b])
+
+
+def _upload_direct_f32(lazy, take, band, rows, ranges, blocks, device, count_fills):
+    """The direct route of ``_upload_variable``: an fp32 file-backed variable, contiguous snapshots, every
+    level.  A slab of ``rows`` snapshots is read straight into one of two pinned staging buffers and copied to
+    the device asynchronously, so the next read overlaps the previous host->device copy.
+    (A float32 variable that only declares a fill value -- xarray writes _FillValue = NaN on every float
+    variable -- takes this route too: the fill value is replaced and the NaN counted on the device, behind the
+    upload: no host pass, no host sync.)
+    -> (bytes moved, device NaN counter or None)."""
+    import torch
+
+    n, (i0, i1) = len(take), band
+    nlev, nlat_all, nlon = lazy.shape[1:]
+    nlat = i1 - i0
+    m_v = nlev * nlat * nlon
+    whole = (i0, i1) == (0, nlat_all)
+    on_gpu = device.type == "cuda"
+    # (a NaN fill value is already what it should become)
+    fills = [np.float32(f) for f in lazy.packing.fills if f == f] if count_fills and lazy.packing is not None else []
+    pinned = [torch.empty((rows, m_v), dtype=torch.float32) for _ in range(2)]
+    if on_gpu:
+        pinned = [b.pin_memory() for b in pinned]
+    events = [None, None]
+    nan_count = torch.zeros((), dtype=torch.int64, device=device) if count_fills else None
+    nbytes = 0
+    for it, j0 in enumerate(range(0, n, rows)):
+        j1 = min(n, j0 + rows)
+        buf = pinned[it & 1]
+        if events[it & 1] is not None:
+            events[it & 1].synchronize()            # the copy that last used this buffer is done
+        view = buf[: j1 - j0].numpy().reshape((j1 - j0, nlev, nlat, nlon))
+        if whole:
+            lazy.read_slab(int(take[j0]), int(take[j1 - 1]) + 1, view)
+        else:
+            lazy.read_box((int(take[j0]), 0, i0, 0), (j1 - j0, nlev, nlat, nlon), view)
+        dev = buf[: j1 - j0].to(device, non_blocking=True)
+        nbytes += (j1 - j0) * m_v * 4
+        if count_fills:
+            for f in fills:
+                dev.masked_fill_(dev == f, float("nan"))
+            nan_count += torch.isnan(dev).sum()
+        _scatter_slab(dev, j0, j1, ranges, blocks)
+        if on_gpu:
+            events[it & 1] = torch.cuda.Event()
+            events[it & 1].record()
+        del dev
+    return nbytes, nan_count
+
+
+def _upload_host_decode(da, level_idx, take, band, rows, ranges, blocks, device, count_fills):
+    """The host route of ``_upload_variable``: whatever the other two do not take (an in-memory variable, a
+    level subset, an irregular resampling, packed values the kernel's limits exclude).  A slab of ``rows``
+    snapshots is read or sliced, gathered, decoded (``labeled.Packing.decode``) and made contiguous on the
+    host, then uploaded.  -> (bytes moved, device NaN counter or None)."""
+    import torch
+
+    lazy, n, (i0, i1) = da.lazy, len(take), band
+    nlev_all, nlat_all, nlon = da.shape[1:]
+    nlat = i1 - i0
+    m_v = len(level_idx) * nlat * nlon
+    whole = (i0, i1) == (0, nlat_all)
+    host = None if lazy is not None else da.values
+    packing = lazy.packing if lazy is not None else None
+    contiguous = np.array_equal(take, np.arange(take[0], take[0] + n)) if n else True
+    all_levels = len(level_idx) == nlev_all and np.array_equal(level_idx, np.arange(nlev_all))
+
+    def read(lo, hi):
+        if lazy is None:
+            return host[lo:hi] if whole else host[lo:hi, :, i0:i1]
+        if whole:
+            return lazy.read_slab(lo, hi)
+        return lazy.read_box((lo, 0, i0, 0), (hi - lo, nlev_all, nlat, nlon))
+
+    nan_count = torch.zeros((), dtype=torch.int64, device=device) if count_fills else None
+    nbytes = 0
+    for j0 in range(0, n, rows):
+        j1 = min(n, j0 + rows)
+        if contiguous:
+            slab = read(int(take[j0]), int(take[j1 - 1]) + 1)
+        else:  # resampled: gather the selected snapshots
+            idx = take[j0:j1]
+            lo = int(idx.min())
+            slab = read(lo, int(idx.max()) + 1)[idx - lo]
+        if not all_levels:
+            slab = slab[:, level_idx]
+        if packing is not None:                 # file values -> physical ones
+            slab = packing.decode(slab)
+        slab = np.ascontiguousarray(slab.reshape(j1 - j0, m_v), dtype=np.float32)
+        nbytes += slab.nbytes
+        dev = torch.from_numpy(slab).to(device, non_blocking=False)
+        if count_fills:
+            nan_count += torch.isnan(dev).sum()
+        _scatter_slab(dev, j0, j1, ranges, blocks)
+        del dev
+    return nbytes, nan_count
+
+
 def _upload_variable(da: DataArray, level_idx, take, device, kern, center, scale, stats, band=None, pad4=False):
     """One variable (time, level, lat, lon) -> centred/scaled row blocks (time, rows) in HBM.
 
@@ -668,7 +771,9 @@ def _upload_variable(da: DataArray, level_idx, take, device, kern, center, scale
     caller drops them (returned widths are the padded ones, ``m_v`` the true count).
 
     Streams time slabs: file/host -> pinned staging -> device slab -> strided device copy
-    into each row block.  Row order inside the variable: level slowest, longitude fastest.
+    into each row block, by one of three routes (``_upload_packed_i16``, ``_upload_direct_f32``,
+    ``_upload_host_decode``); K5 centres / scales every block behind the last slab.
+    Row order inside the variable: level slowest, longitude fastest.
     ``band`` = (i0, i1): only these latitude rows (this rank's shard); file-backed variables
     are then read as hyperslabs, so a rank touches only its own bytes of the file.
 
@@ -677,7 +782,7 @@ def _upload_variable(da: DataArray, level_idx, take, device, kern, center, scale
     file, over PCIe and in the staging) and one K14 launch per row block unpacks and gathers the
     selected levels / latitude band; a regular resampling is compacted while it is read -- so
     neither ``all_levels`` nor a contiguous ``take`` is asked for.  Every other packed case is
-    decoded on the host (same arithmetic) in the slow branch.  A variable that declares fill codes
+    decoded on the host (same arithmetic) by the host route.  A variable that declares fill codes
     appends (name, number of them in the selection) to ``stats["fills"]``."""
     import torch
 
@@ -688,94 +793,35 @@ def _upload_variable(da: DataArray, level_idx, take, device, kern, center, scale
         raise ValueError(f"variable {da.name}: expected dims (time, level, latitude, longitude), got {da.dims}")
     n = len(take)
     nlev_all, nlat_all, nlon = da.shape[1:]
-    i0, i1 = band if band is not None else (0, nlat_all)
-    nlat = i1 - i0
-    whole = (i0, i1) == (0, nlat_all)
+    band = band if band is not None else (0, nlat_all)
+    nlat = band[1] - band[0]
     m_v = len(level_idx) * nlat * nlon
     ranges = dsvd.split_rows(m_v)
     blocks = [torch.zeros((n, b - a + (-(b - a)) % 4), dtype=torch.float32, device=device) if pad4 and (b - a) % 4
               else torch.empty((n, b - a), dtype=torch.float32, device=device) for a, b in ranges]
+    # the route
     lazy = da.lazy
-    host = None if lazy is not None else da.values
-    rows = max(1, SLAB_BYTES // max(1, nlev_all * max(nlat, 1) * nlon * 4))
+    packing = lazy.packing if lazy is not None else None
     contiguous = np.array_equal(take, np.arange(take[0], take[0] + n)) if n else True
     all_levels = len(level_idx) == nlev_all and np.array_equal(level_idx, np.arange(nlev_all))
-    nbytes = 0
-    # fast path: fp32 file-backed variable, contiguous snapshots, every level: the slab is read
-    # straight into one of two pinned staging buffers and copied to the device asynchronously,
-    # so the next read overlaps the previous host->device copy
-    packing = lazy.packing if lazy is not None else None
-    # (a float32 variable that only declares a fill value -- xarray writes _FillValue = NaN on every float
-    # variable -- keeps this path: the fill value is replaced and the NaN counted on the device)
     direct = lazy is not None and contiguous and all_levels and lazy.dtype == np.float32 and \
         (packing is None or not packing.affine)
-    on_gpu = device.type == "cuda"
     step = _take_step(take)
     declared = bool(packing.fills) if packing is not None else any(
         k in getattr(da, "encoding", {}) for k in ("_FillValue", "missing_value"))
     # packed bytes travel and K14 unpacks: what the kernel's own limits allow (anything else is decoded on the host)
-    unpacked = (packing is not None and lazy.dtype == np.int16 and on_gpu and hasattr(kern, "unpack_i16_")
+    unpacked = (packing is not None and lazy.dtype == np.int16 and device.type == "cuda" and hasattr(kern, "unpack_i16_")
                 and step is not None and n > 0 and m_v > 0 and len(level_idx) <= 64 and len(packing.fills) <= 2
                 and (int(np.max(level_idx)) - int(np.min(level_idx)) + 1) * nlat * nlon < 2 ** 31)
+    rows = max(1, SLAB_BYTES // max(1, nlev_all * max(nlat, 1) * nlon * 4))     # snapshots per fp32 slab
     if unpacked:
-        nbytes, found = _upload_packed_i16(lazy, level_idx, take, step, (i0, i1), ranges, blocks, device, kern, declared)
-        if declared:
-            stats.setdefault("fills", []).append((da.name, found))
-    nan_count = torch.zeros((), dtype=torch.int64, device=device) if declared and not unpacked else None
-    pinned = None
-    if direct:
-        pinned = [torch.empty((rows, m_v), dtype=torch.float32) for _ in range(2)]
-        if on_gpu:
-            pinned = [b.pin_memory() for b in pinned]
-    events = [None, None]
-    for it, j0 in enumerate(() if unpacked else range(0, n, rows)):
-        j1 = min(n, j0 + rows)
-        if direct:
-            buf = pinned[it & 1]
-            if events[it & 1] is not None:
-                events[it & 1].synchronize()        # the copy that last used this buffer is done
-            view = buf[: j1 - j0].numpy().reshape((j1 - j0, nlev_all, nlat, nlon))
-            if whole:
-                lazy.read_slab(int(take[j0]), int(take[j1 - 1]) + 1, view)
-            else:
-                lazy.read_box((int(take[j0]), 0, i0, 0), (j1 - j0, nlev_all, nlat, nlon), view)
-            dev = buf[: j1 - j0].to(device, non_blocking=True)
-            nbytes += (j1 - j0) * m_v * 4
-        else:
-            def read(lo, hi):
-                if lazy is None:
-                    return host[lo:hi] if whole else host[lo:hi, :, i0:i1]
-                if whole:
-                    return lazy.read_slab(lo, hi)
-                return lazy.read_box((lo, 0, i0, 0), (hi - lo, nlev_all, nlat, nlon))
-
-            if contiguous:
-                slab = read(int(take[j0]), int(take[j1 - 1]) + 1)
-            else:  # resampled: gather the selected snapshots
-                idx = take[j0:j1]
-                lo = int(idx.min())
-                slab = read(lo, int(idx.max()) + 1)[idx - lo]
-            if not all_levels:
-                slab = slab[:, level_idx]
-            if packing is not None:                 # file values -> physical ones (labeled.Packing.decode)
-                slab = packing.decode(slab)
-            slab = np.ascontiguousarray(slab.reshape(j1 - j0, m_v), dtype=np.float32)
-            nbytes += slab.nbytes
-            dev = torch.from_numpy(slab).to(device, non_blocking=False)
-        if nan_count is not None:                   # on the device, behind the upload: no host pass, no host sync
-            if direct:
-                for f in packing.fills:
-                    if f == f:                      # (a NaN fill value is already what it should become)
-                        dev.masked_fill_(dev == np.float32(f), float("nan"))
-            nan_count += torch.isnan(dev).sum()
-        for (a, b), Xb in zip(ranges, blocks):
-            Xb[j0:j1, : b - a].copy_(dev[:, a:b])
-        if direct and on_gpu:
-            events[it & 1] = torch.cuda.Event()
-            events[it & 1].record()
-        del dev
-    if nan_count is not None:
-        stats.setdefault("fills", []).append((da.name, nan_count))
+        nbytes, found = _upload_packed_i16(lazy, level_idx, take, step, band, ranges, blocks, device, kern, declared)
+    elif direct:
+        nbytes, found = _upload_direct_f32(lazy, take, band, rows, ranges, blocks, device, declared)
+    else:
+        nbytes, found = _upload_host_decode(da, level_idx, take, band, rows, ranges, blocks, device, declared)
+    if found is not None:
+        stats.setdefault("fills", []).append((da.name, found))
     for (a, b), Xb in zip(ranges, blocks):
         if center:
             mu, sd = kern.row_center_scale_(Xb[:, : b - a], bool(scale))   # (the zero rows stay zero: 0 / 0 otherwise)
@@ -783,6 +829,403 @@ def _upload_variable(da: DataArray, level_idx, take, device, kern, center, scale
             if scale:
                 stats["std"].append(sd)
     return blocks, m_v, nbytes
+
+
+@dataclass(frozen=True, eq=False)
+class _Job:
+    """The shape of one ``_device_pipeline`` call: what is decomposed, how, and this rank's share of it."""
+    names: list            # the variables, in the file's order
+    level_idx: np.ndarray  # the selected levels as indices into the file's level axis
+    levels: np.ndarray
+    take: np.ndarray       # the selected snapshots as indices into the file's time axis
+    time: np.ndarray       # their labels
+    lats: np.ndarray
+    lons: np.ndarray
+    nlev: int
+    nlat: int
+    nlon: int
+    d: int                 # delay embedding
+    k: int                 # n_components
+    svd_type: str
+    center: bool
+    scale: bool
+    save_data_matrix: bool
+    engine_opts: dict
+    out_dtype: type        # of the returned arrays: the file's float type
+    band: tuple | None     # this rank's latitude rows [i0, i1), None for a single rank
+    rows_local: int        # space points of this rank (before the embedding)
+    rows_global: int       # rows of the embedded matrix over all ranks
+    wide: bool             # fewer rows than embedded snapshots
+    can_stream: bool
+    shard: str             # " (rank r of N: latitude rows i0:i1)" for the log lines, "" for a single rank
+
+    @property
+    def n(self) -> int:
+        return len(self.take)
+
+    @property
+    def lat_rows(self) -> tuple:
+        return self.band if self.band else (0, self.nlat)
+
+
+def _plan_job(ds: Dataset, parsed_config: dict, comm) -> _Job:
+    names = list(ds.data_vars)
+    d = parsed_config["delay_embedding"]
+    level_idx, levels, take, time = plan_selection(ds, parsed_config["levels"], parsed_config["delta_time"])
+    log_and_print(logger, f"Dataset slicing completed successfully using levels {list(levels)}")
+    log_and_print(logger, f"Resampled the dataset with time delta: {parsed_config['delta_time']}")
+    lats, lons = ds.coords["latitude"].values, ds.coords["longitude"].values
+    nlev, nlat, nlon = len(levels), len(lats), len(lons)
+    band = lat_band(nlat, comm.rank, comm.world_size) if comm.world_size > 1 else None
+    rows_global = d * len(names) * nlev * nlat * nlon
+    wide = rows_global < len(take) - d + 1
+    src_dtype = ds[names[0]].dtype
+    return _Job(
+        names=names, level_idx=level_idx, levels=levels, take=take, time=time, lats=lats, lons=lons,
+        nlev=nlev, nlat=nlat, nlon=nlon, d=d, k=parsed_config["n_components"], svd_type=parsed_config["svd_type"],
+        center=parsed_config["mean_center"], scale=parsed_config["scale"],
+        save_data_matrix=parsed_config["save_data_matrix"], engine_opts=_engine_opts(parsed_config),
+        out_dtype=src_dtype if src_dtype in (np.float32, np.float64) else np.float64,
+        band=band, rows_local=len(names) * nlev * ((band[1] - band[0]) if band else nlat) * nlon,
+        rows_global=rows_global, wide=wide,
+        # what can be streamed from the file in passes when X does not fit: anything tall whose data
+        # matrix is not asked for (un-centred standard SVD included: the exact mean deflation centres
+        # the pieces as they pass; a spectrum steeper than the Gram resolves costs one more pass)
+        can_stream=not wide and not parsed_config["save_data_matrix"],
+        shard=f" (rank {comm.rank} of {comm.world_size}: latitude rows {band[0]}:{band[1]})" if band else "")
+
+
+def _sync(device) -> None:
+    if device.type == "cuda":
+        import torch
+
+        torch.cuda.synchronize()
+
+
+# ---- residency: X in HBM, or streamed from the file in passes
+def _stream_bytes_for(need: int, free: int, reserve: int, can_stream: bool, *, rows: int, n: int, rows_all: int,
+                      world_size: int, others_fit: bool = True) -> int:
+    """The residency decision of one rank.  ``need``: bytes of this rank's ``rows x n`` fp32 share of X plus
+    ``reserve``, what the resident path allocates next to it; ``free``: free HBM; ``others_fit``: the vote of the
+    ranks.  -> 0: X is resident; > 0: the bytes of X a streamed piece may take.  A slice that neither fits nor
+    can be streamed is refused with the number of ranks that would hold its ``rows_all x n`` values."""
+    if need <= free and others_fit:
+        return 0
+    if can_stream:
+        return max(1 << 30, min(free // 3, 32 << 30))
+    ranks = -(-4 * rows_all * n // max(free - reserve, 1 << 30))
+    raise MemoryError(
+        f"the snapshot matrix of this rank ({rows} x {n} fp32 = {4 * rows * n / 1e9:.1f} GB) "
+        f"does not fit the {free / 1e9:.1f} GB of free HBM; shard the space points over more GPUs: "
+        f"python -m torch.distributed.run --nproc-per-node N -m dmd_era5_amd.era5_svd with N >= "
+        f"{max(ranks, world_size + 1)} (without save_data_matrix such a slice is streamed from the "
+        "file in passes instead)")
+
+
+def _all_ranks_fit(fits: bool, comm, device) -> bool:
+    """One decision for all ranks: the resident and the streaming path exchange differently."""
+    if not comm.exchanges:
+        return fits
+    import torch
+
+    flags = comm.allgather(torch.tensor([1 if fits else 0], dtype=torch.int64, device=device))
+    return all(int(f.item()) for f in flags)
+
+
+def _decide_stream_bytes(job: _Job, comm, kern, device) -> int:
+    """``_stream_bytes_for`` on what this device has free.  DMDX_STREAM_BYTES > 0 forces the streaming path
+    (tests); off the GPU X is always resident."""
+    from . import svd as dsvd
+
+    forced = int(os.environ.get("DMDX_STREAM_BYTES", "0"))
+    if forced or device.type != "cuda":
+        return forced
+    # X should be resident: find out before the allocator does
+    reserve = _resident_reserve_bytes(job.rows_local, job.n, job.d, job.k, job.svd_type, kern)
+    need = 4 * job.rows_local * job.n + reserve
+    free = dsvd.free_device_bytes(device)
+    return _stream_bytes_for(need, free, reserve, job.can_stream, rows=job.rows_local, n=job.n,
+                             rows_all=len(job.names) * job.nlev * job.nlat * job.nlon, world_size=comm.world_size,
+                             others_fit=_all_ranks_fit(need <= free, comm, device))
+
+
+# ---- the streamed run
+class _StreamedPieces:
+    """The piece source of the streamed run.  Every call is one pass over the file: per variable and latitude
+    sub-band, the centred / scaled row blocks of that piece.  The passes leave behind the row means / stds per
+    (variable index, first latitude row), the fill codes met per piece, and the bytes moved (all passes)."""
+
+    def __init__(self, ds, job: _Job, comm, kern, device, sub):
+        self.ds, self.job, self.comm, self.kern, self.device, self.sub = ds, job, comm, kern, device, sub
+        self.means, self.stds, self.fills, self.moved = {}, {}, {}, 0
+
+    def __call__(self):
+        import torch
+
+        job = self.job
+        for vi, name in enumerate(job.names):
+            for j0, j1 in self.sub:
+                st = {"mean": [], "std": []}
+                vb, _, nbytes = _upload_variable(self.ds[name], job.level_idx, job.take, self.device, self.kern,
+                                                 job.center, job.scale, st, (j0, j1))
+                if st.get("fills"):
+                    # one rank: the piece is refused before it reaches a Gram or a product.  Several
+                    # ranks: the ranks have different numbers of pieces, so there is no common point
+                    # for a collective here; the counts are kept and summed once behind the SVD call,
+                    # which every rank leaves at the same place (its finite checks are made on
+                    # all-reduced quantities)
+                    if not self.comm.exchanges:
+                        _raise_on_fill_codes(st["fills"], self.comm, self.device,
+                                             f"latitude rows {j0}:{j1} of the selected slice (the first piece with any)")
+                    self.fills[(vi, j0)] = st["fills"][0]
+                if job.center:
+                    self.means[(vi, j0)] = torch.cat(st["mean"])
+                if job.scale:
+                    self.stds[(vi, j0)] = torch.cat(st["std"])
+                self.moved += nbytes
+                yield vb
+
+
+def _svd_streamed(ds: Dataset, job: _Job, comm, kern, device, stream_bytes: int):
+    """X does not fit: the Gram is accumulated and the projection made while latitude sub-bands of the
+    variables pass through the HBM, two or three times (svd.svd_snapshots_streaming).
+    -> (SvdResult with the rows in this rank's (k, d, variable, level, band, lon) order, stats);
+    ``stats["moved"]``: file bytes moved over all passes."""
+    import torch
+
+    from . import svd as dsvd
+
+    if not job.can_stream:
+        raise ValueError("the streaming path needs save_data_matrix = False and a tall problem")
+    names, nlev, nlon, d = job.names, job.nlev, job.nlon, job.d
+    i0, i1 = job.lat_rows
+    h = max(1, stream_bytes // max(1, 4 * job.n * nlev * nlon))       # latitude rows per piece
+    sub = [(j, min(i1, j + h)) for j in range(i0, i1, h)]
+    pieces = _StreamedPieces(ds, job, comm, kern, device, sub)
+    log_and_print(logger, f"Snapshot matrix larger than the HBM: streaming it in {len(names) * len(sub)} pieces of "
+                          f"<= {h} latitude rows{job.shard}")
+    log_and_print(logger, f"Performing {job.svd_type} SVD...")
+    failed = None
+    try:
+        if job.svd_type == "standard":
+            Ub, s_, Vh_, sinfo = dsvd.svd_snapshots_streaming(pieces, job.k, job.rows_global, delay=d, comm=comm, kern=kern)
+        else:
+            Ub, s_, Vh_, sinfo = dsvd.svd_randomized_streaming(pieces, job.k, job.rows_global, job.n, delay=d, comm=comm,
+                                                               kern=kern, **job.engine_opts)
+    except np.linalg.LinAlgError as e:          # (raised on all-reduced quantities: by every rank or by none)
+        failed = e
+    declared = [nm for nm in names if any(key in getattr(ds[nm], "encoding", {}) for key in ("_FillValue", "missing_value"))]
+    if comm.exchanges and declared:
+        # several ranks: ONE summed check here, where every rank arrives whether the SVD raised or returned
+        local = {}
+        for (vi, _), (nm, c) in sorted(pieces.fills.items()):
+            local[nm] = local.get(nm, 0) + int(c)
+        _raise_on_fill_codes([(nm, local.get(nm, 0)) for nm in declared], comm, device)
+    if failed is not None:
+        raise failed
+    if sinfo.get("warning"):
+        log_and_print(logger, "WARNING: " + sinfo["warning"])
+    kk = int(s_.numel())
+    Ul = torch.empty((kk, d, len(names), nlev, i1 - i0, nlon), dtype=torch.float32, device=device)
+    mean_l = torch.empty((len(names), nlev, i1 - i0, nlon), dtype=torch.float32, device=device)
+    std_l = torch.empty_like(mean_l) if job.scale else None
+    idx = 0
+    for vi in range(len(names)):
+        for j0, j1 in sub:      # a piece's rows: (level, its latitude rows, longitude), embedded as k_delay * m_piece + s
+            Ul[:, :, vi, :, j0 - i0:j1 - i0, :] = dsvd._assemble_rows(Ub[idx], d).reshape(kk, d, nlev, j1 - j0, nlon)
+            if job.center:
+                mean_l[vi, :, j0 - i0:j1 - i0, :] = pieces.means[(vi, j0)].reshape(nlev, j1 - j0, nlon)
+            if job.scale:
+                std_l[vi, :, j0 - i0:j1 - i0, :] = pieces.stds[(vi, j0)].reshape(nlev, j1 - j0, nlon)
+            Ub[idx] = None
+            idx += 1
+    res = dsvd.SvdResult(Ut=Ul.reshape(kk, -1), s=s_, Vh=Vh_, info=sinfo)
+    return res, {"mean": [mean_l.reshape(-1)], "std": [std_l.reshape(-1)] if job.scale else [], "moved": pieces.moved}
+
+
+# ---- the resident run
+def _ingest_resident(ds: Dataset, job: _Job, comm, kern, device):
+    """Every variable of this rank's band -> centred / scaled row blocks in HBM.
+    -> (blocks, true_rows, stats, bytes moved); ``true_rows``: the width of every block without the zero rows
+    ``pad4`` appended.  Missing values raise here, before any SVD work."""
+    from . import svd as dsvd
+
+    # `python -m dmd_era5.era5_svd.era5_svd` is one process per slice: every run is a "first
+    # call".  While the slice crosses PCIe (the GPU and most host threads are idle) a side
+    # thread takes the SVD path once on a toy matrix, so that the dense libraries' handles and
+    # the code objects of every kernel are loaded when the real matrix is resident.  Only for
+    # slices of >= 1 GiB: the reference's default config (0.4 GB, scripts/bench_default_config.py)
+    # ingests in 0.1-0.4 s, less than the toy run takes -- 2.62 s primed against 1.99 s.
+    # (DMDX_PRIME_MIN_BYTES: tests force the primer onto small slices)
+    prime_min = int(os.environ.get("DMDX_PRIME_MIN_BYTES", str(1 << 30)))
+    primer = _prime_async(device, job.svd_type) if device.type == "cuda" and \
+        4 * job.rows_local * job.n >= prime_min else None
+    blocks, true_rows, stats, total = [], [], {"mean": [], "std": []}, 0
+    for name in job.names:
+        # (a tall problem on a grid whose space-point count is not a multiple of 4: 1-3 zero rows per variable)
+        vb, m_v, nbytes = _upload_variable(ds[name], job.level_idx, job.take, device, kern, job.center, job.scale,
+                                           stats, job.band, pad4=not job.wide)
+        blocks.extend(vb)
+        true_rows.extend(b - a for a, b in dsvd.split_rows(m_v))
+        total += nbytes
+    if primer is not None:
+        primer.join()
+    _sync(device)
+    _raise_on_fill_codes(stats.get("fills"), comm, device)
+    return blocks, true_rows, stats, total
+
+
+def _svd_transposed(blocks, job: _Job, comm, kern):
+    """WIDE problem (fewer space rows than snapshots: a coarse mock grid over a long period).
+    sklearn transposes wide inputs (extmath.py:562-566) and LAPACK does not care; here the
+    tall algorithms run on E^T -- the embedded matrix is small by definition (< n^2 floats),
+    so it is materialised -- and the factors swap roles."""
+    import torch
+
+    from . import svd as dsvd
+
+    d, nd = job.d, job.n - job.d + 1
+    if comm.world_size > 1:
+        raise ValueError(f"{job.rows_global} space rows < {nd} snapshots: a wide problem is small, "
+                         "run it as a single process (no torch.distributed)")
+    Xall = torch.cat(blocks, dim=1)                                            # (n, M)
+    E = torch.cat([Xall[kd:kd + nd].T for kd in range(d)], dim=0).contiguous()  # (d M, nd): row kd*M + s
+    del Xall
+    log_and_print(logger, f"Performing {job.svd_type} SVD...")
+    if job.svd_type == "standard":
+        rt = dsvd.svd_snapshots(E, job.k, flip_sign=False, kern=kern)
+    else:
+        rt = dsvd.svd_randomized(E, job.k, flip_sign=False, kern=kern, **job.engine_opts)
+    Ut = rt.Vh.to(torch.float32)                   # (k, d M): left singular vectors of E
+    Vh = rt.Ut.to(torch.float64)                   # (k, nd)
+    big = Ut.abs().argmax(dim=1, keepdim=True)     # u-based sign convention (svd_flip)
+    sign = torch.where(Ut.gather(1, big) < 0, -1.0, 1.0)
+    res = dsvd.SvdResult(Ut=Ut * sign, s=rt.s, Vh=Vh * sign.to(torch.float64), info=dict(rt.info, wide=True))
+    log_and_print(logger, f"{job.svd_type.capitalize()} SVD complete.")
+    return res
+
+
+def _drop_pad_rows(res, blocks, true_rows, d: int):
+    """Drop the zero rows the ingest appended (their rows of U are exactly zero)
+    -> (SvdResult on the true rows, the blocks as their narrow views)."""
+    import torch
+
+    from . import svd as dsvd
+
+    Mp = sum(int(b.shape[1]) for b in blocks)
+    keep, off = [], 0
+    for b, r in zip(blocks, true_rows):
+        keep.append(torch.arange(off, off + r, device=b.device))
+        off += int(b.shape[1])
+    kk = res.Ut.shape[0]
+    Ut = res.Ut.reshape(kk, d, Mp).index_select(2, torch.cat(keep)).reshape(kk, -1)
+    return dsvd.SvdResult(Ut=Ut, s=res.s, Vh=res.Vh, info=res.info), [b[:, :r] for b, r in zip(blocks, true_rows)]
+
+
+def _svd_resident(blocks, true_rows, job: _Job, comm, kern):
+    """-> (SvdResult on this rank's true rows, the row blocks without their pad rows)."""
+    from . import svd as dsvd
+
+    if job.wide:
+        res = _svd_transposed(blocks, job, comm, kern)
+    elif job.svd_type == "standard":
+        log_and_print(logger, "Performing standard SVD...")
+        res = dsvd.svd_snapshots(blocks, job.k, delay=job.d, comm=comm, kern=kern)
+        if res.info.get("mean_deflated"):
+            log_and_print(logger, "Un-centred data: SVD of the centred matrix + rank-one update for the time mean.")
+        if res.info.get("warning"):
+            log_and_print(logger, "WARNING: " + res.info["warning"])
+        log_and_print(logger, "Standard SVD complete.")
+    else:
+        log_and_print(logger, "Performing randomized SVD...")
+        res = dsvd.svd_randomized(blocks, job.k, delay=job.d, comm=comm, kern=kern, **job.engine_opts)
+        log_and_print(logger, "Randomized SVD complete.")
+    if any(int(b.shape[1]) != r for b, r in zip(blocks, true_rows)):
+        return _drop_pad_rows(res, blocks, true_rows, job.d)
+    return res, blocks
+
+
+# ---- the gather to rank 0's host memory
+def _assemble(t, lead: tuple, job: _Job, comm) -> np.ndarray | None:
+    """Rank-local (*lead, rows of this rank in (variable, level, band, lon) order) pieces ->
+    the global (*lead, variable, level, latitude, longitude) host array on rank 0."""
+    parts = comm.gather_to_root(t)
+    if parts is None:
+        return None
+    grid = (len(job.names), job.nlev, job.nlat, job.nlon)
+    if len(parts) == 1:
+        return parts[0].numpy().reshape(lead + grid)
+    out = np.empty(lead + grid, dtype=parts[0].numpy().dtype)
+    for r, part in enumerate(parts):
+        j0, j1 = lat_band(job.nlat, r, comm.world_size)
+        out[..., j0:j1, :] = part.numpy().reshape(lead + grid[:2] + (j1 - j0, job.nlon))
+    return out
+
+
+def _row_vector(parts, job: _Job, comm, coords) -> DataArray | None:
+    """Per-row values of the ingest (means, stds) -> the (space,) DataArray of the embedded rows on rank 0."""
+    import torch
+
+    v = _assemble(torch.cat(parts), (), job, comm)
+    if v is None:
+        return None
+    return DataArray(np.tile(v.reshape(-1).astype(job.out_dtype), job.d), ("space",),
+                     {k: coords[k] for k in ("space", "original_variable")})
+
+
+def _data_matrix(blocks, job: _Job, comm, device, coords) -> DataArray | None:
+    """The embedded data matrix ``save_data_matrix`` asks for, (space, time) on rank 0."""
+    import torch
+
+    from . import svd as dsvd
+    from .slice_tools import _apply_delay_embedding_np
+
+    d, n = job.d, blocks[0].shape[0]
+    nt, M = n - d + 1, sum(int(b.shape[1]) for b in blocks)
+    if not comm.exchanges and device.type == "cuda" and nt > 0 and \
+            4 * d * M * nt + (1 << 30) <= dsvd.free_device_bytes(device):
+        # one rank and room for it: the embedded matrix is laid out on the device as the file
+        # wants it -- (space = k_delay * M + s, time) row-major, E[k M + s, t] = X[t + k, s] -- and
+        # leaves in one copy.  (The host route below gathers the time-major blocks, embeds them
+        # column-major as the reference does and lets the writer transpose 0.8 GB: 0.27 s of the
+        # 0.73 s a warm main() takes on the reference's default config; this takes 0.06 s.)
+        Xe = torch.empty((d, M, nt), dtype=torch.float32, device=device)
+        off = 0
+        for b in blocks:
+            mb = int(b.shape[1])
+            for kd in range(d):
+                Xe[kd, off:off + mb].copy_(b[kd:kd + nt].T)
+            off += mb
+        return DataArray(Xe.reshape(d * M, nt).cpu().numpy().astype(job.out_dtype, copy=False), ("space", "time"), coords)
+    # several ranks, or no room: concatenate on the host (a device-side cat would hold X twice in HBM)
+    Xall = torch.cat(blocks, dim=1) if comm.exchanges else torch.cat([b.cpu() for b in blocks], dim=1)
+    Xg = _assemble(Xall, (n,), job, comm)                # (time, variable, level, lat, lon) on rank 0
+    del Xall
+    if Xg is None:
+        return None
+    Xc = Xg.reshape(n, -1).T.astype(job.out_dtype, copy=False)
+    return DataArray(_apply_delay_embedding_np(np.asfortranarray(Xc), d), ("space", "time"), coords)
+
+
+def _gather_results(res, stats, blocks, job: _Job, comm, device):
+    """The row-sharded results -> what ``_device_pipeline`` returns: U, then the row means and stds, then X
+    are gathered to rank 0 in the global row order; the other ranks get None for them and for the coords."""
+    kk = res.Ut.shape[0]
+    Ug = _assemble(res.Ut, (kk, job.d), job, comm)       # local row order k_delay*m_loc + s_loc
+    U = None if Ug is None else Ug.reshape(kk, -1).T.astype(job.out_dtype, copy=False)
+    s = res.s.cpu().numpy().astype(job.out_dtype, copy=False)
+    V = res.Vh.cpu().numpy().astype(job.out_dtype, copy=False)
+    coords = X = X_mean = X_std = None
+    if comm.rank == 0:
+        one = space_labels(job.levels, job.lats, job.lons)
+        coords = delay_coords(np.tile(one, (len(job.names), 1)), np.repeat(job.names, one.shape[0]), job.time, job.d)
+    if job.center and job.d > 1:  # the reference keeps the mean / std only in this case (ref :400-414)
+        X_mean = _row_vector(stats["mean"], job, comm, coords)
+        if job.scale:
+            X_std = _row_vector(stats["std"], job, comm, coords)
+    if job.save_data_matrix:
+        X = _data_matrix(blocks, job, comm, device, coords)
+    return U, s, V, coords, X, X_mean, X_std
 
 
 def _device_pipeline(ds: Dataset, parsed_config: dict, comm=None, kern=None, device=None):
@@ -799,7 +1242,10 @@ def _device_pipeline(ds: Dataset, parsed_config: dict, comm=None, kern=None, dev
 
     ``kern`` / ``device``: the kernel provider and where the row blocks live -- the HIP kernels
     on the current GPU unless a test injects its CPU double (main() never does: without
-    libdmdx.so or a GPU ``default_kernels()`` raises)."""
+    libdmdx.so or a GPU ``default_kernels()`` raises).
+
+    The stages: ``_plan_job`` (the shape of the job), ``_decide_stream_bytes`` (X resident or streamed),
+    ``_svd_streamed`` or ``_ingest_resident`` + ``_svd_resident``, ``_gather_results``."""
     import time as _time
 
     import torch
@@ -808,287 +1254,33 @@ def _device_pipeline(ds: Dataset, parsed_config: dict, comm=None, kern=None, dev
     from .kernels import default_kernels
 
     comm = comm or dsvd.Comm()
-    root = comm.rank == 0
     if kern is None:
         kern = default_kernels()
         device = torch.device("cuda", torch.cuda.current_device())
-    sync = torch.cuda.synchronize if device.type == "cuda" else (lambda: None)
-    d = parsed_config["delay_embedding"]
-    center, scale = parsed_config["mean_center"], parsed_config["scale"]
-    names = list(ds.data_vars)
-    level_idx, levels, take, time = plan_selection(ds, parsed_config["levels"], parsed_config["delta_time"])
-    log_and_print(logger, f"Dataset slicing completed successfully using levels {list(levels)}")
-    log_and_print(logger, f"Resampled the dataset with time delta: {parsed_config['delta_time']}")
-    lats, lons = ds.coords["latitude"].values, ds.coords["longitude"].values
-    nlev, nlat, nlon = len(levels), len(lats), len(lons)
-    band = lat_band(nlat, comm.rank, comm.world_size) if comm.world_size > 1 else None
-
-    k = parsed_config["n_components"]
-    rows_global = d * len(names) * nlev * nlat * nlon
-    wide = rows_global < len(take) - d + 1
-    shard = f" (rank {comm.rank} of {comm.world_size}: latitude rows {band[0]}:{band[1]})" if band else ""
-    stream_bytes = int(os.environ.get("DMDX_STREAM_BYTES", "0"))      # > 0 forces the streaming path (tests)
-    # what can be streamed from the file in passes when X does not fit: anything tall whose data
-    # matrix is not asked for (un-centred standard SVD included: the exact mean deflation centres
-    # the pieces as they pass; a spectrum steeper than the Gram resolves costs one more pass)
-    can_stream = not wide and not parsed_config["save_data_matrix"]
-    if device.type == "cuda" and not stream_bytes:
-        # X should be resident: find out before the allocator does
-        rows = len(names) * nlev * ((band[1] - band[0]) if band else nlat) * nlon
-        reserve = _resident_reserve_bytes(rows, len(take), d, k, parsed_config["svd_type"], kern)
-        need = 4 * rows * len(take) + reserve
-        # free HBM = what the driver reports + what torch's allocator holds cached but unused
-        free = torch.cuda.mem_get_info(device)[0] + max(
-            0, torch.cuda.memory_reserved(device) - torch.cuda.memory_allocated(device))
-        fits = need <= free
-        if comm.exchanges:   # one decision for all ranks: the resident and the streaming path exchange differently
-            flags = comm.allgather(torch.tensor([1 if fits else 0], dtype=torch.int64, device=device))
-            fits = all(int(f.item()) for f in flags)
-        if not fits:
-            if can_stream:
-                stream_bytes = max(1 << 30, min(free // 3, 32 << 30))
-            else:
-                ranks = -(-4 * len(names) * nlev * nlat * nlon * len(take) // max(free - reserve, 1 << 30))
-                raise MemoryError(
-                    f"the snapshot matrix of this rank ({rows} x {len(take)} fp32 = {4 * rows * len(take) / 1e9:.1f} GB) "
-                    f"does not fit the {free / 1e9:.1f} GB of free HBM; shard the space points over more GPUs: "
-                    f"python -m torch.distributed.run --nproc-per-node N -m dmd_era5_amd.era5_svd with N >= "
-                    f"{max(ranks, comm.world_size + 1)} (without save_data_matrix such a slice is streamed from the "
-                    "file in passes instead)")
-
-    blocks = []
+    job = _plan_job(ds, parsed_config, comm)
+    stream_bytes = _decide_stream_bytes(job, comm, kern, device)
+    t0 = _time.perf_counter()
     if stream_bytes:
-        # X does not fit: the Gram is accumulated and the projection made while latitude sub-bands of
-        # the variables pass through the HBM, two or three times (svd.svd_snapshots_streaming)
-        if not can_stream:
-            raise ValueError("the streaming path needs save_data_matrix = False and a tall problem")
-        i0, i1 = band if band else (0, nlat)
-        h = max(1, stream_bytes // max(1, 4 * len(take) * nlev * nlon))       # latitude rows per piece
-        sub = [(j, min(i1, j + h)) for j in range(i0, i1, h)]
-        means, stds, moved, fills = {}, {}, [0], {}
-
-        def pieces():
-            for vi, name in enumerate(names):
-                for j0, j1 in sub:
-                    st = {"mean": [], "std": []}
-                    vb, _, nbytes = _upload_variable(ds[name], level_idx, take, device, kern, center, scale, st, (j0, j1))
-                    if st.get("fills"):
-                        # one rank: the piece is refused before it reaches a Gram or a product.  Several
-                        # ranks: the ranks have different numbers of pieces, so there is no common point
-                        # for a collective here; the counts are kept and summed once behind the SVD call,
-                        # which every rank leaves at the same place (its finite checks are made on
-                        # all-reduced quantities)
-                        if not comm.exchanges:
-                            _raise_on_fill_codes(st["fills"], comm, device,
-                                                 f"latitude rows {j0}:{j1} of the selected slice (the first piece with any)")
-                        fills[(vi, j0)] = st["fills"][0]
-                    if center:
-                        means[(vi, j0)] = torch.cat(st["mean"])
-                    if scale:
-                        stds[(vi, j0)] = torch.cat(st["std"])
-                    moved[0] += nbytes
-                    yield vb
-
-        t0 = _time.perf_counter()
-        log_and_print(logger, f"Snapshot matrix larger than the HBM: streaming it in {len(names) * len(sub)} pieces of "
-                              f"<= {h} latitude rows{shard}")
-        log_and_print(logger, f"Performing {parsed_config['svd_type']} SVD...")
-        failed = None
-        try:
-            if parsed_config["svd_type"] == "standard":
-                Ub, s_, Vh_, sinfo = dsvd.svd_snapshots_streaming(pieces, k, rows_global, delay=d, comm=comm, kern=kern)
-            else:
-                Ub, s_, Vh_, sinfo = dsvd.svd_randomized_streaming(pieces, k, rows_global, len(take), delay=d, comm=comm,
-                                                                   kern=kern, **_engine_opts(parsed_config))
-        except np.linalg.LinAlgError as e:          # (raised on all-reduced quantities: by every rank or by none)
-            failed = e
-        declared = [nm for nm in names if any(key in getattr(ds[nm], "encoding", {}) for key in ("_FillValue", "missing_value"))]
-        if comm.exchanges and declared:
-            # several ranks: ONE summed check here, where every rank arrives whether the SVD raised or returned
-            local = {}
-            for (vi, _), (nm, c) in sorted(fills.items()):
-                local[nm] = local.get(nm, 0) + int(c)
-            _raise_on_fill_codes([(nm, local.get(nm, 0)) for nm in declared], comm, device)
-        if failed is not None:
-            raise failed
-        if sinfo.get("warning"):
-            log_and_print(logger, "WARNING: " + sinfo["warning"])
-        kk = int(s_.numel())
-        Ul = torch.empty((kk, d, len(names), nlev, i1 - i0, nlon), dtype=torch.float32, device=device)
-        mean_l = torch.empty((len(names), nlev, i1 - i0, nlon), dtype=torch.float32, device=device)
-        std_l = torch.empty_like(mean_l) if scale else None
-        idx = 0
-        for vi in range(len(names)):
-            for j0, j1 in sub:      # a piece's rows: (level, its latitude rows, longitude), embedded as k_delay * m_piece + s
-                Ul[:, :, vi, :, j0 - i0:j1 - i0, :] = dsvd._assemble_rows(Ub[idx], d).reshape(kk, d, nlev, j1 - j0, nlon)
-                if center:
-                    mean_l[vi, :, j0 - i0:j1 - i0, :] = means[(vi, j0)].reshape(nlev, j1 - j0, nlon)
-                if scale:
-                    std_l[vi, :, j0 - i0:j1 - i0, :] = stds[(vi, j0)].reshape(nlev, j1 - j0, nlon)
-                Ub[idx] = None
-                idx += 1
-        res = dsvd.SvdResult(Ut=Ul.reshape(kk, -1), s=s_, Vh=Vh_, info=sinfo)
-        stats = {"mean": [mean_l.reshape(-1)], "std": [std_l.reshape(-1)] if scale else []}
-        npass = int(sinfo.get("passes_over_X", 2))
-        total = moved[0] // npass
-        sync()
+        blocks = []
+        res, stats = _svd_streamed(ds, job, comm, kern, device, stream_bytes)
+        npass = int(res.info.get("passes_over_X", 2))
+        total = stats["moved"] // npass
+        _sync(device)
         dt = _time.perf_counter() - t0
-        log_and_print(logger, f"{parsed_config['svd_type'].capitalize()} SVD complete.")
+        log_and_print(logger, f"{job.svd_type.capitalize()} SVD complete.")
         log_and_print(logger, f"Ingest + SVD ({npass} passes over the file): {dt:.2f} s "
                               f"({npass * total / 1e9 / max(dt, 1e-9):.1f} GB/s of file data)")
-        t0 = _time.perf_counter()
     else:
-        t0 = _time.perf_counter()
-        # `python -m dmd_era5.era5_svd.era5_svd` is one process per slice: every run is a "first
-        # call".  While the slice crosses PCIe (the GPU and most host threads are idle) a side
-        # thread takes the SVD path once on a toy matrix, so that the dense libraries' handles and
-        # the code objects of every kernel are loaded when the real matrix is resident.  Only for
-        # slices of >= 1 GiB: the reference's default config (0.4 GB, scripts/bench_default_config.py)
-        # ingests in 0.1-0.4 s, less than the toy run takes -- 2.62 s primed against 1.99 s.
-        # (DMDX_PRIME_MIN_BYTES: tests force the primer onto small slices)
-        prime_min = int(os.environ.get("DMDX_PRIME_MIN_BYTES", str(1 << 30)))
-        primer = _prime_async(device, parsed_config["svd_type"]) if device.type == "cuda" and \
-            4 * rows * len(take) >= prime_min else None
-        stats, total, true_rows = {"mean": [], "std": []}, 0, []
-        for name in names:
-            # (a tall problem on a grid whose space-point count is not a multiple of 4: 1-3 zero rows per variable)
-            vb, m_v, nbytes = _upload_variable(ds[name], level_idx, take, device, kern, center, scale, stats, band,
-                                               pad4=not wide)
-            blocks.extend(vb)
-            true_rows.extend(b - a for a, b in dsvd.split_rows(m_v))
-            total += nbytes
-        if primer is not None:
-            primer.join()
-        sync()
-        _raise_on_fill_codes(stats.get("fills"), comm, device)      # missing values: before any SVD work
+        blocks, true_rows, stats, total = _ingest_resident(ds, job, comm, kern, device)
         dt = _time.perf_counter() - t0
         log_and_print(logger, f"Ingest: {total / 1e9:.3f} GB to HBM in {dt:.2f} s ({total / 1e9 / max(dt, 1e-9):.2f} GB/s, "
-                              f"{len(blocks)} row blocks, centre/scale on device){shard}")
+                              f"{len(blocks)} row blocks, centre/scale on device){job.shard}")
         t0 = _time.perf_counter()
-    if stream_bytes:
-        pass          # res, stats are ready
-    elif wide:
-        # WIDE problem (fewer space rows than snapshots: a coarse mock grid over a long period).
-        # sklearn transposes wide inputs (extmath.py:562-566) and LAPACK does not care; here the
-        # tall algorithms run on E^T -- the embedded matrix is small by definition (< n^2 floats),
-        # so it is materialised -- and the factors swap roles.
-        if comm.world_size > 1:
-            raise ValueError(f"{rows_global} space rows < {len(take) - d + 1} snapshots: a wide problem is small, "
-                             "run it as a single process (no torch.distributed)")
-        nd = len(take) - d + 1
-        Xall = torch.cat(blocks, dim=1)                                            # (n, M)
-        E = torch.cat([Xall[kd:kd + nd].T for kd in range(d)], dim=0).contiguous()  # (d M, nd): row kd*M + s
-        del Xall
-        log_and_print(logger, f"Performing {parsed_config['svd_type']} SVD...")
-        if parsed_config["svd_type"] == "standard":
-            rt = dsvd.svd_snapshots(E, k, flip_sign=False, kern=kern)
-        else:
-            rt = dsvd.svd_randomized(E, k, flip_sign=False, kern=kern, **_engine_opts(parsed_config))
-        Ut = rt.Vh.to(torch.float32)                   # (k, d M): left singular vectors of E
-        Vh = rt.Ut.to(torch.float64)                   # (k, nd)
-        big = Ut.abs().argmax(dim=1, keepdim=True)     # u-based sign convention (svd_flip)
-        sign = torch.where(Ut.gather(1, big) < 0, -1.0, 1.0)
-        res = dsvd.SvdResult(Ut=Ut * sign, s=rt.s, Vh=Vh * sign.to(torch.float64), info=dict(rt.info, wide=True))
-        log_and_print(logger, f"{parsed_config['svd_type'].capitalize()} SVD complete.")
-    elif parsed_config["svd_type"] == "standard":
-        log_and_print(logger, "Performing standard SVD...")
-        res = dsvd.svd_snapshots(blocks, k, delay=d, comm=comm, kern=kern)
-        if res.info.get("mean_deflated"):
-            log_and_print(logger, "Un-centred data: SVD of the centred matrix + rank-one update for the time mean.")
-        if res.info.get("warning"):
-            log_and_print(logger, "WARNING: " + res.info["warning"])
-        log_and_print(logger, "Standard SVD complete.")
-    else:
-        log_and_print(logger, "Performing randomized SVD...")
-        res = dsvd.svd_randomized(blocks, k, delay=d, comm=comm, kern=kern, **_engine_opts(parsed_config))
-        log_and_print(logger, "Randomized SVD complete.")
-    if not stream_bytes and any(int(b.shape[1]) != r for b, r in zip(blocks, true_rows)):
-        # drop the zero rows the ingest appended (their rows of U are exactly zero); from here on the
-        # blocks are the narrow views again
-        Mp = sum(int(b.shape[1]) for b in blocks)
-        keep, off = [], 0
-        for b, r in zip(blocks, true_rows):
-            keep.append(torch.arange(off, off + r, device=device))
-            off += int(b.shape[1])
-        kk_ = res.Ut.shape[0]
-        Ut = res.Ut.reshape(kk_, d, Mp).index_select(2, torch.cat(keep)).reshape(kk_, -1)
-        res = dsvd.SvdResult(Ut=Ut, s=res.s, Vh=res.Vh, info=res.info)
-        blocks = [b[:, :r] for b, r in zip(blocks, true_rows)]
-    sync()
-    dt = _time.perf_counter() - t0
-    if not stream_bytes:
+        res, blocks = _svd_resident(blocks, true_rows, job, comm, kern)
+        _sync(device)
+        dt = _time.perf_counter() - t0
         log_and_print(logger, f"SVD stage: {dt:.3f} s ({total / 1e9 / max(dt, 1e-9):.1f} GB/s of X)")
-    src_dtype = ds[names[0]].dtype
-    out_dtype = src_dtype if src_dtype in (np.float32, np.float64) else np.float64
-
-    def assemble(t: "torch.Tensor", lead: tuple) -> np.ndarray | None:
-        """Rank-local (*lead, rows of this rank in (variable, level, band, lon) order) pieces ->
-        the global (*lead, variable, level, latitude, longitude) host array on rank 0."""
-        parts = comm.gather_to_root(t)
-        if parts is None:
-            return None
-        if len(parts) == 1:
-            return parts[0].numpy().reshape(lead + (len(names), nlev, nlat, nlon))
-        out = np.empty(lead + (len(names), nlev, nlat, nlon), dtype=parts[0].numpy().dtype)
-        for r, part in enumerate(parts):
-            j0, j1 = lat_band(nlat, r, comm.world_size)
-            out[..., j0:j1, :] = part.numpy().reshape(lead + (len(names), nlev, j1 - j0, nlon))
-        return out
-
-    kk = res.Ut.shape[0]
-    Ug = assemble(res.Ut, (kk, d))                       # local row order k_delay*m_loc + s_loc
-    U = None if Ug is None else Ug.reshape(kk, -1).T.astype(out_dtype, copy=False)
-    s = res.s.cpu().numpy().astype(out_dtype, copy=False)
-    V = res.Vh.cpu().numpy().astype(out_dtype, copy=False)
-
-    coords = X = X_mean = X_std = None
-    if root:
-        one = space_labels(levels, lats, lons)
-        coords = delay_coords(np.tile(one, (len(names), 1)), np.repeat(names, one.shape[0]), time, d)
-    if center and d > 1:  # the reference keeps the mean / std only in this case (ref :400-414)
-        mu = assemble(torch.cat(stats["mean"]), ())
-        if root:
-            X_mean = DataArray(np.tile(mu.reshape(-1).astype(out_dtype), d), ("space",),
-                               {k_: coords[k_] for k_ in ("space", "original_variable")})
-        if scale:
-            sd = assemble(torch.cat(stats["std"]), ())
-            if root:
-                X_std = DataArray(np.tile(sd.reshape(-1).astype(out_dtype), d), ("space",),
-                                  {k_: coords[k_] for k_ in ("space", "original_variable")})
-    if parsed_config["save_data_matrix"]:
-        from .slice_tools import _apply_delay_embedding_np
-
-        n = blocks[0].shape[0]
-        nt, M = n - d + 1, sum(int(b.shape[1]) for b in blocks)
-        on_device = False
-        if not comm.exchanges and device.type == "cuda" and nt > 0:
-            free = torch.cuda.mem_get_info(device)[0] + max(
-                0, torch.cuda.memory_reserved(device) - torch.cuda.memory_allocated(device))
-            on_device = 4 * d * M * nt + (1 << 30) <= free
-        if on_device:
-            # one rank and room for it: the embedded matrix is laid out on the device as the file
-            # wants it -- (space = k_delay * M + s, time) row-major, E[k M + s, t] = X[t + k, s] -- and
-            # leaves in one copy.  (The host route below gathers the time-major blocks, embeds them
-            # column-major as the reference does and lets the writer transpose 0.8 GB: 0.27 s of the
-            # 0.73 s a warm main() takes on the reference's default config; this takes 0.06 s.)
-            Xe = torch.empty((d, M, nt), dtype=torch.float32, device=device)
-            off = 0
-            for b in blocks:
-                mb = int(b.shape[1])
-                for kd in range(d):
-                    Xe[kd, off:off + mb].copy_(b[kd:kd + nt].T)
-                off += mb
-            X = DataArray(Xe.reshape(d * M, nt).cpu().numpy().astype(out_dtype, copy=False), ("space", "time"), coords)
-            del Xe
-        else:
-            # several ranks, or no room: concatenate on the host (a device-side cat would hold X twice in HBM)
-            Xall = torch.cat(blocks, dim=1) if comm.exchanges else torch.cat([b.cpu() for b in blocks], dim=1)
-            Xg = assemble(Xall, (n,))                        # (time, variable, level, lat, lon) on rank 0
-            del Xall
-            if root:
-                Xc = Xg.reshape(n, -1).T.astype(out_dtype, copy=False)
-                X = DataArray(_apply_delay_embedding_np(np.asfortranarray(Xc), d), ("space", "time"), coords)
-    return U, s, V, coords, X, X_mean, X_std
+    return _gather_results(res, stats, blocks, job, comm, device)
 
 
 _PRIMED: set = set()

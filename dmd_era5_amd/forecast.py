@@ -43,7 +43,7 @@ import torch
 
 from .bopdmd import OptDMDResult, _phi
 from .labeled import Packing
-from .svd import Comm, _kern, _pitched, embed_view
+from .svd import Comm, _kern, _pitched, embed_view, free_device_bytes
 
 __all__ = ["svd_coefficients", "dmd_coefficients", "ensemble_coefficients", "expand_blocks", "iter_fields",
            "score_blocks", "project_blocks", "spread_blocks", "spread_score_blocks", "area_weights", "verify_blocks",
@@ -325,8 +325,7 @@ def expand_blocks(Ublocks, Ct: torch.Tensor, means=None, stds=None, delay_block:
         need = 4 * T * sum(int(U.shape[1]) for U, _ in views)
         dev = Ublocks[0].device
         if dev.type == "cuda":
-            free = torch.cuda.mem_get_info(dev)[0] + max(
-                0, torch.cuda.memory_reserved(dev) - torch.cuda.memory_allocated(dev))
+            free = free_device_bytes(dev)
             if need > free:
                 raise MemoryError(f"expand_blocks: the fields need {need} bytes ({T} snapshots x "
                                   f"{need // (4 * max(T, 1))} rows, fp32) and {free} bytes of device memory are "

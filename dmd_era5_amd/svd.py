@@ -692,6 +692,12 @@ def top_eigh(G: torch.Tensor, l: int, method: str = "auto", tol: float = 1e-9,
 BLOCK_ROWS = 131072
 
 
+def free_device_bytes(device) -> int:
+    """Free HBM: what the driver reports + what torch's allocator holds cached but unused."""
+    return int(torch.cuda.mem_get_info(device)[0] + max(
+        0, torch.cuda.memory_reserved(device) - torch.cuda.memory_allocated(device)))
+
+
 def _pitched(kern, Wt: torch.Tensor) -> torch.Tensor:
     """The small operand of K2, re-pitched ONCE for all row blocks (HipKernels.pitch)."""
     fn = getattr(kern, "pitch", None)
