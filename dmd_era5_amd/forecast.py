@@ -26,6 +26,9 @@ variable), where the field is formed and without storing it in fp32: :func:`pack
 ``DmdForecast.pack``; ``era5_svd.write_forecast_slice`` writes them.  A model fitted on the anomalies against a slot
 climatology (K18, :mod:`climatology`) takes ``climatology=`` / ``times=`` in ``DmdForecast.fields`` and ``verify`` and in
 ``write_forecast_slice``: the climatology is put back on the expanded fields, the analysis is anomalised for the scores.
+The members of a bagged fit as an ensemble forecast -- the continuous ranked probability score, area-weighted per group,
+and the rank histogram -- are K19 (``HipKernels.crps``, csrc/crps.hip): :func:`member_coefficients`,
+:func:`crps_blocks` and ``DmdForecast.ensemble_crps``; no member field is stored there either.
 
 Layout as everywhere in the package (kernels.py): a column-major matrix is held as its row-major
 transpose -- U blocks are ``(k, rows)`` (``SvdResult.Ut``), coefficients ``Ct`` are ``(T, k)``,
@@ -47,7 +50,8 @@ from .svd import Comm, _kern, _pitched, embed_view, free_device_bytes
 
 __all__ = ["svd_coefficients", "dmd_coefficients", "ensemble_coefficients", "expand_blocks", "iter_fields",
            "score_blocks", "project_blocks", "spread_blocks", "spread_score_blocks", "area_weights", "verify_blocks",
-           "pack_blocks", "pack_field_blocks", "range_blocks", "range_field_blocks", "DmdForecast"]
+           "member_coefficients", "crps_blocks", "pack_blocks", "pack_field_blocks", "range_blocks",
+           "range_field_blocks", "DmdForecast"]
 
 
 # ---------------------------------------------------------------------------
@@ -108,6 +112,28 @@ def ensemble_coefficients(results, t: torch.Tensor, ddof: int = 1) -> tuple[torc
     return Cbar.to(torch.float32).contiguous(), Dev.to(torch.float32).contiguous(), ratio
 
 
+def member_coefficients(results, t: torch.Tensor) -> tuple[torch.Tensor, float]:
+    """The members of an ensemble of fitted models (``OptDMDResult.trials`` of a bagged fit) at the times ``t``:
+    ``(Cm (B, T, k) fp32, imag_ratio)``.  Every member is evaluated as :func:`dmd_coefficients` does, in
+    complex128, and rounded once: ``Cm[b]`` is ``dmd_coefficients(results[b], t)[0]`` bit for bit.  These are the
+    members themselves (what K19 takes), not the scaled deviations of :func:`ensemble_coefficients`;
+    ``imag_ratio`` is the largest of the members'."""
+    results = list(results)
+    if not results:
+        raise ValueError("member_coefficients: no members")
+    ks = {int(r.modes.shape[0]) for r in results}
+    if len(ks) != 1:
+        raise ValueError(f"member_coefficients: the members have different numbers of coordinates {sorted(ks)}")
+    dev = results[0].eigs.device
+    tt = torch.as_tensor(t, dtype=torch.float64, device=dev).reshape(-1)
+    Z, ratio = [], 0.0
+    for r in results:
+        z, q = _model64(r, tt)
+        Z.append(z.to(torch.float32).to(dev))
+        ratio = max(ratio, q)
+    return torch.stack(Z).contiguous(), ratio
+
+
 # ---------------------------------------------------------------------------
 # one block
 # ---------------------------------------------------------------------------
@@ -164,6 +190,40 @@ def _verify(kern, Ut, Ct, Xt, mean, std, weight, clim, out, want_rows):
         out += cols
         cols = out
     return cols, (Q.sum(dim=1) if want_rows else None)
+
+
+def _crps(kern, Ut, Cm, Xt, mean, std, weight, out, hist, want_rows):
+    """K19 of one row range: (cols (2, T) fp64, rows (2, m) fp64 | None, hist (B + 1,) int64); ``out`` / ``hist`` are
+    added to."""
+    f = getattr(kern, "crps", None)
+    if f is not None:
+        return f(Ut, Cm, Xt, mean, std, weight, out=out, hist=hist, want_rows=want_rows)
+    B = int(Cm.shape[0])
+    X = Xt.to(torch.float64)
+    P = Cm.to(torch.float64) @ Ut.to(torch.float64)                 # (B, T, rows)
+    if std is not None:
+        P = P * std.to(torch.float64)
+    if mean is not None:
+        P = P + mean.to(torch.float64)
+    absq = (P - X).abs().sum(dim=0)
+    coef = 2.0 * torch.arange(1, B + 1, dtype=torch.float64, device=P.device) - (B + 1)
+    pair = (torch.sort(P, dim=0).values * coef[:, None, None]).sum(dim=0)      # sum_{b < b'} |x_b - x_b'|
+    fin = torch.isfinite(absq)
+    pair = torch.where(fin, pair, torch.full_like(pair, float("nan")))
+    rank = (P < X).sum(dim=0)
+    Q = torch.stack([absq, pair])                                   # (2, T, rows)
+    if weight is None:
+        cols, sel = Q.sum(dim=2), fin
+    else:                                                           # weight 0 leaves the row out: no 0 * NaN
+        keep = weight != 0
+        cols = (Q[:, :, keep] * weight[keep].to(torch.float64)).sum(dim=2)
+        sel = fin & keep
+    counts = torch.bincount(rank[sel].reshape(-1), minlength=B + 1).to(torch.int64)
+    if out is not None:
+        out += cols
+        hist += counts
+        cols, counts = out, hist
+    return cols, (Q.sum(dim=1) if want_rows else None), counts
 
 
 def _merge_range(P: torch.Tensor, out):
@@ -586,6 +646,112 @@ def verify_blocks(Ublocks, Ct: torch.Tensor, Xblocks, means=None, stds=None, wei
     return res
 
 
+def crps_blocks(Ublocks, Cm: torch.Tensor, Xblocks, means=None, stds=None, weights=None, groups=None, delay: int = 1,
+                comm: Comm | None = None, want_rows: bool = False, fair: bool = True, kern=None,
+                n_groups: int | None = None) -> dict:
+    """The continuous ranked probability score and the rank histogram of the B member forecasts
+    ``mean + std * (U c_b)`` against the snapshots ``Xblocks`` (the analysis) on the grid, without storing a member
+    field (K19).  ``Cm``: (B, T, k) fp32, :func:`member_coefficients`.
+
+    ``Xblocks``, ``means``, ``stds``, ``weights``, ``groups``, ``delay``, ``n_groups`` exactly as in
+    :func:`verify_blocks`: a row with weight 0 is left out whatever it holds, a negative or non-finite weight is a
+    ValueError before any launch, a group may come in several runs and be absent from a block or a rank.
+
+    With S0 = sum w sum_b |x_b - y|, S1 = sum w sum_{b < b'} |x_b - x_b'| over the rows of a group and W = the sum of
+    its weights, returns per group and snapshot (G, T)
+      ``crps`` = S0 / (B W) - S1 / (B (B - 1) W) (``fair=True``: the estimator that is unbiased for a finite
+      ensemble; B < 2 is a ValueError) or S0 / (B W) - S1 / (B^2 W) (``fair=False``: the CRPS of the empirical
+      distribution of the members; with B = 1 the weighted mean absolute error),
+      ``member_mae`` = S0 / (B W), the mean absolute error of a member, and
+      ``member_distance`` = 2 S1 / (B (B - 1) W), the mean distance between two different members (NaN for B = 1),
+    the same over all snapshots as ``*_total`` (G,), the raw ``sums`` (G, 2, T), ``rank_hist`` (G, B + 1) int64 (how
+    many selected, finite elements had r members below the analysis; flat for a calibrated ensemble), ``weight``
+    (G,), ``rows`` and ``masked_rows`` (G,) as :func:`verify_blocks`, and with ``want_rows`` the list ``row_crps``
+    of per-row vectors of the local blocks: the CRPS over time of every grid point (unweighted).
+
+    Row shards: ONE ``comm.allreduce_sum_`` of the stacked ``[sums, hist, W, rows, masked]`` per call.  A rank
+    without blocks still takes part.  The counts travel as fp64: exact below 2^53 per bin."""
+    kern = _kern(kern)
+    comm = comm or Comm()
+    if Cm.dim() != 3:
+        raise ValueError(f"crps_blocks: Cm must be (B, T, k), got {tuple(Cm.shape)}")
+    B, T = int(Cm.shape[0]), int(Cm.shape[1])
+    if fair and B < 2:
+        raise ValueError(f"crps_blocks: the fair estimator needs B >= 2 members, got {B} (pass fair=False)")
+    if weights is not None:
+        weights = list(weights)
+        for b, v in enumerate(weights):
+            x = torch.as_tensor(v).to(torch.float64)
+            bad = int((~torch.isfinite(x) | (x < 0)).sum())
+            if bad:
+                raise ValueError(f"crps_blocks: {bad} weights of block {b} are negative or not finite (a row is left "
+                                 "out with the weight 0)")
+    Ublocks, Xblocks = list(Ublocks), list(Xblocks)
+    if len(Ublocks) != len(Xblocks):
+        raise ValueError(f"crps_blocks: {len(Ublocks)} blocks of U, {len(Xblocks)} of X")
+    for b, U in enumerate(Ublocks):
+        if U.shape[1] % delay:
+            raise ValueError(f"crps_blocks: the {int(U.shape[1])} rows of U block {b} are no multiple of the delay {delay}")
+    rows_of = [int(U.shape[1]) // delay for U in Ublocks]
+    pieces, G = _group_pieces(groups, rows_of, [delay] * len(rows_of), n_groups, "crps_blocks")
+    runs = None if groups is None else [_runs(g) for g in groups]
+    Cp = _pitched_dev(kern, Cm)
+    acc = hist = None
+    meta, row_sums = torch.zeros((3, G), dtype=torch.float64), []
+    for b, (U, X) in enumerate(zip(Ublocks, Xblocks)):
+        E = embed_view(X, delay)
+        if E.shape != (T, U.shape[1]):
+            raise ValueError(f"crps_blocks: block {b} of X is {tuple(E.shape)} (delay {delay}), U and Cm ask for "
+                             f"{(T, int(U.shape[1]))}")
+        mb = rows_of[b]
+        if acc is None:
+            acc = torch.zeros((G, 2, T), dtype=torch.float64, device=U.device)
+            hist = torch.zeros((G, B + 1), dtype=torch.int64, device=U.device)
+        mean, std, w = (_vec(v, b, delay, U.device) for v in (means, stds, weights))
+        for name, v in (("means", mean), ("stds", std), ("weights", w)):
+            if v is not None and v.numel() != delay * mb:
+                raise ValueError(f"crps_blocks: {name}[{b}] has {v.numel() // delay} entries, the block {mb} rows")
+        wcpu = None if w is None else w[:mb].to(device="cpu", dtype=torch.float64)
+        for s, e, g in ([(0, mb, 0)] if runs is None else runs[b]):
+            ww = None if wcpu is None else wcpu[s:e]
+            meta[0, g] += delay * (float(e - s) if ww is None else float(ww.sum()))
+            meta[1, g] += delay * (e - s)
+            meta[2, g] += 0 if ww is None else delay * int((ww == 0).sum())
+        R = torch.zeros((2, delay * mb), dtype=torch.float64, device=U.device) if want_rows else None
+        for s, e, g in pieces[b]:
+            cut = (lambda v: None if v is None else v[s:e])
+            _, r, _ = _crps(kern, U[:, s:e], Cp, E[:, s:e], cut(mean), cut(std), cut(w), acc[g], hist[g], want_rows)
+            if want_rows:
+                R[:, s:e] = r
+        if want_rows:
+            row_sums.append(R)
+    if acc is None:        # a rank without blocks still takes part in the collective
+        acc = torch.zeros((G, 2, T), dtype=torch.float64, device=Cm.device)
+        hist = torch.zeros((G, B + 1), dtype=torch.int64, device=Cm.device)
+    flat = torch.cat([acc.reshape(-1), hist.reshape(-1).to(torch.float64), meta.reshape(-1).to(acc.device)])
+    flat = comm.allreduce_sum_(flat, tag="crps_allreduce")
+    n0, n1 = G * 2 * T, G * 2 * T + G * (B + 1)
+    sums = flat[:n0].reshape(G, 2, T)
+    rank_hist = flat[n0:n1].reshape(G, B + 1).round().to(torch.int64)
+    W, rows, masked = flat[n1:].reshape(3, G)
+    npairs = float(B * (B - 1))
+
+    def scores(S, Wn):
+        S0, S1 = S[:, 0], S[:, 1]
+        mae = S0 / (B * Wn)
+        dist = 2.0 * S1 / (npairs * Wn) if B > 1 else torch.full_like(mae, float("nan"))
+        crps = mae - S1 / ((npairs if fair else float(B * B)) * Wn)
+        return {"crps": crps, "member_mae": mae, "member_distance": dist}
+
+    res = scores(sums, W[:, None])
+    res.update({f"{key}_total": v for key, v in scores(sums.sum(dim=2), W * T).items()})
+    res.update(sums=sums, rank_hist=rank_hist, weight=W, rows=rows.to(torch.int64), masked_rows=masked.to(torch.int64))
+    if want_rows:
+        div = npairs if fair else float(B * B)
+        res["row_crps"] = [R[0] / (B * T) - R[1] / (div * T) for R in row_sums]
+    return res
+
+
 def _group_pieces(groups, rows, reps, n_groups, who):
     """-> (pieces, G): per block the list of (first row, one past the last row, group) of its launches.  ``rows``:
     the physical rows of every block, each label vector repeated for the ``reps`` delays of its block."""
@@ -967,6 +1133,33 @@ class DmdForecast:
             res["row_spread"] = sp["row_spread"]
         res["spread_skill"] = sp["spread"] / res["rmse"]
         res["spread_skill_total"] = sp["spread_total"] / res["rmse_total"] if res["rmse_total"] > 0.0 else float("inf")
+        return res
+
+    def member_coefficients(self, t) -> tuple[torch.Tensor, float]:
+        """:func:`member_coefficients` of the trials of a bagged fit, on the device of the U blocks."""
+        trials = None if self.result is None else getattr(self.result, "trials", None)
+        if not trials:
+            raise ValueError("DmdForecast: the result holds no trials; fit with bopdmd(..., num_trials > 0, "
+                             "keep_trials=True)")
+        Cm, imag = member_coefficients(trials, t)
+        k = int(self.Ublocks[0].shape[0])
+        if Cm.shape[2] != k:
+            raise ValueError(f"DmdForecast: the trials were fitted on {Cm.shape[2]} coordinates, U has {k} columns")
+        return Cm.to(self.Ublocks[0].device), imag
+
+    def ensemble_crps(self, Xblocks, t, weights=None, groups=None, comm: Comm | None = None, want_rows: bool = False,
+                      fair: bool = True, n_groups: int | None = None) -> dict:
+        """:func:`crps_blocks` of the trials of a bagged fit, as an ensemble forecast, against the snapshots
+        ``Xblocks`` at the times ``t`` (with a delay d the blocks hold len(t) + d - 1 snapshots): the area-weighted
+        CRPS per group and the rank histogram, one launch per block and group run, one collective.
+        The CRPS is translation invariant -- it depends on differences of members and analysis only -- so a model
+        fitted on anomalies is verified against the anomalised analysis (``Climatology.remove_``) and the score is
+        the score of the full fields: there is no ``climatology=`` argument.  ``imag_ratio`` is added to the
+        result."""
+        Cm, imag = self.member_coefficients(t)
+        res = crps_blocks(self.Ublocks, Cm, Xblocks, self.means, self.stds, weights, groups, self.delay, comm, want_rows,
+                          fair, self.kern, n_groups)
+        res["imag_ratio"] = imag
         return res
 
     def reconstruct_svd(self, n_components: int | None = None, cols=None, delay_block: int | None = 0,

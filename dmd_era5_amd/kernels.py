@@ -427,6 +427,57 @@ class HipKernels:
         _lib.check(rc, "dmdx_spread_score_f32")
         return var, rows
 
+    # -- K19 ----------------------------------------------------------------
+    @property
+    def crps_max_k(self) -> int:
+        return int(self._lib.dmdx_crps_max_k())
+
+    @property
+    def crps_max_members(self) -> int:
+        return int(self._lib.dmdx_crps_max_members())
+
+    def crps(self, Ut: torch.Tensor, Cm: torch.Tensor, Xt: torch.Tensor, mean: torch.Tensor | None = None,
+             std: torch.Tensor | None = None, weight: torch.Tensor | None = None, out: torch.Tensor | None = None,
+             hist: torch.Tensor | None = None, want_rows: bool = False):
+        """The sums behind the CRPS and the rank counts of the B member fields x_b = mean + std * (U c_b) against
+        X, no member field stored.  Ut: (k, m), Cm: (B, T, k) fp32 (the members' coefficients, pitched like
+        ``forecast._pitched_dev`` or not), Xt: (T, m) fp32 (the delay view included), mean / std / weight: (m,)
+        fp32 or None (0 / 1 / 1) -> (cols, rows, hist): ``cols`` a (2, T) fp64 tensor of sum_i w sum_b |x_b - x|
+        and sum_i w sum_{b < b'} |x_b - x_b'| over the rows with w != 0; ``rows`` the (2, m) fp64 sums of the same
+        two quantities over t, unweighted, or None; ``hist`` the (B + 1,) int64 counts of the rank
+        #{b : x_b < x} over the selected, finite elements.
+
+        ``out`` / ``hist``: a contiguous (2, T) fp64 and a contiguous (B + 1,) int64 tensor the sums and the counts
+        are ADDED to (row blocks, groups of rows); both or neither."""
+        m, k, ldu, T, B, Dt, ldc = self._spread_args(Ut, Cm, std, "crps")
+        if B > self.crps_max_members:
+            raise _lib.DmdxError(f"crps: {B} members, at most {self.crps_max_members}")
+        mx, Tx, ldx = _check_mat(Xt, torch.float32, "crps X")
+        if (mx, Tx) != (m, T) or Xt.device != Ut.device:
+            raise _lib.DmdxError(f"crps: X must be ({T}, {m}) on {Ut.device}, got {tuple(Xt.shape)}")
+        for v, name in ((mean, "mean"), (weight, "weight")):
+            _check_vec(v, m, Ut.device, "crps", name)
+        if (out is None) != (hist is None):
+            raise _lib.DmdxError("crps: out and hist are accumulated into together: pass both or neither")
+        if out is not None:
+            if out.shape != (2, T) or out.dtype != torch.float64 or not out.is_contiguous() or out.device != Ut.device:
+                raise _lib.DmdxError(f"crps: out must be a contiguous (2, {T}) fp64 tensor on {Ut.device}")
+            if (hist.shape != (B + 1,) or hist.dtype != torch.int64 or not hist.is_contiguous()
+                    or hist.device != Ut.device):
+                raise _lib.DmdxError(f"crps: hist must be a contiguous ({B + 1},) int64 tensor on {Ut.device}")
+            cols, counts = out, hist
+        else:
+            cols = torch.empty((2, T), dtype=torch.float64, device=Ut.device)
+            counts = torch.empty(B + 1, dtype=torch.int64, device=Ut.device)
+        rows = torch.empty((2, m), dtype=torch.float64, device=Ut.device) if want_rows else None
+        ws = self._workspace(Ut.device, self._lib.dmdx_crps_workspace_bytes(m, k, T, B))
+        rc = self._timed("crps", (m, k, T, B), lambda: self._lib.dmdx_crps_f32(
+            _ptr(Ut), m, k, ldu, _ptr(Dt), ldc, T, B, _ptr(mean), _ptr(std), _ptr(Xt), ldx, _ptr(weight),
+            _ptr(cols), T, _ptr(rows), m, _ptr(counts), int(out is not None), _ptr(ws), ws.numel(), self._stream()
+        ))
+        _lib.check(rc, "dmdx_crps_f32")
+        return cols, rows, counts
+
     # -- K13 ----------------------------------------------------------------
     @property
     def project_max_k(self) -> int:

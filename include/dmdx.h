@@ -66,7 +66,10 @@
  *     -- with accumulate == 0 -- var_col is written, nothing else.  S, U and sigma are addressed with 64-bit
  *     offsets and one dword per lane: no alignment is asked for and none selects another path; a 16-byte aligned D
  *     with ldd % 4 == 0 is staged with 16-byte loads, with identical values.  m, T, B T and every leading
- *     dimension must be < 2^31 (DMDX_E_INVALID beyond, before anything is written).
+ *     dimension must be < 2^31 (DMDX_E_INVALID beyond, before anything is written);
+ *   - K19 (dmdx_crps_f32): U, C (k x (B T)), mu, sigma, X and w are only read, inside their logical elements; every
+ *     logical element of row and -- with accumulate == 0 -- of col and hist is written, nothing else; addressing
+ *     and alignment as K15.
  *
  * Value contract (tests/test_gpu_value_domain.py holds every fp32 entry point to it)
  *   - NaN / Inf propagate like IEEE arithmetic on the logical operands, nothing more and nothing less:
@@ -426,6 +429,61 @@ int dmdx_verify_f32(const float* U, int64_t m, int64_t k, int64_t ldu, const flo
                     const float* w, const float* clim, double* col, int64_t ldcol,
                     double* row, int64_t ldrow, int accumulate,
                     void* workspace, size_t workspace_bytes, void* stream);
+
+/* ---- K19: fair CRPS and rank histogram of B member fields on the grid ------------------------------------------
+ * What an ensemble forecast of gridded fields is published with besides its spread-skill ratio: the continuous
+ * ranked probability score, area-weighted, and the rank histogram -- without storing a member field.  The operands
+ * are K16's -- U (m x k, ldu), mu / sigma (m floats each, nullable: 0 / 1), X (m x T, ldx; rows > ldx allowed, the
+ * zero-copy delay view), w (m floats, nullable: 1) -- but C (k x (B T), ldc) carries the members the way K15's D
+ * does: column b T + t holds the coefficients of member b at snapshot t (the members themselves, not deviations).
+ * 1 <= k <= dmdx_crps_max_k() (256), 1 <= B <= dmdx_crps_max_members() = DMDX_CRPS_MAX_B (256).  Per element, fp32:
+ *   x_b  = sigma * acc_b + mu        K12's chain over k for the columns of member b and K12's two-step epilogue:
+ *                                    member b's field is bit for bit what dmdx_expand_f32 gives for C_b
+ *   abs  = sum_b |x_b - y|           y = X[i, t]; b = 0, 1, ... in this order, each term rounded once
+ *   pair = sum_{b < b'} |x_b - x_b'| each term rounded once; ONE fp32 chain of B (B - 1) / 2 terms per element, in an
+ *                                    order that depends on (B, k) only (members are held in registers in blocks of
+ *                                    DMDX_CRPS_MEMBER_BLOCK_SMALL_K = 16 for k <= 128 and DMDX_CRPS_MEMBER_BLOCK = 8
+ *                                    above, and the chains of the later members are repeated per block); where abs
+ *                                    is not finite pair is made NaN
+ *   rank = #{ b : x_b < y }          an integer in 0 .. B; a tie counts as "not below"
+ * and the outputs
+ *   col[q * ldcol + t] (+)= sum over the rows i with w[i] != 0 of fl(w[i] * quantity_q[i, t])    ldcol >= T
+ *                           q = 0: abs, q = 1: pair (DMDX_CRPS_NQ = 2)
+ *   row[q * ldrow + i]  =  sum_t quantity_q[i, t]       nullable, ldrow >= m, unweighted, always overwritten
+ *   hist[r]           (+)= number of elements (i, t) with w[i] != 0, a FINITE abs[i, t], and rank == r
+ *                           B + 1 int64, nullable
+ * The host forms the scores: CRPS = col0 / (B W) - col1 / (B (B - 1) W) (the fair estimator) or
+ * col0 / (B W) - col1 / (B^2 W) (the plain ensemble estimator), W = sum of the weights.
+ * A row with w[i] == 0 is SELECTED out of col and hist, whatever it holds; its `row` sums are the plain sums.  With
+ * every w == 0 col is +0.0 and hist is 0.  accumulate != 0 adds to col and hist (row blocks; a group of rows is a
+ * pointer offset); otherwise every logical element of col and hist is written and none read.
+ * Sums as K16's: fp32 over at most DMDX_CRPS_FP32_ROWS rows (columns: the rows of one workgroup; rows: 16
+ * snapshots), fp64 beyond, through per-workgroup partial slots in the workspace and reduce kernels.  No
+ * floating-point atomics: the order of every fp sum depends on (m, T, B, k) only, two calls give the same bits.  The
+ * counts are integers: a workgroup counts a tile in 32-bit LDS counters (integer atomics; a tile has 128 x 32 = 4096
+ * elements, and the counters are emptied into 64-bit registers after every tile, so no width overflows for any T),
+ * writes its 64-bit counts to its own slot of the workspace, and a reduce kernel adds the slots.
+ * Values: a non-finite X[i, t] with w[i] != 0 makes column t of both sums non-finite and row i of `row`; that
+ * element enters no bin.  A non-finite U[i, j], mu[i] or sigma[i] does the same to row i and, if w[i] != 0, to every
+ * column.  Everything else keeps its bits.  Integer operands with power-of-two w and partial sums below 2^24 give
+ * exact integers; identical members give pair == +0.0 exactly; (2^e U, 2^-e C) changes no bit.
+ * Memory as for K12 / K16: only logical elements are read or written, the workspace is exactly
+ * dmdx_crps_workspace_bytes(m, k, T, B) and needs no initialisation, no alignment is required.  m, T, B T and the
+ * leading dimensions must be < 2^31.  A refused call (DMDX_E_INVALID: a null U, C, X or col, k outside 1 .. 256, B
+ * outside 1 .. DMDX_CRPS_MAX_B, ldu < m, ldc < k, ldx < 1, ldcol < T, ldrow < m with row given, a size >= 2^31;
+ * DMDX_E_WORKSPACE: a null or short workspace) has written nothing. */
+#define DMDX_CRPS_NQ 2
+#define DMDX_CRPS_FP32_ROWS 128
+#define DMDX_CRPS_MAX_B 256
+#define DMDX_CRPS_MEMBER_BLOCK 8
+#define DMDX_CRPS_MEMBER_BLOCK_SMALL_K 16
+int dmdx_crps_max_k(void);
+int dmdx_crps_max_members(void);
+size_t dmdx_crps_workspace_bytes(int64_t m, int64_t k, int64_t T, int64_t B);
+int dmdx_crps_f32(const float* U, int64_t m, int64_t k, int64_t ldu, const float* C, int64_t ldc, int64_t T, int64_t B,
+                  const float* mu, const float* sigma, const float* X, int64_t ldx, const float* w,
+                  double* col, int64_t ldcol, double* row, int64_t ldrow, int64_t* hist, int accumulate,
+                  void* workspace, size_t workspace_bytes, void* stream);
 
 /* ---- K14: CF-packed int16 codes -> fp32 snapshots of one row block ---------------------------------------------
  * What xr.open_dataset's mask_and_scale decoding (reference era5_svd.py:132 through retrieve_era5_slice) does to a
