@@ -92,6 +92,8 @@ SIGNATURES = {
     "dmdx_clim_mean_f32": (C.c_int, [_p, _i64, _i64, _i64, _p, _i64, _p, _i64, _p, _i64, _p]),
     "dmdx_clim_std_f32": (C.c_int, [_p, _i64, _i64, _i64, _p, _i64, _p, _i64, _p, _i64, C.c_int, _p, _i64, _p]),
     "dmdx_clim_apply_f32": (C.c_int, [_p, _i64, _i64, _i64, _p, _i64, _p, _i64, _p, _i64, C.c_int, _p, _i64, _p]),
+    "dmdx_row_missing_count_f32": (C.c_int, [_p, _i64, _i64, _i64, _p, _p]),
+    "dmdx_row_mask_apply_f32": (C.c_int, [_p, _i64, _i64, _i64, _p, C.c_float, _p]),
     "dmdx_pack_triu_f64": (C.c_int, [_p, _i64, _i64, _p, _p]),
     "dmdx_unpack_triu_f64": (C.c_int, [_p, _i64, _p, _i64, _p]),
     "dmdx_exp_basis": (C.c_int, [_p, _p, _i64, _i64, _p, _p, C.c_int, _p]),

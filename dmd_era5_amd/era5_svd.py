@@ -20,7 +20,13 @@ DVC (``use_dvc=True``) is out of scope and raises.
 
 Optional engine keys in the config dict (absent from the reference, defaults reproduce
 its behaviour): ``svd_seed`` (int, makes "randomized" reproducible), ``n_oversamples``,
-``n_iter``.
+``n_iter``, and ``missing``: ``"raise"`` (the default) refuses a slice with missing values;
+``"mask"`` takes every grid point that is missing (fill value, NaN, Inf) in at least one selected
+snapshot out of the decomposition (K20: its rows of X are zero, so are its rows of U) and
+returns it as missing: the result gains ``space_mask`` (int8 over ``space``, 1 = used) and the
+attributes ``missing`` / ``masked_points``, ``X_mean`` / ``X_std`` are NaN there, and
+``reconstruct_from_svd_results`` / ``write_forecast_slice`` give NaN / ``_FillValue`` at those
+points.  Sea-surface temperature, missing over land in every file, needs it.
 """
 from __future__ import annotations
 
@@ -67,6 +73,18 @@ _console.setFormatter(logging.Formatter("%(asctime)s - %(name)s - %(levelname)s 
 logger.addHandler(_console)
 
 _ENGINE_KEYS = {"svd_seed": "random_state", "n_oversamples": "n_oversamples", "n_iter": "n_iter"}
+
+
+MISSING_MODES = ("raise", "mask")
+
+
+def _missing_mode(config: dict) -> str:
+    """The engine-only key ``missing`` of a config / parsed config; absent means "raise"."""
+    mode = config.get("missing", "raise")
+    if mode not in MISSING_MODES:
+        raise ValueError(f'missing = {mode!r} is not supported: use "raise" (refuse a slice with missing values, '
+                         'the default) or "mask" (leave the affected grid points out of the decomposition)')
+    return mode
 
 
 def _engine_opts(parsed_config: dict) -> dict:
@@ -193,7 +211,10 @@ def svd_on_era5(da, parsed_config: dict):
 
 def combine_svd_results(U, s, V, coords, **kwargs) -> Dataset:
     """U(space, components), s(components), V(components, time) [+ X, X_mean, X_std] as
-    one Dataset with the coordinates of the decomposed array (ref :266-333)."""
+    one Dataset with the coordinates of the decomposed array (ref :266-333).  ``space_mask=`` (with
+    ``masked_points=``, the number of grid points left out): the result of ``missing = "mask"`` -- one more
+    variable ``space_mask`` over ``space`` (int8, 1 = used in the decomposition) and the attributes ``missing``
+    and ``masked_points``; absent otherwise."""
     comp = np.arange(U.shape[1])
     row = {k: coords[k] for k in ("space", "original_variable", "delay") if k in coords}
     cds = dict(coords)
@@ -206,6 +227,18 @@ def combine_svd_results(U, s, V, coords, **kwargs) -> Dataset:
     for key in ("X", "X_mean", "X_std"):
         if kwargs.get(key) is not None:
             ds[key] = kwargs[key]
+    if kwargs.get("space_mask") is not None:
+        # missing = "mask": which rows took part (1) and which were left out and are missing in every product (0)
+        mask = kwargs["space_mask"]
+        if not isinstance(mask, DataArray):
+            mask = DataArray(np.asarray(mask).astype(np.int8), ("space",), {k: v for k, v in row.items() if k != "delay"})
+        ds["space_mask"] = mask
+        ds.attrs["missing"] = "mask"
+        points = kwargs.get("masked_points")
+        if points is None:                           # (grid points, not embedded rows: every delay block repeats them)
+            d = int(np.unique(coords["delay"].values).size) if "delay" in coords else 1
+            points = int((np.asarray(mask.values) == 0).sum()) // d
+        ds.attrs["masked_points"] = int(points)
     return ds
 
 
@@ -220,7 +253,9 @@ def reconstruct_from_svd_results(svd_ds: Dataset, n_components: int | None = Non
     ``destandardize``: apply ``X_std`` and ``X_mean`` when the file has them (it has them only for a
     delay embedding d > 1 -- the reference's quirk, ref :400-414 -- so for d = 1 the standardized
     matrix is what comes back either way).  fp32 results are formed by K12 on the device in row
-    blocks; float64 results (the small-slice fp64 route) take the library's fp64 product."""
+    blocks; float64 results (the small-slice fp64 route) take the library's fp64 product.
+    A result of ``missing = "mask"`` comes back with NaN at the masked points: through their NaN mean
+    when the mean is applied, through K20 on the expanded block otherwise."""
     U, s, V = (np.asarray(svd_ds[k].values) for k in ("U", "s", "V"))
     k = int(s.shape[0])
     r = k if n_components is None else int(n_components)
@@ -231,17 +266,21 @@ def reconstruct_from_svd_results(svd_ds: Dataset, n_components: int | None = Non
     mu = np.asarray(svd_ds["X_mean"].values) if destandardize and "X_mean" in names else None
     sd = np.asarray(svd_ds["X_std"].values) if destandardize and "X_std" in names else None
     M = int(U.shape[0])
+    # a result of missing = "mask": NaN at the masked points -- through the NaN of their mean where there is one
+    gone = np.asarray(svd_ds["space_mask"].values) == 0 if "space_mask" in names and mu is None else None
     if U.dtype == np.float64:
         X = (U[:, :r] * s[:r]) @ V[:r][:, tidx]
         if sd is not None:
             X *= sd[:, None]
         if mu is not None:
             X += mu[:, None]
+        if gone is not None:
+            X[gone] = np.nan
     else:
         import torch
 
         from . import forecast
-        from .svd import _kern, split_rows
+        from .svd import _kern, row_mask_apply_, split_rows
 
         kern = _kern(kern)
         dev = torch.device("cuda" if getattr(kern, "name", "") == "hip" else "cpu")
@@ -252,6 +291,8 @@ def reconstruct_from_svd_results(svd_ds: Dataset, n_components: int | None = Non
             Ut = torch.from_numpy(np.ascontiguousarray(U[a:b, :r].T.astype(np.float32, copy=False))).to(dev)
             vec = [None if v is None else [torch.from_numpy(np.ascontiguousarray(v[a:b], dtype=np.float32))] for v in (mu, sd)]
             (Xt,) = forecast.expand_blocks([Ut], Ct, vec[0], vec[1], kern=kern)
+            if gone is not None:
+                row_mask_apply_(kern, Xt, torch.from_numpy(gone[a:b].astype(np.int32)).to(dev), float("nan"))
             X[a:b] = Xt.T.cpu().numpy()
             del Xt, Ut
     row = {c: svd_ds.coords[c] for c in ("space", "original_variable", "delay", "time") if c in svd_ds.coords}
@@ -442,7 +483,10 @@ def project_onto_svd_results(svd_ds: Dataset, X, n_components: int | None = None
     ``(components, time)`` DataArray in U's dtype, with the time coordinate of ``X`` if it has one; attrs
     ``energy_total`` = ||(X - mean) / std||_F^2 and ``captured_total`` = the part of it the r columns hold.
     fp32 results are formed by K13 on the device in row blocks, X read once; float64 ones (the small-slice
-    fp64 route) take the library's fp64 product."""
+    fp64 route) take the library's fp64 product.
+    A result of ``missing = "mask"`` brings its ``space_mask``: the masked rows of ``X`` (missing there too) take
+    no part -- they are zeroed on the device copy, ``X`` itself is not changed -- and ``energy_total`` counts the
+    used points only."""
     U = np.asarray(svd_ds["U"].values)
     k = int(U.shape[1])
     r = k if n_components is None else int(n_components)
@@ -466,8 +510,15 @@ def project_onto_svd_results(svd_ds: Dataset, X, n_components: int | None = None
     if sd is not None and (sd == 0).any():
         raise ValueError(f"{int((sd == 0).sum())} entries of std are zero")
     T = int(Xv.shape[1])
+    # a result of missing = "mask": the masked rows are missing in X too -- they count as 0, their mean / std as 0 / 1
+    used = np.asarray(svd_ds["space_mask"].values) != 0 if "space_mask" in names else None
+    if used is not None:
+        mu = None if mu is None else np.where(used, mu, 0.0)
+        sd = None if sd is None else np.where(used, sd, 1.0)
     if U.dtype == np.float64:
         Xs = Xv.astype(np.float64)
+        if used is not None:
+            Xs[~used] = 0.0
         if mu is not None:
             Xs = Xs - mu[:, None]
         if sd is not None:
@@ -487,10 +538,16 @@ def project_onto_svd_results(svd_ds: Dataset, X, n_components: int | None = None
         def f32(a):
             return torch.from_numpy(np.ascontiguousarray(a, dtype=np.float32))
 
+        def snapshots(a, b):
+            x = f32(Xv[a:b].T)
+            # (project_blocks zeroes the masked rows in place: on a copy of the caller's array, never on the array)
+            return x.clone() if used is not None and dev.type == "cpu" else x.to(dev)
+
         res = forecast.project_blocks(
-            (f32(U[a:b, :r].T).to(dev) for a, b in blocks), (f32(Xv[a:b].T).to(dev) for a, b in blocks),
+            (f32(U[a:b, :r].T).to(dev) for a, b in blocks), (snapshots(a, b) for a, b in blocks),
             None if mu is None else [f32(mu[a:b]) for a, b in blocks],
-            None if sd is None else [f32(sd[a:b]) for a, b in blocks], kern=kern)
+            None if sd is None else [f32(sd[a:b]) for a, b in blocks], kern=kern,
+            masks=None if used is None else [used[a:b] for a, b in blocks])
         C = res["Ct"].T.cpu().numpy().astype(U.dtype)
         energy = res["energy_total"]
     coords = {"components": Coord("components", np.arange(r))}
@@ -600,9 +657,54 @@ def _raise_on_fill_codes(found, comm, device, where: str = "the selected slice")
     if bad:
         what = ", ".join(f"variable {k}: {v} missing values (fill codes)" for k, v in bad.items())
         msg = (f"{what} in {where}; an SVD of data with missing values is not defined -- "
-               "select levels / times without them or fill them before the decomposition")
+               "select levels / times without them or fill them before the decomposition"
+               ' (or set missing = "mask" to leave the affected grid points out of it)')
         log_and_print(logger, msg, "error")
         raise ValueError(msg)
+
+
+def _report_missing(names, counts, n: int, comm, device) -> int:
+    """``missing = "mask"``: what was taken out of the decomposition.  ``counts``: per variable the int32 row
+    counts of K20 (one vector per row block / piece of this rank, physical rows), the same variables on every rank;
+    ``n``: the selected snapshots.  One all-reduce of [missing values, masked points, points, points that are only
+    partly missing] per variable, made where ``_raise_on_fill_codes`` makes its own, so that every rank arrives; one
+    log line per variable (a warning when a point with valid snapshots is dropped); if no point is left over all
+    variables and ranks, every rank raises.  -> the masked points of all variables and ranks."""
+    import torch
+
+    v = torch.zeros((len(names), 4), dtype=torch.int64, device=device)
+    for i, per_block in enumerate(counts):
+        for c in per_block:
+            on = c != 0
+            v[i] += torch.stack([c.sum(dtype=torch.int64), on.sum(), torch.tensor(c.numel(), device=c.device),
+                                 (on & (c < n)).sum()]).to(device)
+    if comm.exchanges:
+        comm.allreduce_sum_(v, tag="missing_allreduce")
+    masked_all = points_all = 0
+    for name, (values, masked, points, partly) in zip(names, v.tolist()):
+        masked_all, points_all = masked_all + masked, points_all + points
+        msg = (f"variable {name}: {values} missing values, {masked} of {points} grid points masked out of the "
+               f"decomposition ({partly} of them missing in only a part of the {n} snapshots)")
+        if partly:
+            log_and_print(logger, "WARNING: " + msg + ": their valid snapshots are dropped with them", "warning")
+        else:
+            log_and_print(logger, msg)
+    if masked_all == points_all:
+        msg = (f"all {points_all} grid points of the selected slice have a missing value in at least one snapshot: "
+               'missing = "mask" leaves nothing to decompose')
+        log_and_print(logger, msg, "error")
+        raise ValueError(msg)
+    return int(masked_all)
+
+
+def _mask_block_(kern, Xb, cnt, mu, sd) -> None:
+    """The masked rows (count != 0) of a centred / scaled block become 0, their means / stds NaN."""
+    from . import svd as dsvd
+
+    dsvd.row_mask_apply_(kern, Xb, cnt, 0.0)
+    for v in (mu, sd):
+        if v is not None:
+            v.masked_fill_(cnt != 0, float("nan"))
 
 
 def _upload_packed_i16(lazy, level_idx, take, step, band, ranges, blocks, device, kern, count_fills):
@@ -760,7 +862,8 @@ def _upload_host_decode(da, level_idx, take, band, rows, ranges, blocks, device,
     return nbytes, nan_count
 
 
-def _upload_variable(da: DataArray, level_idx, take, device, kern, center, scale, stats, band=None, pad4=False):
+def _upload_variable(da: DataArray, level_idx, take, device, kern, center, scale, stats, band=None, pad4=False,
+                     missing: str = "raise"):
     """One variable (time, level, lat, lon) -> centred/scaled row blocks (time, rows) in HBM.
 
     ``pad4``: a variable whose number of space points is not a multiple of 4 (a grid with an odd
@@ -783,7 +886,11 @@ def _upload_variable(da: DataArray, level_idx, take, device, kern, center, scale
     selected levels / latitude band; a regular resampling is compacted while it is read -- so
     neither ``all_levels`` nor a contiguous ``take`` is asked for.  Every other packed case is
     decoded on the host (same arithmetic) by the host route.  A variable that declares fill codes
-    appends (name, number of them in the selection) to ``stats["fills"]``."""
+    appends (name, number of them in the selection) to ``stats["fills"]``.
+
+    ``missing = "mask"``: behind the last slab, whichever route ran, K20 counts the non-finite snapshots
+    of every row of every block (``stats["count"]``, int32 per block), K5 runs unchanged, and the rows
+    with a count become 0 in X and NaN in the means / stds; nothing goes to ``stats["fills"]``."""
     import torch
 
     from . import svd as dsvd
@@ -820,14 +927,22 @@ def _upload_variable(da: DataArray, level_idx, take, device, kern, center, scale
         nbytes, found = _upload_direct_f32(lazy, take, band, rows, ranges, blocks, device, declared)
     else:
         nbytes, found = _upload_host_decode(da, level_idx, take, band, rows, ranges, blocks, device, declared)
-    if found is not None:
+    mask = missing == "mask"
+    if found is not None and not mask:
         stats.setdefault("fills", []).append((da.name, found))
     for (a, b), Xb in zip(ranges, blocks):
+        mu = sd = None
+        # (every variable is counted, whether it declares a fill value or merely holds a NaN; the pad rows are not)
+        cnt = dsvd.row_missing_count(kern, Xb[:, : b - a]) if mask else None
         if center:
+            # (rows are independent: a NaN spoils its own row only)
             mu, sd = kern.row_center_scale_(Xb[:, : b - a], bool(scale))   # (the zero rows stay zero: 0 / 0 otherwise)
             stats["mean"].append(mu)
             if scale:
                 stats["std"].append(sd)
+        if mask:
+            _mask_block_(kern, Xb[:, : b - a], cnt, mu, sd)
+            stats.setdefault("count", []).append(cnt)
     return blocks, m_v, nbytes
 
 
@@ -858,6 +973,7 @@ class _Job:
     wide: bool             # fewer rows than embedded snapshots
     can_stream: bool
     shard: str             # " (rank r of N: latitude rows i0:i1)" for the log lines, "" for a single rank
+    missing: str = "raise"  # "mask": grid points with a missing value are left out of the decomposition
 
     @property
     def n(self) -> int:
@@ -892,7 +1008,8 @@ def _plan_job(ds: Dataset, parsed_config: dict, comm) -> _Job:
         # matrix is not asked for (un-centred standard SVD included: the exact mean deflation centres
         # the pieces as they pass; a spectrum steeper than the Gram resolves costs one more pass)
         can_stream=not wide and not parsed_config["save_data_matrix"],
-        shard=f" (rank {comm.rank} of {comm.world_size}: latitude rows {band[0]}:{band[1]})" if band else "")
+        shard=f" (rank {comm.rank} of {comm.world_size}: latitude rows {band[0]}:{band[1]})" if band else "",
+        missing=_missing_mode(parsed_config))
 
 
 def _sync(device) -> None:
@@ -958,6 +1075,7 @@ class _StreamedPieces:
     def __init__(self, ds, job: _Job, comm, kern, device, sub):
         self.ds, self.job, self.comm, self.kern, self.device, self.sub = ds, job, comm, kern, device, sub
         self.means, self.stds, self.fills, self.moved = {}, {}, {}, 0
+        self.counts = {}      # missing = "mask": the K20 row counts per piece (a function of its data: every pass the same)
 
     def __call__(self):
         import torch
@@ -967,7 +1085,9 @@ class _StreamedPieces:
             for j0, j1 in self.sub:
                 st = {"mean": [], "std": []}
                 vb, _, nbytes = _upload_variable(self.ds[name], job.level_idx, job.take, self.device, self.kern,
-                                                 job.center, job.scale, st, (j0, j1))
+                                                 job.center, job.scale, st, (j0, j1), missing=job.missing)
+                if job.missing == "mask":
+                    self.counts[(vi, j0)] = torch.cat(st["count"])
                 if st.get("fills"):
                     # one rank: the piece is refused before it reaches a Gram or a product.  Several
                     # ranks: the ranks have different numbers of pieces, so there is no common point
@@ -1014,8 +1134,17 @@ def _svd_streamed(ds: Dataset, job: _Job, comm, kern, device, stream_bytes: int)
                                                                kern=kern, **job.engine_opts)
     except np.linalg.LinAlgError as e:          # (raised on all-reduced quantities: by every rank or by none)
         failed = e
+    except Exception as e:                      # missing = "mask" with nothing left: the report below says so
+        if job.missing != "mask":
+            raise
+        failed = e
     declared = [nm for nm in names if any(key in getattr(ds[nm], "encoding", {}) for key in ("_FillValue", "missing_value"))]
-    if comm.exchanges and declared:
+    masked_points = None
+    if job.missing == "mask":
+        # (the same place as the summed fill-code check below: every rank arrives here)
+        masked_points = _report_missing(names, [[pieces.counts[(vi, j0)] for j0, _ in sub if (vi, j0) in pieces.counts]
+                                                for vi in range(len(names))], job.n, comm, device)
+    elif comm.exchanges and declared:
         # several ranks: ONE summed check here, where every rank arrives whether the SVD raised or returned
         local = {}
         for (vi, _), (nm, c) in sorted(pieces.fills.items()):
@@ -1029,6 +1158,7 @@ def _svd_streamed(ds: Dataset, job: _Job, comm, kern, device, stream_bytes: int)
     Ul = torch.empty((kk, d, len(names), nlev, i1 - i0, nlon), dtype=torch.float32, device=device)
     mean_l = torch.empty((len(names), nlev, i1 - i0, nlon), dtype=torch.float32, device=device)
     std_l = torch.empty_like(mean_l) if job.scale else None
+    count_l = torch.zeros(mean_l.shape, dtype=torch.int32, device=device) if job.missing == "mask" else None
     idx = 0
     for vi in range(len(names)):
         for j0, j1 in sub:      # a piece's rows: (level, its latitude rows, longitude), embedded as k_delay * m_piece + s
@@ -1037,17 +1167,24 @@ def _svd_streamed(ds: Dataset, job: _Job, comm, kern, device, stream_bytes: int)
                 mean_l[vi, :, j0 - i0:j1 - i0, :] = pieces.means[(vi, j0)].reshape(nlev, j1 - j0, nlon)
             if job.scale:
                 std_l[vi, :, j0 - i0:j1 - i0, :] = pieces.stds[(vi, j0)].reshape(nlev, j1 - j0, nlon)
+            if count_l is not None:
+                count_l[vi, :, j0 - i0:j1 - i0, :] = pieces.counts[(vi, j0)].reshape(nlev, j1 - j0, nlon)
             Ub[idx] = None
             idx += 1
     res = dsvd.SvdResult(Ut=Ul.reshape(kk, -1), s=s_, Vh=Vh_, info=sinfo)
-    return res, {"mean": [mean_l.reshape(-1)], "std": [std_l.reshape(-1)] if job.scale else [], "moved": pieces.moved}
+    stats = {"mean": [mean_l.reshape(-1)], "std": [std_l.reshape(-1)] if job.scale else [], "moved": pieces.moved}
+    if count_l is not None:
+        stats["count"], stats["masked_points"] = [count_l.reshape(-1)], masked_points
+        res = _mask_u_rows(res, stats["count"], d, kern)
+    return res, stats
 
 
 # ---- the resident run
 def _ingest_resident(ds: Dataset, job: _Job, comm, kern, device):
     """Every variable of this rank's band -> centred / scaled row blocks in HBM.
     -> (blocks, true_rows, stats, bytes moved); ``true_rows``: the width of every block without the zero rows
-    ``pad4`` appended.  Missing values raise here, before any SVD work."""
+    ``pad4`` appended.  Missing values raise here, before any SVD work -- or, with ``missing = "mask"``, are
+    reported here (``stats["count"]`` per block, ``stats["masked_points"]`` over all ranks)."""
     from . import svd as dsvd
 
     # `python -m dmd_era5.era5_svd.era5_svd` is one process per slice: every run is a "first
@@ -1061,17 +1198,23 @@ def _ingest_resident(ds: Dataset, job: _Job, comm, kern, device):
     primer = _prime_async(device, job.svd_type) if device.type == "cuda" and \
         4 * job.rows_local * job.n >= prime_min else None
     blocks, true_rows, stats, total = [], [], {"mean": [], "std": []}, 0
+    per_variable = []
     for name in job.names:
         # (a tall problem on a grid whose space-point count is not a multiple of 4: 1-3 zero rows per variable)
+        seen = len(stats.get("count", []))
         vb, m_v, nbytes = _upload_variable(ds[name], job.level_idx, job.take, device, kern, job.center, job.scale,
-                                           stats, job.band, pad4=not job.wide)
+                                           stats, job.band, pad4=not job.wide, missing=job.missing)
         blocks.extend(vb)
         true_rows.extend(b - a for a, b in dsvd.split_rows(m_v))
+        per_variable.append(stats.get("count", [])[seen:])
         total += nbytes
     if primer is not None:
         primer.join()
     _sync(device)
-    _raise_on_fill_codes(stats.get("fills"), comm, device)
+    if job.missing == "mask":
+        stats["masked_points"] = _report_missing(job.names, per_variable, job.n, comm, device)
+    else:
+        _raise_on_fill_codes(stats.get("fills"), comm, device)
     return blocks, true_rows, stats, total
 
 
@@ -1122,8 +1265,27 @@ def _drop_pad_rows(res, blocks, true_rows, d: int):
     return dsvd.SvdResult(Ut=Ut, s=res.s, Vh=res.Vh, info=res.info), [b[:, :r] for b, r in zip(blocks, true_rows)]
 
 
-def _svd_resident(blocks, true_rows, job: _Job, comm, kern):
-    """-> (SvdResult on this rank's true rows, the row blocks without their pad rows)."""
+def _mask_u_rows(res, counts, d: int, kern):
+    """``missing = "mask"``: the rows of U of the masked grid points, in every delay block, are set to 0 (K20 on
+    the (k, rows) blocks of U^T).  Zero rows of X give exactly zero rows of U already; this also covers the
+    orthonormal completion of a rank-deficient slice, which writes into every column.  ``counts``: the int32 row
+    counts of this rank's physical rows, in row order."""
+    import torch
+
+    from . import svd as dsvd
+
+    cnt = torch.cat(list(counts))
+    kk = res.Ut.shape[0]
+    Ut = res.Ut.contiguous()
+    per_delay = Ut.view(kk, d, -1)
+    for kd in range(d):
+        dsvd.row_mask_apply_(kern, per_delay[:, kd], cnt, 0.0)
+    return dsvd.SvdResult(Ut=Ut, s=res.s, Vh=res.Vh, info=res.info)
+
+
+def _svd_resident(blocks, true_rows, job: _Job, comm, kern, counts=None):
+    """-> (SvdResult on this rank's true rows, the row blocks without their pad rows).  ``counts``: the row counts
+    of ``missing = "mask"`` (``_mask_u_rows``)."""
     from . import svd as dsvd
 
     if job.wide:
@@ -1141,7 +1303,9 @@ def _svd_resident(blocks, true_rows, job: _Job, comm, kern):
         res = dsvd.svd_randomized(blocks, job.k, delay=job.d, comm=comm, kern=kern, **job.engine_opts)
         log_and_print(logger, "Randomized SVD complete.")
     if any(int(b.shape[1]) != r for b, r in zip(blocks, true_rows)):
-        return _drop_pad_rows(res, blocks, true_rows, job.d)
+        res, blocks = _drop_pad_rows(res, blocks, true_rows, job.d)
+    if counts is not None:
+        res = _mask_u_rows(res, counts, job.d, kern)
     return res, blocks
 
 
@@ -1207,9 +1371,17 @@ def _data_matrix(blocks, job: _Job, comm, device, coords) -> DataArray | None:
     return DataArray(_apply_delay_embedding_np(np.asfortranarray(Xc), d), ("space", "time"), coords)
 
 
-def _gather_results(res, stats, blocks, job: _Job, comm, device):
+def _space_mask(used, d: int, coords) -> DataArray:
+    """``used``: bool over the physical grid points in row order -> ``space_mask``: int8 over the embedded
+    ``space`` axis, 1 = the point took part in the decomposition."""
+    return DataArray(np.tile(np.asarray(used).astype(np.int8), d), ("space",),
+                     {k: coords[k] for k in ("space", "original_variable") if k in coords})
+
+
+def _gather_results(res, stats, blocks, job: _Job, comm, device, extras: dict | None = None):
     """The row-sharded results -> what ``_device_pipeline`` returns: U, then the row means and stds, then X
-    are gathered to rank 0 in the global row order; the other ranks get None for them and for the coords."""
+    are gathered to rank 0 in the global row order; the other ranks get None for them and for the coords.
+    ``missing = "mask"``: ``extras`` receives ``space_mask`` (rank 0; None elsewhere) and ``masked_points``."""
     kk = res.Ut.shape[0]
     Ug = _assemble(res.Ut, (kk, job.d), job, comm)       # local row order k_delay*m_loc + s_loc
     U = None if Ug is None else Ug.reshape(kk, -1).T.astype(job.out_dtype, copy=False)
@@ -1225,10 +1397,16 @@ def _gather_results(res, stats, blocks, job: _Job, comm, device):
             X_std = _row_vector(stats["std"], job, comm, coords)
     if job.save_data_matrix:
         X = _data_matrix(blocks, job, comm, device, coords)
+    if job.missing == "mask" and extras is not None:
+        import torch
+
+        cnt = _assemble(torch.cat(stats["count"]), (), job, comm)       # one more small gather, made by every rank
+        extras["masked_points"] = stats["masked_points"]
+        extras["space_mask"] = None if cnt is None else _space_mask(cnt.reshape(-1) == 0, job.d, coords)
     return U, s, V, coords, X, X_mean, X_std
 
 
-def _device_pipeline(ds: Dataset, parsed_config: dict, comm=None, kern=None, device=None):
+def _device_pipeline(ds: Dataset, parsed_config: dict, comm=None, kern=None, device=None, extras: dict | None = None):
     """Slice -> (U, s, V, coords, X, X_mean, X_std) with X resident only in HBM.
 
     Row order = the reference's flatten order (variable-major, then level, latitude,
@@ -1243,6 +1421,10 @@ def _device_pipeline(ds: Dataset, parsed_config: dict, comm=None, kern=None, dev
     ``kern`` / ``device``: the kernel provider and where the row blocks live -- the HIP kernels
     on the current GPU unless a test injects its CPU double (main() never does: without
     libdmdx.so or a GPU ``default_kernels()`` raises).
+
+    ``extras``: a dict that receives what ``missing = "mask"`` adds to the result -- ``space_mask`` (the int8
+    DataArray over ``space`` on rank 0, None elsewhere) and ``masked_points`` (over all ranks).  Masked points are
+    zero rows of X and of U, NaN in X_mean / X_std; the masking happens in the ingest (``_upload_variable``).
 
     The stages: ``_plan_job`` (the shape of the job), ``_decide_stream_bytes`` (X resident or streamed),
     ``_svd_streamed`` or ``_ingest_resident`` + ``_svd_resident``, ``_gather_results``."""
@@ -1276,11 +1458,11 @@ def _device_pipeline(ds: Dataset, parsed_config: dict, comm=None, kern=None, dev
         log_and_print(logger, f"Ingest: {total / 1e9:.3f} GB to HBM in {dt:.2f} s ({total / 1e9 / max(dt, 1e-9):.2f} GB/s, "
                               f"{len(blocks)} row blocks, centre/scale on device){job.shard}")
         t0 = _time.perf_counter()
-        res, blocks = _svd_resident(blocks, true_rows, job, comm, kern)
+        res, blocks = _svd_resident(blocks, true_rows, job, comm, kern, stats.get("count"))
         _sync(device)
         dt = _time.perf_counter() - t0
         log_and_print(logger, f"SVD stage: {dt:.3f} s ({total / 1e9 / max(dt, 1e-9):.1f} GB/s of X)")
-    return _gather_results(res, stats, blocks, job, comm, device)
+    return _gather_results(res, stats, blocks, job, comm, device, extras)
 
 
 _PRIMED: set = set()
@@ -1344,7 +1526,7 @@ def _small_float64_slice(ds: Dataset, parsed_config: dict) -> bool:
     return 8 * cells * int(parsed_config["delay_embedding"]) <= FP64_MAX_BYTES
 
 
-def _host_pipeline_fp64(ds: Dataset, parsed_config: dict):
+def _host_pipeline_fp64(ds: Dataset, parsed_config: dict, extras: dict | None = None):
     """The reference's own sequence (ref era5_svd.py:384-415) on the mirrored slice tools, for
     small float64 slices: slice -> resample -> standardize -> flatten -> delay-embed on the host
     in float64 (a few MB: not a device job), then ``svd_on_era5``, whose float64 input takes the
@@ -1357,19 +1539,46 @@ def _host_pipeline_fp64(ds: Dataset, parsed_config: dict):
     d = parsed_config["delay_embedding"]
     ds = slice_era5_dataset(ds, levels=parsed_config["levels"])
     ds = resample_era5_dataset(ds, parsed_config["delta_time"])
+    bad = None
+    if _missing_mode(parsed_config) == "mask":
+        # the rule of the device pipeline, in numpy: a grid point with a snapshot that is not finite is left out
+        import torch
+
+        from . import svd as dsvd
+
+        names = list(ds.data_vars)
+        cnt = np.logical_not(np.isfinite(flatten_era5_variables(ds).values)).sum(axis=1).astype(np.int32)
+        per = torch.from_numpy(cnt).reshape(len(names), -1)
+        masked = _report_missing(names, [[c] for c in per], int(ds.coords["time"].values.shape[0]), dsvd.Comm(),
+                                 torch.device("cpu"))
+        bad = cnt != 0
     ds_mean = ds_std = None
     if parsed_config["mean_center"] and parsed_config["scale"]:
         ds, ds_mean, ds_std = standardize_data(ds)
     elif parsed_config["mean_center"]:
         ds, ds_mean, ds_std = standardize_data(ds, scale=False)
-    da = apply_delay_embedding(flatten_era5_variables(ds), d)
+    flat = flatten_era5_variables(ds)                                  # (a new array: the caller's values stay)
+    if bad is not None:
+        flat.values[bad] = 0.0
+    da = apply_delay_embedding(flat, d)
     row = {c: da.coords[c] for c in ("space", "original_variable", "delay") if c in da.coords}
+
+    def row_vector(stat: Dataset) -> DataArray:
+        v = flatten_era5_variables(stat).values
+        if bad is not None:
+            v[bad] = np.nan
+        return DataArray(np.tile(v, d), ("space",), row)
+
     da_mean = da_std = None
     if ds_mean is not None and d > 1:                                  # (the reference's d == 1 quirk: no X_mean)
-        da_mean = DataArray(np.tile(flatten_era5_variables(ds_mean).values, d), ("space",), row)
+        da_mean = row_vector(ds_mean)
         if ds_std is not None:
-            da_std = DataArray(np.tile(flatten_era5_variables(ds_std).values, d), ("space",), row)
+            da_std = row_vector(ds_std)
     U, s, V = svd_on_era5(da, parsed_config)
+    if bad is not None:
+        U[np.tile(bad, d)] = 0.0                                       # (already zero, up to an orthonormal completion)
+        if extras is not None:
+            extras["masked_points"], extras["space_mask"] = masked, _space_mask(~bad, d, da.coords)
     return U, s, V, da.coords, (da if parsed_config["save_data_matrix"] else None), da_mean, da_std
 
 
@@ -1422,9 +1631,10 @@ def main(config: dict | None = None, write_to_netcdf: bool = False, use_dvc: boo
     if config is None:
         config = config_reader("era5-svd")
     parsed_config = config_parser(config, "era5-svd")
-    for key in _ENGINE_KEYS:
+    for key in (*_ENGINE_KEYS, "missing"):
         if key in config:
             parsed_config[key] = config[key]
+    masking = _missing_mode(parsed_config) == "mask"
 
     try:
         svd_results, _ = retrieve_svd_results(parsed_config, use_dvc)
@@ -1454,14 +1664,16 @@ def main(config: dict | None = None, write_to_netcdf: bool = False, use_dvc: boo
         ds = ds[parsed_config["variables"]]
         # slice_era5_dataset(levels=...) and resample_era5_dataset(...) happen inside, as index
         # selections applied while the slice is streamed to the device
+        extras = {}
+        more = {"extras": extras} if masking else {}      # (the default call is what it was)
         if comm.world_size == 1 and _small_float64_slice(ds, parsed_config):
-            U, s, V, coords, X, X_mean, X_std = _host_pipeline_fp64(ds, parsed_config)
+            U, s, V, coords, X, X_mean, X_std = _host_pipeline_fp64(ds, parsed_config, **more)
         else:
-            U, s, V, coords, X, X_mean, X_std = _device_pipeline(ds, parsed_config, comm)
+            U, s, V, coords, X, X_mean, X_std = _device_pipeline(ds, parsed_config, comm, **more)
         svd_results = None
         t_pipe = time.perf_counter()
         if comm.rank == 0:
-            svd_results = combine_svd_results(U, s, V, coords, X=X, X_mean=X_mean, X_std=X_std)
+            svd_results = combine_svd_results(U, s, V, coords, X=X, X_mean=X_mean, X_std=X_std, **extras)
             svd_results = add_config_attributes(svd_results, parsed_config)
             svd_results = space_coord_to_level_lat_lon(svd_results)
     except Exception as e:

@@ -46,12 +46,12 @@ import torch
 
 from .bopdmd import OptDMDResult, _phi
 from .labeled import Packing
-from .svd import Comm, _kern, _pitched, embed_view, free_device_bytes
+from .svd import Comm, _kern, _pitched, embed_view, free_device_bytes, row_mask_apply_
 
 __all__ = ["svd_coefficients", "dmd_coefficients", "ensemble_coefficients", "expand_blocks", "iter_fields",
            "score_blocks", "project_blocks", "spread_blocks", "spread_score_blocks", "area_weights", "verify_blocks",
            "member_coefficients", "crps_blocks", "pack_blocks", "pack_field_blocks", "range_blocks",
-           "range_field_blocks", "DmdForecast"]
+           "range_field_blocks", "mask_weights", "DmdForecast"]
 
 
 # ---------------------------------------------------------------------------
@@ -919,8 +919,30 @@ def range_field_blocks(Xblocks, groups=None, kern=None, n_groups: int | None = N
     return _range_pieces(pieces, G, dev, lambda b, s, e, o: _field_range(kern, Xblocks[b][:, s:e], o), state)
 
 
+def _masked_count(masks, b, device) -> torch.Tensor:
+    """Block b of a list of ``space_mask`` vectors (1 = used, 0 = masked) as the int32 count K20 takes: != 0 at the
+    masked rows."""
+    return (torch.as_tensor(masks[b]).to(device).reshape(-1) == 0).to(torch.int32).contiguous()
+
+
+def mask_weights(weights, masks) -> list:
+    """The per-block row weights of :func:`verify_blocks` / :func:`crps_blocks` with the masked grid points left
+    out: ``weights`` (per block the weight of every physical row; None: all ones) with 0 where ``masks`` (per block
+    the ``space_mask`` of its physical rows, 1 = used in the decomposition) is 0.  A row with weight 0 is selected
+    out of every score, whatever it holds -- the NaN that the mean of a masked point is."""
+    out = []
+    for b, m in enumerate(masks):
+        used = torch.as_tensor(m).reshape(-1) != 0
+        w = torch.ones(used.shape, dtype=torch.float32, device=used.device) if weights is None else \
+            torch.as_tensor(weights[b]).to(device=used.device, dtype=torch.float32).reshape(-1)
+        if w.shape != used.shape:
+            raise ValueError(f"mask_weights: block {b} has {w.numel()} weights and {used.numel()} mask entries")
+        out.append(torch.where(used, w, torch.zeros_like(w)))
+    return out
+
+
 def project_blocks(Ublocks, Xblocks, means=None, stds=None, delay: int = 1, comm: Comm | None = None, kern=None,
-                   shape: tuple[int, int] | None = None) -> dict:
+                   shape: tuple[int, int] | None = None, masks=None) -> dict:
     """The coefficients of raw snapshots in the basis U: ``c_t = U^T ((x_t - mean) / std)``, X read once and
     no standardised copy made (K13).  The snapshots need not be the ones U was computed from.
 
@@ -928,6 +950,10 @@ def project_blocks(Ublocks, Xblocks, means=None, stds=None, delay: int = 1, comm
     order); with ``delay`` d > 1 the zero-copy embedded view (n - d + 1, d * rows) of every block is
     projected.  ``means`` / ``stds``: lists of per-row vectors of the PHYSICAL rows of every block (None:
     0 / 1), repeated for every delay; a std with a zero entry is refused (ValueError) before any launch.
+    ``masks``: per block the ``space_mask`` of its physical rows (1 = used, 0 = masked: the result of
+    ``missing = "mask"``).  The masked rows are missing in the new snapshots as well: they are SET TO 0 IN PLACE in
+    the blocks handed in (K20; rows that are used are not touched), and their mean / std entries -- NaN in such a
+    result -- are taken as 0 / 1, so that K13 never sees a NaN and the energy counts the used points only.
     Returns ``Ct`` (T, k) fp64, per snapshot ``energy`` = ||(x - mean) / std||^2 and ``captured`` =
     ||c_t||^2 / energy_t, the totals ``captured_total`` = sum ||c||^2 / sum energy and ``energy_total``, and
     ``rows`` (global).
@@ -956,7 +982,14 @@ def project_blocks(Ublocks, Xblocks, means=None, stds=None, delay: int = 1, comm
         if E.shape != (T, U.shape[1]) or U.shape[0] != k:
             raise ValueError(f"project_blocks: block {b} of X is {tuple(E.shape)} (delay {delay}) and of U "
                              f"{tuple(U.shape)}; {(T, int(U.shape[1]))} and {(k, int(U.shape[1]))} asked for")
-        acc = _project(kern, U, E, _vec(means, b, delay, U.device), _vec(stds, b, delay, U.device), acc)
+        mu, sd = _vec(means, b, delay, U.device), _vec(stds, b, delay, U.device)
+        if masks is not None:
+            cnt = _masked_count(masks, b, X.device)
+            row_mask_apply_(kern, X, cnt, 0.0)                         # (the physical block: every delay sees the zeros)
+            on = (cnt != 0).to(U.device).repeat(delay)
+            mu = None if mu is None else mu.masked_fill(on, 0.0)
+            sd = None if sd is None else sd.masked_fill(on, 1.0)
+        acc = _project(kern, U, E, mu, sd, acc)
         rows_local += int(U.shape[1])
     if acc is None:        # a rank without blocks still takes part in the collective
         if shape is None:
@@ -990,7 +1023,9 @@ class DmdForecast:
     ``Ublocks``: (k, d * rows) blocks of the left singular vectors; ``means`` / ``stds``: per-row
     vectors of the physical rows of every block, or None; ``delay``: d; ``result``: the
     :class:`OptDMDResult` fitted on ``reduced_coordinates(s, Vh)``; ``s`` / ``Vh``: the SVD factors
-    (only :meth:`reconstruct_svd` needs them)."""
+    (only :meth:`reconstruct_svd` needs them); ``masks``: per block the ``space_mask`` of its physical rows (the
+    result of ``missing = "mask"``; 1 = used), which :meth:`project` and :meth:`restart` hand to
+    :func:`project_blocks`, or None."""
 
     Ublocks: list
     result: OptDMDResult | None = None
@@ -1000,6 +1035,7 @@ class DmdForecast:
     s: torch.Tensor | None = None
     Vh: torch.Tensor | None = None
     kern: object = None
+    masks: list | None = None
 
     def coefficients(self, t) -> tuple[torch.Tensor, float]:
         if self.result is None:
@@ -1178,12 +1214,14 @@ class DmdForecast:
 
     def project(self, Xblocks, comm: Comm | None = None, n_snapshots: int | None = None) -> dict:
         """:func:`project_blocks` of raw snapshots (with a delay d the blocks hold T + d - 1 of them) on this
-        bundle's U, means and stds.  ``n_snapshots``: T, for a rank without blocks."""
+        bundle's U, means, stds and masks (with masks the masked rows of ``Xblocks`` are set to 0 in place).
+        ``n_snapshots``: T, for a rank without blocks."""
         shape = None
         if n_snapshots is not None:
             k = int(self.Ublocks[0].shape[0]) if len(self.Ublocks) else int(self.result.modes.shape[0])
             shape = (int(n_snapshots), k)
-        return project_blocks(self.Ublocks, Xblocks, self.means, self.stds, self.delay, comm, self.kern, shape=shape)
+        return project_blocks(self.Ublocks, Xblocks, self.means, self.stds, self.delay, comm, self.kern, shape=shape,
+                              masks=self.masks)
 
     def restart(self, Xblocks, t, comm: Comm | None = None, rcond: float = 1e-12) -> "DmdForecast":
         """The fitted model re-started from new snapshots: the amplitudes are re-fitted to the coefficients
@@ -1209,7 +1247,8 @@ class DmdForecast:
         k, r, T = int(W.shape[0]), int(alpha.numel()), int(tt.numel())
         if T * k < r:
             raise ValueError(f"DmdForecast.restart: {T} snapshots x {k} coordinates cannot determine {r} amplitudes")
-        proj = project_blocks(self.Ublocks, Xblocks, self.means, self.stds, self.delay, comm, self.kern, shape=(T, k))
+        proj = project_blocks(self.Ublocks, Xblocks, self.means, self.stds, self.delay, comm, self.kern, shape=(T, k),
+                              masks=self.masks)
         C = proj["Ct"].to(device=alpha.device, dtype=torch.complex128)
         phi = _phi(alpha, tt, torch.complex128)
         N = (phi.conj().T @ phi) * (W.conj().T @ W)
@@ -1229,4 +1268,4 @@ class DmdForecast:
                     restart_window=T, captured=proj["captured_total"])
         new = OptDMDResult(eigs=res.eigs, modes=(W * phase).to(res.modes.dtype), amplitudes=amp.to(res.amplitudes.dtype),
                            rel_error=rel, n_iter=0, converged=True, eigs_std=res.eigs_std, info=info)
-        return DmdForecast(self.Ublocks, new, self.means, self.stds, self.delay, self.s, self.Vh, self.kern)
+        return DmdForecast(self.Ublocks, new, self.means, self.stds, self.delay, self.s, self.Vh, self.kern, self.masks)

@@ -739,6 +739,38 @@ class HipKernels:
         _lib.check(rc, "dmdx_clim_apply_f32")
         return Yt
 
+    # -- K20 ----------------------------------------------------------------
+    @staticmethod
+    def _row_count(count, m: int, device, who: str) -> None:
+        if (not isinstance(count, torch.Tensor) or count.dtype != torch.int32 or count.dim() != 1 or count.numel() != m
+                or count.device != device or not count.is_contiguous()):
+            raise _lib.DmdxError(f"{who}: count must be a contiguous int32 vector of length {m} on {device}")
+
+    def row_missing_count(self, Xt: torch.Tensor, out: torch.Tensor | None = None) -> torch.Tensor:
+        """How many snapshots of every row of a block are not finite (NaN of any payload, +-Inf; tested on the
+        bits).  Xt: (n, m) fp32 (any row stride) -> count (m,) int32.  ``out``: a device int32 vector the counts
+        are ADDED to (time slabs accumulate); a fresh one starts at zero.  One read of Xt, no temporary."""
+        m, n, ldx = _check_mat(Xt, torch.float32, "row_missing_count X")
+        count = out if out is not None else torch.zeros(m, dtype=torch.int32, device=Xt.device)
+        self._row_count(count, m, Xt.device, "row_missing_count")
+        rc = self._timed("row_missing_count", (m, n), lambda: self._lib.dmdx_row_missing_count_f32(
+            _ptr(Xt), n, m, ldx, _ptr(count), self._stream()
+        ))
+        _lib.check(rc, "dmdx_row_missing_count_f32")
+        return count
+
+    def row_mask_apply_(self, Xt: torch.Tensor, count: torch.Tensor, value: float = 0.0) -> torch.Tensor:
+        """In place: every element of the rows of Xt ((n, m) fp32, any row stride) with ``count[i] != 0`` becomes
+        ``value`` (its bits: -0.0, NaN); the other rows are neither read nor written.  Xt may be a block of
+        snapshots, a (k, rows) block of U^T or a stored field.  -> Xt."""
+        m, n, ldx = _check_mat(Xt, torch.float32, "row_mask_apply X")
+        self._row_count(count, m, Xt.device, "row_mask_apply")
+        rc = self._timed("row_mask_apply", (m, n), lambda: self._lib.dmdx_row_mask_apply_f32(
+            _ptr(Xt), n, m, ldx, _ptr(count), float(value), self._stream()
+        ))
+        _lib.check(rc, "dmdx_row_mask_apply_f32")
+        return Xt
+
     # -- K6 -----------------------------------------------------------------
     def delay_shift_sum(self, G64: torch.Tensor, d: int, want32: bool = False):
         """Gd[i, j] = sum_{k<d} G[i+k, j+k]."""

@@ -223,6 +223,27 @@ def _kern(kern):
     return default_kernels()
 
 
+def row_missing_count(kern, Xt: torch.Tensor, out: torch.Tensor | None = None) -> torch.Tensor:
+    """K20: per row of the block Xt ((n, m) fp32) the number of snapshots that are not finite, int32 (m,); added to
+    ``out`` when given.  A provider without the kernel (the CPU double of the tests) takes the torch expression."""
+    if hasattr(kern, "row_missing_count"):
+        return kern.row_missing_count(Xt, out)
+    cnt = torch.isfinite(Xt).logical_not().sum(dim=0, dtype=torch.int32)
+    if out is None:
+        return cnt
+    out += cnt
+    return out
+
+
+def row_mask_apply_(kern, Xt: torch.Tensor, count: torch.Tensor, value: float = 0.0) -> torch.Tensor:
+    """K20: every element of the rows of Xt ((n, m) fp32) with ``count != 0`` becomes ``value``, in place; the
+    other rows keep their bits.  Same fallback rule as :func:`row_missing_count`."""
+    if hasattr(kern, "row_mask_apply_"):
+        return kern.row_mask_apply_(Xt, count, value)
+    Xt[:, count != 0] = value
+    return Xt
+
+
 def embed_view(Xt: torch.Tensor, d: int) -> torch.Tensor:
     """Zero-copy delay embedding (reference slice_tools.py:207-211): row
     ``k*m + s`` of the embedded matrix is ``X[s, t+k]``."""

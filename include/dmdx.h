@@ -607,6 +607,28 @@ int dmdx_clim_apply_f32(const float* X, int64_t m, int64_t T, int64_t ldx, const
                         const float* mean, int64_t ldc, const float* sd /* nullable */, int64_t lds, int restore,
                         float* Y, int64_t ldy, void* stream);
 
+/* ---- K20: rows (grid points) with a missing value, and one value for all of them -------------------------------------
+ * What lets a field with a static mask -- sea-surface temperature, missing over land in every file -- through the
+ * decomposition: a grid point that is missing in any snapshot takes no part (its row of X becomes 0, which gives a zero
+ * row of U) and comes back as missing.  X is a row block as everywhere, here with the snapshots first: n snapshots of m
+ * floats, snapshot j at X + j ldx, ldx >= m.
+ *   count   count[i] += the number of j < n with X[j, i] not finite, i < m (device int32).  It ADDS: time slabs and
+ *           repeated calls accumulate, the caller zeroes it once.  "Not finite" is the bit pattern with an exponent of
+ *           all ones (every NaN payload, +Inf, -Inf), tested on integers: denormals, +-0 and +-FLT_MAX are finite
+ *           whatever floating-point options the build has.  One read of X; the partial counts of the time splits of the
+ *           launch meet in integer atomics, whose result does not depend on their order: bit-wise reproducible.
+ *   apply   X[j, i] = value for every j < n of the rows with count[i] != 0.  A row with count[i] == 0 is neither read
+ *           nor written; X is not read at all: the traffic is the stores of the masked rows and m ints.  `value` is
+ *           stored with its bits (-0.0, a NaN).  The same call zeroes the masked rows of X, of a (k, rows) block of U^T,
+ *           and puts NaN on the masked rows of a stored field.
+ * Memory: only logical elements of X are read (count) or written (apply), only count[0 .. m) is read / updated.  No
+ * alignment is asked for beyond that of the elements: a 16-byte aligned X with ldx % 4 == 0 moves 16 bytes per lane
+ * (the ragged last quad element by element), anything else one dword per lane, with the same results.  m need not be
+ * a multiple of 4.  n == 0 or m == 0 returns 0 and touches nothing (null pointers are allowed then).  A refused call
+ * (DMDX_E_INVALID: a negative size, a size >= 2^31, ldx < m, a null or misaligned X or count) has written nothing. */
+int dmdx_row_missing_count_f32(const float* X, int64_t n, int64_t m, int64_t ldx, int32_t* count, void* stream);
+int dmdx_row_mask_apply_f32(float* X, int64_t n, int64_t m, int64_t ldx, const int32_t* count, float value, void* stream);
+
 /* ---- upper triangle of a symmetric fp64 matrix <-> packed row by row ---------------------
  * packed[i (2n - i + 1) / 2 + (j - i)] = A[i][j], j >= i: what the Gram all-reduce of the
  * row-sharded path moves (n (n + 1) / 2 doubles instead of n^2).  unpack writes both triangles. */
