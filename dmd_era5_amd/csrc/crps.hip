@@ -243,16 +243,8 @@ extern "C" int dmdx_crps_f32(const float* U, int64_t m, int64_t k, int64_t ldu, 
   DMDX_CHECK_ARG(B >= 1 && B <= MAXB, "%s: B = %lld outside 1 .. %d", who, (long long)B, MAXB);
   if (int rc = check_common(U, m, k, ldu, C, ldc, T, who)) return rc;
   DMDX_CHECK_ARG(B * T < DIM_LIMIT, "%s: B T = %lld x %lld columns of C must be < 2^31", who, (long long)B, (long long)T);
-  DMDX_CHECK_ARG(ldx >= 1 && ldx < DIM_LIMIT, "%s: ldx = %lld must be in 1 .. 2^31 - 1", who, (long long)ldx);
-  DMDX_CHECK_ARG(ldcol >= T && ldcol < DIM_LIMIT, "%s: ldcol = %lld must be in T = %lld .. 2^31 - 1", who, (long long)ldcol,
-                 (long long)T);
-  DMDX_CHECK_ARG(row == nullptr || (ldrow >= m && ldrow < DIM_LIMIT), "%s: ldrow = %lld must be in m = %lld .. 2^31 - 1", who,
-                 (long long)ldrow, (long long)m);
-  const size_t need = dmdx_crps_workspace_bytes(m, k, T, B);
-  if (workspace == nullptr || workspace_bytes < need) {
-    dmdx_set_error("%s: workspace of %zu bytes, %zu needed", who, workspace == nullptr ? (size_t)0 : workspace_bytes, need);
-    return DMDX_E_WORKSPACE;
-  }
+  if (int rc = check_score_lds(m, T, ldx, ldcol, row, ldrow, who)) return rc;
+  if (int rc = check_workspace(workspace, workspace_bytes, dmdx_crps_workspace_bytes(m, k, T, B), who)) return rc;
   const Plan p = plan_for(m, T);
   hipStream_t st = (hipStream_t)stream;
   const ScoreWs ws = score_ws(workspace, p, m, NQ);
@@ -266,14 +258,7 @@ extern "C" int dmdx_crps_f32(const float* U, int64_t m, int64_t k, int64_t ldu, 
   DMDX_DISPATCH_KG(k, who, DMDX_LAUNCH)
 #undef DMDX_LAUNCH
   DMDX_LAUNCH_CHECK();
-  hipLaunchKernelGGL((reduce_cols_kernel<NQ, ColsOf>), dim3((unsigned)p.ntiles, NQ), dim3(256), 0, st, ws.colpart, p.nrb, T,
-                     ColsOf{col, ldcol}, accumulate);
-  DMDX_LAUNCH_CHECK();
-  if (row != nullptr) {
-    hipLaunchKernelGGL(reduce_rows_kernel<NQ>, dim3((unsigned)((m + 255) / 256), NQ), dim3(256), 0, st, ws.rowpart, p.nsplit, m,
-                       row, ldrow);
-    DMDX_LAUNCH_CHECK();
-  }
+  if (int rc = reduce_score<NQ, NQ>(ws, p, m, T, NQ, ColsOf{col, ldcol}, accumulate, row, ldrow, st)) return rc;
   if (hist != nullptr) {
     hipLaunchKernelGGL(reduce_hist_kernel, dim3((unsigned)(B + 1)), dim3(256), 0, st, histpart, p.nrb * p.nsplit, (int)(B + 1),
                        reinterpret_cast<long long*>(hist), accumulate);

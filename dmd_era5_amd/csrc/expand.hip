@@ -156,12 +156,8 @@ extern "C" int dmdx_expand_score_f32(const float* U, int64_t m, int64_t k, int64
   if (int rc = check_common(U, m, k, ldu, C, ldc, T, "dmdx_expand_score_f32")) return rc;
   DMDX_CHECK_ARG(X != nullptr && sse_col != nullptr, "dmdx_expand_score_f32: X and sse_col must not be null");
   DMDX_CHECK_ARG(ldx >= 1 && ldx < DIM_LIMIT, "dmdx_expand_score_f32: ldx = %lld must be in 1 .. 2^31 - 1", (long long)ldx);
-  const size_t need = dmdx_expand_score_workspace_bytes(m, k, T);
-  if (workspace == nullptr || workspace_bytes < need) {
-    dmdx_set_error("dmdx_expand_score_f32: workspace of %zu bytes, %zu needed", workspace == nullptr ? (size_t)0 : workspace_bytes,
-                   need);
-    return DMDX_E_WORKSPACE;
-  }
+  if (int rc = check_workspace(workspace, workspace_bytes, dmdx_expand_score_workspace_bytes(m, k, T), "dmdx_expand_score_f32"))
+    return rc;
   const Plan p = plan_for(m, T);
   hipStream_t st = (hipStream_t)stream;
   const ScoreWs ws = score_ws(workspace, p, m, 1);
@@ -169,13 +165,5 @@ extern "C" int dmdx_expand_score_f32(const float* U, int64_t m, int64_t k, int64
                             sse_row != nullptr ? ws.rowpart : nullptr, st))
     return rc;
   // sse and ref go to two vectors of the caller's; without ref_col its plane of the launch is left out
-  hipLaunchKernelGGL((reduce_cols_kernel<2, SseRef>), dim3((unsigned)p.ntiles, ref_col != nullptr ? 2 : 1), dim3(256), 0, st,
-                     ws.colpart, p.nrb, T, SseRef{sse_col, ref_col}, accumulate);
-  DMDX_LAUNCH_CHECK();
-  if (sse_row != nullptr) {
-    hipLaunchKernelGGL(reduce_rows_kernel<1>, dim3((unsigned)((m + 255) / 256)), dim3(256), 0, st, ws.rowpart, p.nsplit, m,
-                       sse_row, (int64_t)0);
-    DMDX_LAUNCH_CHECK();
-  }
-  return 0;
+  return reduce_score<2, 1>(ws, p, m, T, ref_col != nullptr ? 2 : 1, SseRef{sse_col, ref_col}, accumulate, sse_row, 0, st);
 }

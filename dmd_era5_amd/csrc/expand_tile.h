@@ -291,6 +291,42 @@ inline ScoreWs score_ws(void* workspace, const Plan& p, int64_t m, int nq_rows) 
           reinterpret_cast<float*>(base + align16((size_t)p.nsplit * nq_rows * (size_t)m * sizeof(double)))};
 }
 
+// the workspace of an entry point against what its *_workspace_bytes asks for
+inline int check_workspace(const void* workspace, size_t workspace_bytes, size_t need, const char* who) {
+  if (workspace == nullptr || workspace_bytes < need) {
+    dmdx_set_error("%s: workspace of %zu bytes, %zu needed", who, workspace == nullptr ? (size_t)0 : workspace_bytes, need);
+    return DMDX_E_WORKSPACE;
+  }
+  return 0;
+}
+
+// X and the (NQ, T) / (NQ, m) results of a score that hands its sums back as matrices (K16, K19)
+inline int check_score_lds(int64_t m, int64_t T, int64_t ldx, int64_t ldcol, const double* row, int64_t ldrow,
+                           const char* who) {
+  DMDX_CHECK_ARG(ldx >= 1 && ldx < DIM_LIMIT, "%s: ldx = %lld must be in 1 .. 2^31 - 1", who, (long long)ldx);
+  DMDX_CHECK_ARG(ldcol >= T && ldcol < DIM_LIMIT, "%s: ldcol = %lld must be in T = %lld .. 2^31 - 1", who, (long long)ldcol,
+                 (long long)T);
+  DMDX_CHECK_ARG(row == nullptr || (ldrow >= m && ldrow < DIM_LIMIT), "%s: ldrow = %lld must be in m = %lld .. 2^31 - 1", who,
+                 (long long)ldrow, (long long)m);
+  return 0;
+}
+
+// The end of a score entry point, behind its tile kernel: the first `planes` of the NQ column quantities go from
+// colpart to where(q) in fp64 and, if `row` is given, the NQ_ROWS row quantities from rowpart to row[q * ldrow + i].
+template <int NQ, int NQ_ROWS, class Out>
+int reduce_score(const ScoreWs& ws, const Plan& p, int64_t m, int64_t T, int planes, Out where, int accumulate, double* row,
+                 int64_t ldrow, hipStream_t st) {
+  hipLaunchKernelGGL((reduce_cols_kernel<NQ, Out>), dim3((unsigned)p.ntiles, planes), dim3(256), 0, st, ws.colpart, p.nrb, T,
+                     where, accumulate);
+  DMDX_LAUNCH_CHECK();
+  if (row != nullptr) {
+    hipLaunchKernelGGL(reduce_rows_kernel<NQ_ROWS>, dim3((unsigned)((m + 255) / 256), NQ_ROWS), dim3(256), 0, st, ws.rowpart,
+                       p.nsplit, m, row, ldrow);
+    DMDX_LAUNCH_CHECK();
+  }
+  return 0;
+}
+
 // One instantiation per granule count: LAUNCH(KG) for KG = ceil(k / 16) in 1 .. 16.
 #define DMDX_DISPATCH_KG(k, who, LAUNCH)                                   \
   switch (((k) + 15) / 16) {                                               \

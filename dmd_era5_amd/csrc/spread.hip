@@ -168,25 +168,13 @@ extern "C" int dmdx_spread_score_f32(const float* U, int64_t m, int64_t k, int64
                                      int accumulate, void* workspace, size_t workspace_bytes, void* stream) {
   if (int rc = check_spread(U, m, k, ldu, D, ldd, T, B, "dmdx_spread_score_f32")) return rc;
   DMDX_CHECK_ARG(var_col != nullptr, "dmdx_spread_score_f32: var_col must not be null");
-  const size_t need = dmdx_spread_score_workspace_bytes(m, k, T, B);
-  if (workspace == nullptr || workspace_bytes < need) {
-    dmdx_set_error("dmdx_spread_score_f32: workspace of %zu bytes, %zu needed", workspace == nullptr ? (size_t)0 : workspace_bytes,
-                   need);
-    return DMDX_E_WORKSPACE;
-  }
+  if (int rc = check_workspace(workspace, workspace_bytes, dmdx_spread_score_workspace_bytes(m, k, T, B), "dmdx_spread_score_f32"))
+    return rc;
   const Plan p = plan_for(m, T);
   hipStream_t st = (hipStream_t)stream;
   const ScoreWs ws = score_ws(workspace, p, m, 1);
   if (int rc = launch<true>(U, m, (int)k, ldu, D, ldd, T, B, sigma, nullptr, 0, ws.colpart,
                             var_row != nullptr ? ws.rowpart : nullptr, st))
     return rc;
-  hipLaunchKernelGGL((reduce_cols_kernel<1, ColsOf>), dim3((unsigned)p.ntiles), dim3(256), 0, st, ws.colpart, p.nrb, T,
-                     ColsOf{var_col, 0}, accumulate);
-  DMDX_LAUNCH_CHECK();
-  if (var_row != nullptr) {
-    hipLaunchKernelGGL(reduce_rows_kernel<1>, dim3((unsigned)((m + 255) / 256)), dim3(256), 0, st, ws.rowpart, p.nsplit, m,
-                       var_row, (int64_t)0);
-    DMDX_LAUNCH_CHECK();
-  }
-  return 0;
+  return reduce_score<1, 1>(ws, p, m, T, 1, ColsOf{var_col, 0}, accumulate, var_row, 0, st);
 }

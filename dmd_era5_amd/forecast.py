@@ -35,6 +35,12 @@ transpose -- U blocks are ``(k, rows)`` (``SvdResult.Ut``), coefficients ``Ct`` 
 fields and snapshots ``(T, rows)``.  A delay-embedded U block is ``(k, d * rows)`` with delay j in
 columns ``[j * rows, (j + 1) * rows)`` (svd._assemble_rows).
 
+The drivers that sum a score over the grid -- :func:`score_blocks`, :func:`spread_score_blocks`, :func:`verify_blocks`,
+:func:`crps_blocks` -- are one loop, :func:`_grid_sums`: U resident, X consumed block by block, the launches of a block
+from :func:`_group_pieces`, one ``allreduce_sum_`` per call; a driver states its accumulators, the kernel call on one
+row range and its score formulas.  :func:`project_blocks` keeps a loop of its own (it learns T and k from the first
+block and writes into the snapshot blocks).
+
 ``kern=None`` means the HIP provider, as in svd.py.  A provider WITHOUT ``expand`` (the CPU kernel
 double of the tests) takes the plain torch expression, as ``svd._tn`` does for K9.
 """
@@ -416,6 +422,95 @@ def iter_fields(Ublocks, Ct: torch.Tensor, means=None, stds=None, delay_block: i
         yield t0, t1, blocks
 
 
+def _check_weights(weights, who):
+    """The per-block row weights as a list (or None); a negative or non-finite one is refused, before any launch."""
+    if weights is None:
+        return None
+    weights = list(weights)
+    for b, v in enumerate(weights):
+        x = torch.as_tensor(v).to(torch.float64)
+        bad = int((~torch.isfinite(x) | (x < 0)).sum())
+        if bad:
+            raise ValueError(f"{who}: {bad} weights of block {b} are negative or not finite (a row is left "
+                             "out with the weight 0)")
+    return weights
+
+
+def _block_vecs(vecs: dict, b, reps, mb, device, who) -> dict:
+    """Block b of every named list of per-row vectors (:func:`_vec`), each of them as long as the block's mb
+    physical rows."""
+    out = {}
+    for name, v in vecs.items():
+        out[name] = x = _vec(v, b, reps, device)
+        if x is not None and x.numel() != reps * mb:
+            raise ValueError(f"{who}: {name}[{b}] has {x.numel() // reps} entries, the block {mb} rows")
+    return out
+
+
+def _grid_sums(who, tag, comm, Ublocks, Xblocks, T, delay, device, vecs: dict, zeros, launch, groups=None,
+               n_groups=None, want_rows=False):
+    """The loop of the drivers that sum a score over the grid (:func:`score_blocks`, :func:`spread_score_blocks`,
+    :func:`verify_blocks`, :func:`crps_blocks`): the blocks in order, the launches of a block in the order of
+    :func:`_group_pieces` (run-major, delay-minor), ONE ``comm.allreduce_sum_`` (``tag``) of everything summed.
+
+    ``Ublocks`` is resident (a list is made of it); ``Xblocks`` -- None for a score without snapshots -- is consumed
+    once, in order, one block alive at a time, and its embedded view must be (T, d * rows).  ``vecs``: name ->
+    list of per-row vectors of the physical rows, or None (``means``, ``stds``, ...).  A ``weights`` entry makes the
+    score a weighted one: it is validated (:func:`_check_weights`), and the sum of the weights W -- per run on the
+    host in fp64, times the delay -- and the rows with weight 0 travel with the row count.
+    ``zeros(G, device)`` -> the tuple of zero accumulators (made at the first block, or on ``device`` by a rank
+    without blocks); ``launch(acc, U, E, v, g)`` adds one row range of group g to them -- ``v``: name -> that range of
+    the block's vectors -- and returns its row sums (..., rows of the range) or None.
+
+    -> (the accumulators after the collective, the counts (rows,) or (W, rows, masked rows), each (G,), the list of
+    the local blocks' row sums)."""
+    comm = comm or Comm()
+    weighted = "weights" in vecs
+    if weighted:
+        vecs = {**vecs, "weights": _check_weights(vecs["weights"], who)}
+    Ublocks = list(Ublocks)
+    for b, U in enumerate(Ublocks):
+        if U.shape[1] % delay:
+            raise ValueError(f"{who}: the {int(U.shape[1])} rows of U block {b} are no multiple of the delay {delay}")
+    rows_of = [int(U.shape[1]) // delay for U in Ublocks]
+    pieces, G = _group_pieces(groups, rows_of, [delay] * len(rows_of), n_groups, who)
+    acc, meta, row_sums = None, torch.zeros((3, G), dtype=torch.float64), []
+    Xs = [None] * len(Ublocks) if Xblocks is None else Xblocks
+    for b, (U, X) in enumerate(zip(Ublocks, Xs, strict=True)):         # (a streamed X that ends early is an error)
+        E = None if X is None else embed_view(X, delay)
+        if E is not None and E.shape != (T, U.shape[1]):
+            raise ValueError(f"{who}: block {b} of X is {tuple(E.shape)} (delay {delay}), U and the coefficients ask "
+                             f"for {(T, int(U.shape[1]))}")
+        mb = rows_of[b]
+        if acc is None:
+            acc = zeros(G, U.device)
+        v = _block_vecs(vecs, b, delay, mb, U.device, who)
+        w = v.get("weights")
+        wcpu = None if w is None else w[:mb].to(device="cpu", dtype=torch.float64)
+        for s, e, g in ([(0, mb, 0)] if groups is None else pieces[b][::delay]):   # the runs: the launches of delay 0
+            ww = None if wcpu is None else wcpu[s:e]
+            meta[0, g] += delay * (float(e - s) if ww is None else float(ww.sum()))
+            meta[1, g] += delay * (e - s)
+            meta[2, g] += 0 if ww is None else delay * int((ww == 0).sum())
+        R = None
+        for s, e, g in pieces[b]:
+            r = launch(acc, U[:, s:e], None if E is None else E[:, s:e],
+                       {name: None if x is None else x[s:e] for name, x in v.items()}, g)
+            if want_rows:
+                if R is None:
+                    R = r.new_zeros(r.shape[:-1] + (delay * mb,))
+                R[..., s:e] = r
+        if want_rows:
+            row_sums.append(R)
+    if acc is None:        # a rank without blocks still takes part in the collective
+        acc = zeros(G, device)
+    flat = torch.cat([a.reshape(-1).to(torch.float64) for a in acc]
+                     + [(meta if weighted else meta[1]).reshape(-1).to(acc[0].device)])
+    flat = comm.allreduce_sum_(flat, tag=tag)
+    parts = flat.split([a.numel() for a in acc] + [flat.numel() - sum(a.numel() for a in acc)])
+    return [p.reshape(a.shape) for p, a in zip(parts, acc)], parts[-1].reshape(-1, G), row_sums
+
+
 def score_blocks(Ublocks, Ct: torch.Tensor, Xblocks, means=None, stds=None, delay: int = 1,
                  comm: Comm | None = None, want_rows: bool = False, kern=None) -> dict:
     """How well ``mean + std * (U c)`` matches the snapshots, without storing it.
@@ -431,26 +526,14 @@ def score_blocks(Ublocks, Ct: torch.Tensor, Xblocks, means=None, stds=None, dela
     Row shards: ONE ``comm.allreduce_sum_`` of the stacked per-snapshot vectors per call, whatever
     the number of local blocks (ranks hold different numbers of them)."""
     kern = _kern(kern)
-    comm = comm or Comm()
     T = int(Ct.shape[0])
     Cp = _pitched(kern, Ct)
-    cols, rows_local, row_sse = None, 0, []
-    for b, (U, X) in enumerate(zip(Ublocks, Xblocks, strict=True)):   # (a streamed X that ends early is an error)
-        E = embed_view(X, delay)
-        if E.shape != (T, U.shape[1]):
-            raise ValueError(f"score_blocks: block {b} of X is {tuple(E.shape)} (delay {delay}), U and Ct ask for "
-                             f"{(T, int(U.shape[1]))}")
-        c, r = _expand_score(kern, U, Cp, E, _vec(means, b, delay, U.device), _vec(stds, b, delay, U.device),
-                             cols, want_rows)
-        cols = c
-        rows_local += int(U.shape[1])
-        if want_rows:
-            row_sse.append(r)
-    if cols is None:        # a rank without blocks still takes part in the collective
-        cols = torch.zeros((2, T), dtype=torch.float64, device=Ct.device)
-    flat = torch.cat([cols.reshape(-1), torch.tensor([float(rows_local)], dtype=torch.float64, device=cols.device)])
-    flat = comm.allreduce_sum_(flat, tag="score_allreduce")
-    sse, ref, rows = flat[:T], flat[T:2 * T], float(flat[2 * T])
+    (cols,), counts, row_sse = _grid_sums(
+        "score_blocks", "score_allreduce", comm, Ublocks, Xblocks, T, delay, Ct.device, {"means": means, "stds": stds},
+        lambda G, dev: (torch.zeros((2, T), dtype=torch.float64, device=dev),),
+        lambda acc, U, E, v, g: _expand_score(kern, U, Cp, E, v["means"], v["stds"], acc[0], want_rows)[1],
+        want_rows=want_rows)
+    sse, ref, rows = cols[0], cols[1], float(counts[0, 0])
     sse_total, ref_total = sse.sum(), ref.sum()
     res = {
         "sse": sse, "ref": ref, "rel_error": torch.sqrt(sse / ref), "rmse": torch.sqrt(sse / rows),
@@ -489,20 +572,14 @@ def spread_score_blocks(Ublocks, Dev: torch.Tensor, stds=None, delay: int = 1, c
     Row shards: ONE ``comm.allreduce_sum_`` of the stacked ``[var, rows]`` per call, whatever the number of
     local blocks.  A rank without blocks still takes part."""
     kern = _kern(kern)
-    comm = comm or Comm()
     T = int(Dev.shape[1])
     Dp = _pitched_dev(kern, Dev)
-    var, rows_local, row_var = None, 0, []
-    for b, U in enumerate(Ublocks):
-        var, r = _spread_score(kern, U, Dp, _vec(stds, b, delay, U.device), var, want_rows)
-        rows_local += int(U.shape[1])
-        if want_rows:
-            row_var.append(r)
-    if var is None:        # a rank without blocks still takes part in the collective
-        var = torch.zeros(T, dtype=torch.float64, device=Dev.device)
-    flat = torch.cat([var, torch.tensor([float(rows_local)], dtype=torch.float64, device=var.device)])
-    flat = comm.allreduce_sum_(flat, tag="spread_allreduce")
-    var, rows = flat[:T], float(flat[T])
+    (var,), counts, row_var = _grid_sums(
+        "spread_score_blocks", "spread_allreduce", comm, Ublocks, None, T, delay, Dev.device, {"stds": stds},
+        lambda G, dev: (torch.zeros(T, dtype=torch.float64, device=dev),),
+        lambda acc, U, E, v, g: _spread_score(kern, U, Dp, v["stds"], acc[0], want_rows)[1],
+        want_rows=want_rows)
+    rows = float(counts[0, 0])
     var_total = var.sum()
     res = {"var": var, "spread": torch.sqrt(var / rows), "var_total": float(var_total),
            "spread_total": float(torch.sqrt(var_total / (rows * T))), "rows": int(rows)}
@@ -564,70 +641,15 @@ def verify_blocks(Ublocks, Ct: torch.Tensor, Xblocks, means=None, stds=None, wei
     Row shards: ONE ``comm.allreduce_sum_`` of the stacked ``[sums, W, rows, masked]`` per call, whatever the
     number of local blocks and groups.  A rank without blocks still takes part."""
     kern = _kern(kern)
-    comm = comm or Comm()
     T = int(Ct.shape[0])
-    if weights is not None:
-        weights = list(weights)
-        for b, v in enumerate(weights):
-            x = torch.as_tensor(v).to(torch.float64)
-            bad = int((~torch.isfinite(x) | (x < 0)).sum())
-            if bad:
-                raise ValueError(f"verify_blocks: {bad} weights of block {b} are negative or not finite (a row is left "
-                                 "out with the weight 0)")
-    runs = None
-    if groups is not None:
-        runs = [_runs(g) for g in groups]
-        labels = [g for r in runs for _, _, g in r]
-        if labels and min(labels) < 0:
-            raise ValueError("verify_blocks: group labels must be >= 0")
-        G = max(labels) + 1 if labels else 1
-        if n_groups is not None:
-            if G > n_groups and labels:
-                raise ValueError(f"verify_blocks: label {G - 1} with n_groups = {n_groups}")
-            G = int(n_groups)
-    else:
-        G = 1 if n_groups is None else int(n_groups)
     Cp = _pitched(kern, Ct)
-    acc, meta, row_sums = None, torch.zeros((3, G), dtype=torch.float64), []
-    for b, (U, X) in enumerate(zip(Ublocks, Xblocks, strict=True)):   # (a streamed X that ends early is an error)
-        E = embed_view(X, delay)
-        if E.shape != (T, U.shape[1]) or U.shape[1] % delay:
-            raise ValueError(f"verify_blocks: block {b} of X is {tuple(E.shape)} (delay {delay}), U and Ct ask for "
-                             f"{(T, int(U.shape[1]))}")
-        mb = int(U.shape[1]) // delay
-        if acc is None:
-            acc = torch.zeros((G, 6, T), dtype=torch.float64, device=U.device)
-        mean, std, w, clim = (_vec(v, b, delay, U.device) for v in (means, stds, weights, clims))
-        for name, v in (("means", mean), ("stds", std), ("weights", w), ("clims", clim)):
-            if v is not None and v.numel() != delay * mb:
-                raise ValueError(f"verify_blocks: {name}[{b}] has {v.numel() // delay} entries, the block {mb} rows")
-        if runs is None:
-            pieces = [(0, delay * mb, 0)]
-        else:
-            if sum(e - s for s, e, _ in runs[b]) != mb:
-                raise ValueError(f"verify_blocks: groups[{b}] has {sum(e - s for s, e, _ in runs[b])} labels, the block "
-                                 f"{mb} rows")
-            pieces = [(j * mb + s, j * mb + e, g) for s, e, g in runs[b] for j in range(delay)]
-        wcpu = None if w is None else w[:mb].to(device="cpu", dtype=torch.float64)
-        for s, e, g in ([(0, mb, 0)] if runs is None else runs[b]):
-            ww = None if wcpu is None else wcpu[s:e]
-            meta[0, g] += delay * (float(e - s) if ww is None else float(ww.sum()))
-            meta[1, g] += delay * (e - s)
-            meta[2, g] += 0 if ww is None else delay * int((ww == 0).sum())
-        R = torch.zeros((6, delay * mb), dtype=torch.float64, device=U.device) if want_rows else None
-        for s, e, g in pieces:
-            cut = (lambda v: None if v is None else v[s:e])
-            _, r = _verify(kern, U[:, s:e], Cp, E[:, s:e], cut(mean), cut(std), cut(w), cut(clim), acc[g], want_rows)
-            if want_rows:
-                R[:, s:e] = r
-        if want_rows:
-            row_sums.append(R)
-    if acc is None:        # a rank without blocks still takes part in the collective
-        acc = torch.zeros((G, 6, T), dtype=torch.float64, device=Ct.device)
-    flat = torch.cat([acc.reshape(-1), meta.reshape(-1).to(acc.device)])
-    flat = comm.allreduce_sum_(flat, tag="verify_allreduce")
-    sums = flat[:G * 6 * T].reshape(G, 6, T)
-    W, rows, masked = flat[G * 6 * T:].reshape(3, G)
+    (sums,), (W, rows, masked), row_sums = _grid_sums(
+        "verify_blocks", "verify_allreduce", comm, Ublocks, Xblocks, T, delay, Ct.device,
+        {"means": means, "stds": stds, "weights": weights, "clims": clims},
+        lambda G, dev: (torch.zeros((G, 6, T), dtype=torch.float64, device=dev),),
+        lambda acc, U, E, v, g: _verify(kern, U, Cp, E, v["means"], v["stds"], v["weights"], v["clims"], acc[0][g],
+                                        want_rows)[1],
+        groups, n_groups, want_rows)
 
     def scores(S, Wn):
         S0, S1, S2, S3, S4, S5 = (S[:, q] for q in range(6))
@@ -672,68 +694,21 @@ def crps_blocks(Ublocks, Cm: torch.Tensor, Xblocks, means=None, stds=None, weigh
     Row shards: ONE ``comm.allreduce_sum_`` of the stacked ``[sums, hist, W, rows, masked]`` per call.  A rank
     without blocks still takes part.  The counts travel as fp64: exact below 2^53 per bin."""
     kern = _kern(kern)
-    comm = comm or Comm()
     if Cm.dim() != 3:
         raise ValueError(f"crps_blocks: Cm must be (B, T, k), got {tuple(Cm.shape)}")
     B, T = int(Cm.shape[0]), int(Cm.shape[1])
     if fair and B < 2:
         raise ValueError(f"crps_blocks: the fair estimator needs B >= 2 members, got {B} (pass fair=False)")
-    if weights is not None:
-        weights = list(weights)
-        for b, v in enumerate(weights):
-            x = torch.as_tensor(v).to(torch.float64)
-            bad = int((~torch.isfinite(x) | (x < 0)).sum())
-            if bad:
-                raise ValueError(f"crps_blocks: {bad} weights of block {b} are negative or not finite (a row is left "
-                                 "out with the weight 0)")
-    Ublocks, Xblocks = list(Ublocks), list(Xblocks)
-    if len(Ublocks) != len(Xblocks):
-        raise ValueError(f"crps_blocks: {len(Ublocks)} blocks of U, {len(Xblocks)} of X")
-    for b, U in enumerate(Ublocks):
-        if U.shape[1] % delay:
-            raise ValueError(f"crps_blocks: the {int(U.shape[1])} rows of U block {b} are no multiple of the delay {delay}")
-    rows_of = [int(U.shape[1]) // delay for U in Ublocks]
-    pieces, G = _group_pieces(groups, rows_of, [delay] * len(rows_of), n_groups, "crps_blocks")
-    runs = None if groups is None else [_runs(g) for g in groups]
     Cp = _pitched_dev(kern, Cm)
-    acc = hist = None
-    meta, row_sums = torch.zeros((3, G), dtype=torch.float64), []
-    for b, (U, X) in enumerate(zip(Ublocks, Xblocks)):
-        E = embed_view(X, delay)
-        if E.shape != (T, U.shape[1]):
-            raise ValueError(f"crps_blocks: block {b} of X is {tuple(E.shape)} (delay {delay}), U and Cm ask for "
-                             f"{(T, int(U.shape[1]))}")
-        mb = rows_of[b]
-        if acc is None:
-            acc = torch.zeros((G, 2, T), dtype=torch.float64, device=U.device)
-            hist = torch.zeros((G, B + 1), dtype=torch.int64, device=U.device)
-        mean, std, w = (_vec(v, b, delay, U.device) for v in (means, stds, weights))
-        for name, v in (("means", mean), ("stds", std), ("weights", w)):
-            if v is not None and v.numel() != delay * mb:
-                raise ValueError(f"crps_blocks: {name}[{b}] has {v.numel() // delay} entries, the block {mb} rows")
-        wcpu = None if w is None else w[:mb].to(device="cpu", dtype=torch.float64)
-        for s, e, g in ([(0, mb, 0)] if runs is None else runs[b]):
-            ww = None if wcpu is None else wcpu[s:e]
-            meta[0, g] += delay * (float(e - s) if ww is None else float(ww.sum()))
-            meta[1, g] += delay * (e - s)
-            meta[2, g] += 0 if ww is None else delay * int((ww == 0).sum())
-        R = torch.zeros((2, delay * mb), dtype=torch.float64, device=U.device) if want_rows else None
-        for s, e, g in pieces[b]:
-            cut = (lambda v: None if v is None else v[s:e])
-            _, r, _ = _crps(kern, U[:, s:e], Cp, E[:, s:e], cut(mean), cut(std), cut(w), acc[g], hist[g], want_rows)
-            if want_rows:
-                R[:, s:e] = r
-        if want_rows:
-            row_sums.append(R)
-    if acc is None:        # a rank without blocks still takes part in the collective
-        acc = torch.zeros((G, 2, T), dtype=torch.float64, device=Cm.device)
-        hist = torch.zeros((G, B + 1), dtype=torch.int64, device=Cm.device)
-    flat = torch.cat([acc.reshape(-1), hist.reshape(-1).to(torch.float64), meta.reshape(-1).to(acc.device)])
-    flat = comm.allreduce_sum_(flat, tag="crps_allreduce")
-    n0, n1 = G * 2 * T, G * 2 * T + G * (B + 1)
-    sums = flat[:n0].reshape(G, 2, T)
-    rank_hist = flat[n0:n1].reshape(G, B + 1).round().to(torch.int64)
-    W, rows, masked = flat[n1:].reshape(3, G)
+    (sums, rank_hist), (W, rows, masked), row_sums = _grid_sums(
+        "crps_blocks", "crps_allreduce", comm, Ublocks, Xblocks, T, delay, Cm.device,
+        {"means": means, "stds": stds, "weights": weights},
+        lambda G, dev: (torch.zeros((G, 2, T), dtype=torch.float64, device=dev),
+                        torch.zeros((G, B + 1), dtype=torch.int64, device=dev)),
+        lambda acc, U, E, v, g: _crps(kern, U, Cp, E, v["means"], v["stds"], v["weights"], acc[0][g], acc[1][g],
+                                      want_rows)[1],
+        groups, n_groups, want_rows)
+    rank_hist = rank_hist.round().to(torch.int64)          # (the counts travelled as fp64)
     npairs = float(B * (B - 1))
 
     def scores(S, Wn):
@@ -982,7 +957,8 @@ def project_blocks(Ublocks, Xblocks, means=None, stds=None, delay: int = 1, comm
         if E.shape != (T, U.shape[1]) or U.shape[0] != k:
             raise ValueError(f"project_blocks: block {b} of X is {tuple(E.shape)} (delay {delay}) and of U "
                              f"{tuple(U.shape)}; {(T, int(U.shape[1]))} and {(k, int(U.shape[1]))} asked for")
-        mu, sd = _vec(means, b, delay, U.device), _vec(stds, b, delay, U.device)
+        mu, sd = _block_vecs({"means": means, "stds": stds}, b, delay, int(U.shape[1]) // delay, U.device,
+                             "project_blocks").values()
         if masks is not None:
             cnt = _masked_count(masks, b, X.device)
             row_mask_apply_(kern, X, cnt, 0.0)                         # (the physical block: every delay sees the zeros)

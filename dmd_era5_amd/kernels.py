@@ -45,6 +45,38 @@ def _check_vec(v: torch.Tensor | None, m: int, device, who: str, name: str) -> N
         raise _lib.DmdxError(f"{who}: {name} must be a contiguous fp32 vector of length {m} on {device}")
 
 
+def _check_snapshots(Xt: torch.Tensor, m: int, T: int, device, who: str) -> int:
+    """The snapshots a score is taken against: (T, m) fp32 on `device` (any row stride) -> ldx."""
+    mx, Tx, ldx = _check_mat(Xt, torch.float32, f"{who} X")
+    if (mx, Tx) != (m, T) or Xt.device != device:
+        raise _lib.DmdxError(f"{who}: X must be ({T}, {m}) on {device}, got {tuple(Xt.shape)}")
+    return ldx
+
+
+def _out_view(out: torch.Tensor | None, m: int, T: int, dtype, device, who: str, kind: str = ""):
+    """The (T, m) field a kernel writes: ``out`` (inner stride 1, any row stride) or a fresh tensor -> (tensor, ld).
+    ``kind``: what the message adds to the shape (" int16")."""
+    if out is None:
+        return torch.empty((T, m), dtype=dtype, device=device), m
+    mo, To, ld = _check_mat(out, dtype, f"{who} out")
+    if (mo, To) != (m, T) or out.device != device:
+        raise _lib.DmdxError(f"{who}: out must be ({T}, {m}){kind} on {device}, got {tuple(out.shape)}")
+    return out, ld
+
+
+_DTYPE_NAME = {torch.float64: "fp64", torch.int64: "int64"}
+
+
+def _accumulator(out: torch.Tensor | None, shape: tuple, dtype, device, who: str, name: str = "out") -> torch.Tensor:
+    """The sums a kernel writes or adds to: ``out``, contiguous with this shape and dtype on `device`, or a fresh
+    (uninitialised) tensor."""
+    if out is None:
+        return torch.empty(shape, dtype=dtype, device=device)
+    if out.shape != shape or out.dtype != dtype or not out.is_contiguous() or out.device != device:
+        raise _lib.DmdxError(f"{who}: {name} must be a contiguous {shape} {_DTYPE_NAME[dtype]} tensor on {device}")
+    return out
+
+
 class HipKernels:
     """The product kernel provider (libdmdx.so on the current CUDA/HIP device)."""
 
@@ -282,13 +314,7 @@ class HipKernels:
 
         ``out``: a (T, m) fp32 view to write into (inner stride 1, any row stride >= m)."""
         m, k, ldu, T, Ct, ldc = self._expand_args(Ut, Ct, mean, std, "expand")
-        if out is not None:
-            mo, To, ldxh = _check_mat(out, torch.float32, "expand out")
-            if (mo, To) != (m, T) or out.device != Ut.device:
-                raise _lib.DmdxError(f"expand: out must be ({T}, {m}) on {Ut.device}, got {tuple(out.shape)}")
-            Xt = out
-        else:
-            Xt, ldxh = torch.empty((T, m), dtype=torch.float32, device=Ut.device), m
+        Xt, ldxh = _out_view(out, m, T, torch.float32, Ut.device, "expand")
         rc = self._timed("expand", (m, k, T), lambda: self._lib.dmdx_expand_f32(
             _ptr(Ut), m, k, ldu, _ptr(Ct), ldc, T, _ptr(mean), _ptr(std), _ptr(Xt), ldxh, self._stream()
         ))
@@ -304,15 +330,8 @@ class HipKernels:
 
         ``out``: a contiguous (2, T) fp64 tensor the column sums are ADDED to (row blocks of X)."""
         m, k, ldu, T, Ct, ldc = self._expand_args(Ut, Ct, mean, std, "expand_score")
-        mx, Tx, ldx = _check_mat(Xt, torch.float32, "expand_score X")
-        if (mx, Tx) != (m, T) or Xt.device != Ut.device:
-            raise _lib.DmdxError(f"expand_score: X must be ({T}, {m}) on {Ut.device}, got {tuple(Xt.shape)}")
-        if out is not None:
-            if out.shape != (2, T) or out.dtype != torch.float64 or not out.is_contiguous() or out.device != Ut.device:
-                raise _lib.DmdxError(f"expand_score: out must be a contiguous (2, {T}) fp64 tensor on {Ut.device}")
-            cols = out
-        else:
-            cols = torch.empty((2, T), dtype=torch.float64, device=Ut.device)
+        ldx = _check_snapshots(Xt, m, T, Ut.device, "expand_score")
+        cols = _accumulator(out, (2, T), torch.float64, Ut.device, "expand_score")
         rows = torch.empty(m, dtype=torch.float64, device=Ut.device) if want_rows else None
         ws = self._workspace(Ut.device, self._lib.dmdx_expand_score_workspace_bytes(m, k, T))
         rc = self._timed("expand_score", (m, k, T), lambda: self._lib.dmdx_expand_score_f32(
@@ -339,17 +358,10 @@ class HipKernels:
 
         ``out``: a contiguous (6, T) fp64 tensor the column sums are ADDED to (row blocks, groups of rows)."""
         m, k, ldu, T, Ct, ldc = self._expand_args(Ut, Ct, mean, std, "verify")
-        mx, Tx, ldx = _check_mat(Xt, torch.float32, "verify X")
-        if (mx, Tx) != (m, T) or Xt.device != Ut.device:
-            raise _lib.DmdxError(f"verify: X must be ({T}, {m}) on {Ut.device}, got {tuple(Xt.shape)}")
+        ldx = _check_snapshots(Xt, m, T, Ut.device, "verify")
         for v, name in ((weight, "weight"), (clim, "clim")):
             _check_vec(v, m, Ut.device, "verify", name)
-        if out is not None:
-            if out.shape != (6, T) or out.dtype != torch.float64 or not out.is_contiguous() or out.device != Ut.device:
-                raise _lib.DmdxError(f"verify: out must be a contiguous (6, {T}) fp64 tensor on {Ut.device}")
-            cols = out
-        else:
-            cols = torch.empty((6, T), dtype=torch.float64, device=Ut.device)
+        cols = _accumulator(out, (6, T), torch.float64, Ut.device, "verify")
         rows = torch.empty((6, m), dtype=torch.float64, device=Ut.device) if want_rows else None
         ws = self._workspace(Ut.device, self._lib.dmdx_verify_workspace_bytes(m, k, T))
         rc = self._timed("verify", (m, k, T), lambda: self._lib.dmdx_verify_f32(
@@ -391,13 +403,7 @@ class HipKernels:
 
         ``out``: a (T, m) fp32 view to write into (inner stride 1, any row stride >= m)."""
         m, k, ldu, T, B, Dt, ldd = self._spread_args(Ut, Dev, std, "spread")
-        if out is not None:
-            mo, To, lds = _check_mat(out, torch.float32, "spread out")
-            if (mo, To) != (m, T) or out.device != Ut.device:
-                raise _lib.DmdxError(f"spread: out must be ({T}, {m}) on {Ut.device}, got {tuple(out.shape)}")
-            St = out
-        else:
-            St, lds = torch.empty((T, m), dtype=torch.float32, device=Ut.device), m
+        St, lds = _out_view(out, m, T, torch.float32, Ut.device, "spread")
         rc = self._timed("spread", (m, k, T, B), lambda: self._lib.dmdx_spread_f32(
             _ptr(Ut), m, k, ldu, _ptr(Dt), ldd, T, B, _ptr(std), _ptr(St), lds, self._stream()
         ))
@@ -412,12 +418,7 @@ class HipKernels:
 
         ``out``: a contiguous (T,) fp64 tensor the snapshot sums are ADDED to (row blocks of U)."""
         m, k, ldu, T, B, Dt, ldd = self._spread_args(Ut, Dev, std, "spread_score")
-        if out is not None:
-            if out.shape != (T,) or out.dtype != torch.float64 or not out.is_contiguous() or out.device != Ut.device:
-                raise _lib.DmdxError(f"spread_score: out must be a contiguous ({T},) fp64 tensor on {Ut.device}")
-            var = out
-        else:
-            var = torch.empty(T, dtype=torch.float64, device=Ut.device)
+        var = _accumulator(out, (T,), torch.float64, Ut.device, "spread_score")
         rows = torch.empty(m, dtype=torch.float64, device=Ut.device) if want_rows else None
         ws = self._workspace(Ut.device, self._lib.dmdx_spread_score_workspace_bytes(m, k, T, B))
         rc = self._timed("spread_score", (m, k, T, B), lambda: self._lib.dmdx_spread_score_f32(
@@ -452,23 +453,13 @@ class HipKernels:
         m, k, ldu, T, B, Dt, ldc = self._spread_args(Ut, Cm, std, "crps")
         if B > self.crps_max_members:
             raise _lib.DmdxError(f"crps: {B} members, at most {self.crps_max_members}")
-        mx, Tx, ldx = _check_mat(Xt, torch.float32, "crps X")
-        if (mx, Tx) != (m, T) or Xt.device != Ut.device:
-            raise _lib.DmdxError(f"crps: X must be ({T}, {m}) on {Ut.device}, got {tuple(Xt.shape)}")
+        ldx = _check_snapshots(Xt, m, T, Ut.device, "crps")
         for v, name in ((mean, "mean"), (weight, "weight")):
             _check_vec(v, m, Ut.device, "crps", name)
         if (out is None) != (hist is None):
             raise _lib.DmdxError("crps: out and hist are accumulated into together: pass both or neither")
-        if out is not None:
-            if out.shape != (2, T) or out.dtype != torch.float64 or not out.is_contiguous() or out.device != Ut.device:
-                raise _lib.DmdxError(f"crps: out must be a contiguous (2, {T}) fp64 tensor on {Ut.device}")
-            if (hist.shape != (B + 1,) or hist.dtype != torch.int64 or not hist.is_contiguous()
-                    or hist.device != Ut.device):
-                raise _lib.DmdxError(f"crps: hist must be a contiguous ({B + 1},) int64 tensor on {Ut.device}")
-            cols, counts = out, hist
-        else:
-            cols = torch.empty((2, T), dtype=torch.float64, device=Ut.device)
-            counts = torch.empty(B + 1, dtype=torch.int64, device=Ut.device)
+        cols = _accumulator(out, (2, T), torch.float64, Ut.device, "crps")
+        counts = _accumulator(hist, (B + 1,), torch.int64, Ut.device, "crps", "hist")
         rows = torch.empty((2, m), dtype=torch.float64, device=Ut.device) if want_rows else None
         ws = self._workspace(Ut.device, self._lib.dmdx_crps_workspace_bytes(m, k, T, B))
         rc = self._timed("crps", (m, k, T, B), lambda: self._lib.dmdx_crps_f32(
@@ -499,8 +490,7 @@ class HipKernels:
             _check_vec(v, m, Ut.device, "project", name)
         if out is not None:
             Ct, energy = out
-            if Ct.shape != (T, k) or Ct.dtype != torch.float64 or not Ct.is_contiguous() or Ct.device != Ut.device:
-                raise _lib.DmdxError(f"project: out[0] must be a contiguous ({T}, {k}) fp64 tensor on {Ut.device}")
+            _accumulator(Ct, (T, k), torch.float64, Ut.device, "project", "out[0]")
             if (energy is not None) != bool(want_energy) or (energy is not None and (
                     energy.shape != (T,) or energy.dtype != torch.float64 or not energy.is_contiguous()
                     or energy.device != Ut.device)):
@@ -585,18 +575,10 @@ class HipKernels:
     @staticmethod
     def _pack_out(out, counts, m, T, device, who):
         """-> (Qt (T, m) int16, ldq, counts (2,) int64) of a pack call; a given ``counts`` accumulates."""
-        if out is not None:
-            mo, To, ldq = _check_mat(out, torch.int16, f"{who} out")
-            if (mo, To) != (m, T) or out.device != device:
-                raise _lib.DmdxError(f"{who}: out must be ({T}, {m}) int16 on {device}, got {tuple(out.shape)}")
-            Qt = out
-        else:
-            Qt, ldq = torch.empty((T, m), dtype=torch.int16, device=device), m
+        Qt, ldq = _out_view(out, m, T, torch.int16, device, who, " int16")
         if counts is None:
             counts = torch.zeros(2, dtype=torch.int64, device=device)
-        elif counts.shape != (2,) or counts.dtype != torch.int64 or not counts.is_contiguous() or counts.device != device:
-            raise _lib.DmdxError(f"{who}: counts must be a contiguous (2,) int64 tensor on {device}")
-        return Qt, ldq, counts
+        return Qt, ldq, _accumulator(counts, (2,), torch.int64, device, who, "counts")
 
     def expand_range(self, Ut: torch.Tensor, Ct: torch.Tensor, mean: torch.Tensor | None = None,
                      std: torch.Tensor | None = None, out=None):

@@ -241,6 +241,41 @@ def test_bad_weights_are_refused_before_any_launch(bad):
         call_blocks(Cm, blocks, 1, Never(), weights=w)
 
 
+def test_a_streamed_x_is_consumed_block_by_block():
+    """``Xblocks`` as a generator: when the launches of block b run, block b + 1 has not been asked for (a streamed X
+    has one block alive at a time), and the result is the one of the list."""
+    from dmd_era5_amd.forecast import crps_blocks
+
+    rs = np.random.RandomState(193)
+    rows, Bn, Tn, k = (5, 7, 4), 3, 4, 2
+    Ub = [_t(rs.standard_normal((k, mb)).astype(np.float32)) for mb in rows]
+    Xb = [_t(rs.standard_normal((Tn, mb)).astype(np.float32)) for mb in rows]
+    Cm = _t(rs.standard_normal((Bn, Tn, k)).astype(np.float32))
+    groups = [torch.arange(mb) % 2 for mb in rows]                   # runs of one row: several launches per block
+    yielded, seen = [], []
+
+    def stream():
+        for b, X in enumerate(Xb):
+            yielded.append(b)
+            yield X
+
+    class Watching(DoubleWithCrps):
+        def crps(self, Ut, *a, **kw):
+            seen.append((len(yielded), int(Ut.shape[1])))
+            return super().crps(Ut, *a, **kw)
+
+    got = crps_blocks(Ub, Cm, stream(), groups=groups, kern=Watching(), want_rows=True)
+    assert [n for n, _ in seen] == [b + 1 for b, mb in enumerate(rows) for _ in range(mb)]
+    assert yielded == [0, 1, 2]
+    want = crps_blocks(Ub, Cm, Xb, groups=groups, kern=DoubleWithCrps(), want_rows=True)
+    assert set(got) == set(want)
+    for key, v in want.items():
+        if isinstance(v, list):
+            assert len(got[key]) == len(v) and all(torch.equal(a, b) for a, b in zip(got[key], v)), key
+        else:
+            assert torch.equal(got[key], v), key
+
+
 def test_member_coefficients_are_the_members_bit_for_bit():
     from test_ensemble import _members
 
