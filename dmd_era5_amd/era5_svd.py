@@ -308,7 +308,7 @@ FORECAST_STAGE_BYTES = 256 << 20
 
 def write_forecast_slice(path: str, forecast, t, time, variables, levels, latitude, longitude, *, packing=None,
                          ensemble: bool = False, spread: bool = False, slab: int | None = None,
-                         attrs: dict | None = None, climatology=None) -> dict:
+                         attrs: dict | None = None, climatology=None, trend=None, trend_extra=None) -> dict:
     """The fields of a :class:`forecast.DmdForecast` at the model times ``t`` as a NETCDF4 file in the schema of the
     input slice: one ``int16`` variable ``(time, level, latitude, longitude)`` per name with ``scale_factor``,
     ``add_offset`` (float64) and ``_FillValue`` (int16 -32768), the coordinate variables, and the global attributes
@@ -334,6 +334,9 @@ def write_forecast_slice(path: str, forecast, t, time, variables, levels, latitu
     be datetime64).  A time slab is expanded to fp32 (K12), the climatology of its times is put back in place (K18) and
     the slab is packed as a field (K17's streaming pair): one fp32 slab is stored.  The range pass, when no packing is
     given, runs on the restored fields.  The spread has no offset and is written as without a climatology.
+    ``trend``: a :class:`trend.Trend` that was removed (after the climatology) before the fit (``time`` must be
+    datetime64; ``trend_extra``: its user series at ``time``, one row per entry, if it has any).  It is put back on the
+    fp32 slab (K21) before the climatology, on the same route.
 
     Returns ``{"packing": {name: Packing}, "filled": {name: int}, "saturated": {name: int}}`` over the file's
     variables: the values that were not finite and became ``_FillValue``, and those a given packing clamped."""
@@ -382,18 +385,26 @@ def write_forecast_slice(path: str, forecast, t, time, variables, levels, latitu
 
     if climatology is not None and not np.issubdtype(time.dtype, np.datetime64):
         raise ValueError("write_forecast_slice: a climatology needs datetime64 time labels")
+    if trend is not None and not np.issubdtype(time.dtype, np.datetime64):
+        raise ValueError("write_forecast_slice: a trend needs datetime64 time labels")
+    if trend_extra is not None:
+        trend_extra = np.asarray(trend_extra, dtype=np.float64).reshape(T, -1)
+    offset = climatology is not None or trend is not None     # the fields pass through an fp32 slab
     fbuf = []
 
     def restored(t0, t1):
-        """The full fields of a slab: expand, then the climatology of its times in place (the buffers are reused)."""
+        """The full fields of a slab: expand, then the trend and the climatology of its times in place (the buffers
+        are reused)."""
         o = [B[:t1 - t0] for B in fbuf] if fbuf else None
         F = fc.expand_blocks(Ub, Ct[t0:t1], forecast.means, forecast.stds, dblock, out=o, delay=d, kern=kern)
         if not fbuf:
             fbuf.extend(F)
-        return climatology.restore_(F, time[t0:t1])
+        if trend is not None:
+            F = trend.restore_(F, time[t0:t1], extra=None if trend_extra is None else trend_extra[t0:t1])
+        return F if climatology is None else climatology.restore_(F, time[t0:t1])
 
     # the packings: the range pass stores coefficients and extrema only (the spread is a field: slab by slab)
-    if packing is None and climatology is not None:
+    if packing is None and offset:
         state = None
         for t0 in range(0, T, slab):
             state = fc.range_field_blocks(restored(t0, min(T, t0 + slab)), groups, kern, nvar, state)
@@ -445,7 +456,7 @@ def write_forecast_slice(path: str, forecast, t, time, variables, levels, latitu
             t1 = min(T, t0 + slab)
             n = t1 - t0
             out = [dslab[0, :n, a:b] for a, b in zip(starts[:-1], starts[1:])]
-            if climatology is not None:
+            if offset:
                 counts = fc.pack_field_blocks(restored(t0, t1), groups, packing, out, kern, nvar, counts)["counts"]
             else:
                 counts = fc.pack_blocks(Ub, Ct[t0:t1], forecast.means, forecast.stds, groups, packing, dblock, d, out,

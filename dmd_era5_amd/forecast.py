@@ -26,6 +26,8 @@ variable), where the field is formed and without storing it in fp32: :func:`pack
 ``DmdForecast.pack``; ``era5_svd.write_forecast_slice`` writes them.  A model fitted on the anomalies against a slot
 climatology (K18, :mod:`climatology`) takes ``climatology=`` / ``times=`` in ``DmdForecast.fields`` and ``verify`` and in
 ``write_forecast_slice``: the climatology is put back on the expanded fields, the analysis is anomalised for the scores.
+A trend and harmonic regression that was removed as well (K21, :mod:`trend`) takes ``trend=`` in the same three places
+and shares ``times=``: out after the climatology, back before it.
 The members of a bagged fit as an ensemble forecast -- the continuous ranked probability score, area-weighted per group,
 and the rank histogram -- are K19 (``HipKernels.crps``, csrc/crps.hip): :func:`member_coefficients`,
 :func:`crps_blocks` and ``DmdForecast.ensemble_crps``; no member field is stored there either.
@@ -983,10 +985,12 @@ def project_blocks(Ublocks, Xblocks, means=None, stds=None, delay: int = 1, comm
             "energy_total": float(e_total), "rows": int(rows)}
 
 
-def _climatology_args(climatology, times, who: str) -> None:
-    if (climatology is None) != (times is None):
+def _climatology_args(climatology, times, who: str, trend=None) -> None:
+    if trend is None and (climatology is None) != (times is None):
         raise ValueError(f"{who}: climatology and times go together (the datetime64 stamps say which slot a "
                          "snapshot takes)")
+    if trend is not None and times is None:
+        raise ValueError(f"{who}: trend and times go together (the datetime64 stamps are what the design is formed at)")
 
 
 # ---------------------------------------------------------------------------
@@ -1022,18 +1026,24 @@ class DmdForecast:
             raise ValueError(f"DmdForecast: the DMD was fitted on {Ct.shape[1]} coordinates, U has {k} columns")
         return Ct.to(self.Ublocks[0].device), imag
 
-    def fields(self, t, delay_block: int | None = 0, out=None, climatology=None, times=None) -> list[torch.Tensor]:
+    def fields(self, t, delay_block: int | None = 0, out=None, climatology=None, times=None, trend=None,
+               trend_extra=None) -> list[torch.Tensor]:
         """The model's fields at the times ``t``: (len(t), rows) per block; ``delay_block=0`` (the
         default) the physical rows, None all d * rows of the embedding.
         ``climatology``: a :class:`climatology.Climatology` the model was fitted on the anomalies of; its fields at
-        ``times`` (the datetime64 stamps of ``t``) are put back in place (K18), so that full fields come out."""
+        ``times`` (the datetime64 stamps of ``t``) are put back in place (K18), so that full fields come out.
+        ``trend``: a :class:`trend.Trend` that was removed (after the climatology) before the fit; it is evaluated at
+        the same ``times`` (``trend_extra``: its user series there, if it has any) and put back in place (K21) before
+        the climatology."""
         if self.delay == 1:
             delay_block = None
-        _climatology_args(climatology, times, "DmdForecast.fields")
-        if climatology is not None and delay_block is None and self.delay > 1:
-            raise ValueError("DmdForecast.fields: a climatology lives on the physical rows; pass a delay_block")
+        _climatology_args(climatology, times, "DmdForecast.fields", trend)
+        if (climatology is not None or trend is not None) and delay_block is None and self.delay > 1:
+            raise ValueError("DmdForecast.fields: a climatology or a trend lives on the physical rows; pass a delay_block")
         res = expand_blocks(self.Ublocks, self.coefficients(t)[0], self.means, self.stds, delay_block, out=out,
                             delay=self.delay, kern=self.kern)
+        if trend is not None:
+            trend.restore_(res, times, extra=trend_extra)
         if climatology is not None:
             climatology.restore_(res, times)
         return res
@@ -1048,7 +1058,7 @@ class DmdForecast:
 
     def verify(self, Xblocks, t, weights=None, clims=None, groups=None, comm: Comm | None = None,
                want_rows: bool = False, ensemble: bool = False, n_groups: int | None = None, climatology=None,
-               times=None) -> dict:
+               times=None, trend=None, trend_extra=None) -> dict:
         """:func:`verify_blocks` of the model at the times ``t`` against the snapshots ``Xblocks`` (with a delay d
         the blocks hold len(t) + d - 1 snapshots): weighted RMSE, bias and anomaly correlation per group.
         ``ensemble=True`` verifies the ensemble mean of a bagged fit (``Cbar`` of :meth:`ensemble_coefficients`).
@@ -1056,14 +1066,22 @@ class DmdForecast:
         is anomalised against it into a scratch copy per block (``times``: the datetime64 stamps of the snapshots of
         ``Xblocks``) and ``clims`` becomes zero: forecast and analysis are both anomalies against the time-dependent
         climatology, which is what the anomaly correlation is defined with.  ``clims`` and ``climatology`` together
-        are refused.  ``imag_ratio`` is added to the result."""
-        _climatology_args(climatology, times, "DmdForecast.verify")
-        if climatology is not None:
+        are refused.  ``trend``: a :class:`trend.Trend` that was removed before the fit (``trend_extra``: its user
+        series at ``times``): the analysis is detrended in the same scratch copy, after the climatology, and ``clims``
+        becomes zero; ``clims`` and ``trend`` together are refused as well.  ``imag_ratio`` is added to the result."""
+        _climatology_args(climatology, times, "DmdForecast.verify", trend)
+        if climatology is not None or trend is not None:
             if clims is not None:
-                raise ValueError("DmdForecast.verify: clims and climatology are two definitions of the anomaly; pass one")
+                raise ValueError("DmdForecast.verify: clims and climatology are two definitions of the anomaly; pass one"
+                                 if trend is None else
+                                 "DmdForecast.verify: clims and trend are two definitions of the anomaly; pass one")
             Xblocks = list(Xblocks)
-            Xblocks = climatology.remove_(Xblocks, times, out=[torch.empty(tuple(X.shape), dtype=X.dtype, device=X.device)
-                                                               for X in Xblocks])
+            scratch = [torch.empty(tuple(X.shape), dtype=X.dtype, device=X.device) for X in Xblocks]
+            if climatology is not None:
+                Xblocks = climatology.remove_(Xblocks, times, out=scratch)
+            if trend is not None:
+                Xblocks = trend.remove_(Xblocks, times, out=None if climatology is not None else scratch,
+                                        extra=trend_extra)
             clims = [torch.zeros(int(X.shape[1]), dtype=torch.float32, device=X.device) for X in Xblocks]
         if ensemble:
             Ct, _, imag = self.ensemble_coefficients(t)

@@ -721,6 +721,63 @@ class HipKernels:
         _lib.check(rc, "dmdx_clim_apply_f32")
         return Yt
 
+    # -- K21 ----------------------------------------------------------------
+    # the fit cuts time over workgroups (a workspace of segment sums, added in order by a second kernel) whenever
+    # there is more than one segment: rows alone fill half of the chip on a 129 780-row block (MEASUREMENTS.md K21).
+    # False walks the segments in one lane; the bits are the same.
+    treg_split = True
+
+    @property
+    def treg_max_p(self) -> int:
+        return int(self._lib.dmdx_treg_max_p())
+
+    def treg_fit(self, Xt: torch.Tensor, W: torch.Tensor, seg: int, out: torch.Tensor | None = None) -> torch.Tensor:
+        """The regression coefficients of every row of a block on a temporal design.  Xt: (T, m) fp32 (any row
+        stride); W: (p, T) fp64 contiguous, ``(D^T D)^-1 D^T`` of the (T, p) design (:func:`trend.weights`), p <= 8;
+        ``seg``: the segment length of the fp64 sums (part of the result: :data:`trend.SEGMENT`) -> coef (p, m)
+        fp32: per segment the sum of ``fp64(x) * W[j, t]`` in ascending t, the segment sums added in ascending
+        order, one rounding.  ``out``: a (p, m) fp32 view to write into (inner stride 1).  One read of Xt."""
+        if not isinstance(W, torch.Tensor) or W.dim() != 2:
+            raise _lib.DmdxError("treg_fit: W must be a (p, T) fp64 tensor")
+        p, T = int(W.shape[0]), int(W.shape[1])
+        if not 1 <= p <= self.treg_max_p or int(seg) < 1:
+            raise _lib.DmdxError(f"treg_fit: p = {p} outside 1..{self.treg_max_p} or seg = {seg} < 1")
+        m = int(Xt.shape[1]) if Xt.dim() == 2 else -1
+        ldx = _check_snapshots(Xt, m, T, Xt.device, "treg_fit")
+        _accumulator(W, (p, T), torch.float64, Xt.device, "treg_fit", "W")
+        coef, ldc = _out_view(out, m, p, torch.float32, Xt.device, "treg_fit")
+        split = self.treg_split and T > int(seg)
+        nbytes = int(self._lib.dmdx_treg_fit_workspace_bytes(m, T, p, int(seg))) if split else 0
+        ws = self._workspace(Xt.device, nbytes) if split else None
+        rc = self._timed("treg_fit", (m, T, p), lambda: self._lib.dmdx_treg_fit_f32(
+            _ptr(Xt), m, T, ldx, _ptr(W), p, T, int(seg), _ptr(coef), ldc, _ptr(ws), nbytes, self._stream()
+        ))
+        _lib.check(rc, "dmdx_treg_fit_f32")
+        return coef
+
+    def treg_apply_(self, Xt: torch.Tensor, D: torch.Tensor, coef: torch.Tensor, restore: bool = False,
+                    out: torch.Tensor | None = None) -> torch.Tensor:
+        """The fitted regression removed from the snapshots, or put back: ``y = fp32(fp64(x) -+ f)`` with
+        ``f = sum over j of fp64(coef[j, i]) * D[t, j]`` in ascending j (fp64, products rounded), + with
+        ``restore``.  Xt: (T, m) fp32; D: (T, p) fp64 contiguous, the design at the times of the snapshots; coef:
+        (p, m) fp32 (inner stride 1).  In place by default; ``out``: a (T, m) fp32 view that does not overlap Xt.
+        -> the tensor written.  One read and one write."""
+        if not isinstance(D, torch.Tensor) or D.dim() != 2:
+            raise _lib.DmdxError("treg_apply: D must be a (T, p) fp64 tensor")
+        T, p = int(D.shape[0]), int(D.shape[1])
+        if not 1 <= p <= self.treg_max_p:
+            raise _lib.DmdxError(f"treg_apply: p = {p} outside 1..{self.treg_max_p}")
+        m = int(Xt.shape[1]) if Xt.dim() == 2 else -1
+        ldx = _check_snapshots(Xt, m, T, Xt.device, "treg_apply")
+        _accumulator(D, (T, p), torch.float64, Xt.device, "treg_apply", "D")
+        _, ldc = _out_view(coef, m, p, torch.float32, Xt.device, "treg_apply coef")
+        Yt, ldy = (Xt, ldx) if out is None else _out_view(out, m, T, torch.float32, Xt.device, "treg_apply")
+        rc = self._timed("treg_apply", (m, T, p), lambda: self._lib.dmdx_treg_apply_f32(
+            _ptr(Xt), m, T, ldx, _ptr(D), p, p, _ptr(coef), ldc, int(bool(restore)), _ptr(Yt), ldy, self._stream()
+        ))
+        _lib.check(rc, "dmdx_treg_apply_f32")
+        return Yt
+
     # -- K20 ----------------------------------------------------------------
     @staticmethod
     def _row_count(count, m: int, device, who: str) -> None:

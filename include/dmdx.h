@@ -629,6 +629,44 @@ int dmdx_clim_apply_f32(const float* X, int64_t m, int64_t T, int64_t ldx, const
 int dmdx_row_missing_count_f32(const float* X, int64_t n, int64_t m, int64_t ldx, int32_t* count, void* stream);
 int dmdx_row_mask_apply_f32(float* X, int64_t n, int64_t m, int64_t ldx, const int32_t* count, float value, void* stream);
 
+/* ---- K21: least-squares regression of every row of a row block on a small temporal design, fitted and removed --------
+ * The companion of K18 for what is not a class of the calendar: an intercept, a polynomial trend, annual and diurnal
+ * harmonics and user series (an ENSO index) as the p <= dmdx_treg_max_p() (8) columns of a design matrix D (T x p).  The
+ * host forms D and W = (D^T D)^-1 D^T (p x T) in fp64; both are data here.  X is a row block as everywhere: T columns
+ * (snapshots) of m floats, ldx >= m.
+ *   W      (device fp64) W[j ldw + t], ldw >= T.         D   (device fp64) D[t ldd + j], ldd >= p.
+ *   coef   (device fp32) coef[j ldc + i], p x m, ldc >= m.
+ *   fit    time is cut into segments of `seg` >= 1 snapshots, [0, seg), [seg, 2 seg), ...  For row i and regressor j:
+ *            tot = +0.0; for every segment in ascending order { acc = +0.0;
+ *              for t ascending in the segment { q = fp64(X[i, t]) * W[j, t] (rounded); acc = acc + q; }  tot = tot + acc; }
+ *            coef[j, i] = fp32(tot)
+ *          all in fp64, never an FMA.  The partition is part of the result and the launch geometry is not: with
+ *          `workspace` (dmdx_treg_fit_workspace_bytes(m, T, p, seg) bytes = ceil(T / seg) p m doubles, no initialisation
+ *          needed) every segment is summed by workgroups of its own and a second kernel adds the partials in ascending
+ *          order; with workspace == NULL one lane walks the segments of its rows one after another.  Both give the same
+ *          bits.  seg >= T is the single chain.  All p sums of a row are formed in one lane: X is read once whatever p is.
+ *   apply  f = +0.0; for j ascending { q = fp64(coef[j, i]) * D[t, j] (rounded); f = f + q; }
+ *          restore == 0: y = fp32(fp64(x) - f)      restore != 0: y = fp32(fp64(x) + f)      -- one rounding to fp32.
+ *          Y == X with ldy == ldx runs in place; any other overlap of the two address ranges is refused.
+ * No allocation, no synchronisation, no atomics: results are bit-wise reproducible.
+ * Memory: only the logical elements of X, W, D and coef are read, only the logical p x m elements of coef, m x T elements
+ * of Y and the declared workspace bytes are written.  No alignment is asked for beyond that of the element types: a
+ * 16-byte aligned X with ldx % 4 == 0 is summed with 16-byte loads (4 rows per lane, the ragged last quad element by
+ * element), anything else one dword per lane; apply stores full chunks of Y as aligned 16-byte stores whatever Y and
+ * ldy are -- all with the same bits.
+ * Values: a non-finite X[i, t] makes the p coefficients of row i non-finite and reaches nothing else; a row of zeros has
+ * coefficients of +0.0 whatever the signs of W; integer X with W on a binary grid and sums below 2^53 come out exactly.
+ * A refused call (DMDX_E_INVALID: a null X, W, D, coef or Y; a negative size; m, T, seg or a leading dimension >= 2^31;
+ * ldx, ldc or ldy < m; ldw < T; ldd < p; p outside 1 .. 8; seg < 1; a pointer not aligned to its element; a workspace
+ * smaller than asked for; X and Y overlapping other than in place) has written nothing.  m == 0 or T == 0 returns 0
+ * after the checks without a launch: coef of T == 0 is not written. */
+int dmdx_treg_max_p(void);
+size_t dmdx_treg_fit_workspace_bytes(int64_t m, int64_t T, int64_t p, int64_t seg);
+int dmdx_treg_fit_f32(const float* X, int64_t m, int64_t T, int64_t ldx, const double* W, int p, int64_t ldw, int64_t seg,
+                      float* coef, int64_t ldc, void* workspace /* nullable */, size_t workspace_bytes, void* stream);
+int dmdx_treg_apply_f32(const float* X, int64_t m, int64_t T, int64_t ldx, const double* D, int p, int64_t ldd,
+                        const float* coef, int64_t ldc, int restore, float* Y, int64_t ldy, void* stream);
+
 /* ---- upper triangle of a symmetric fp64 matrix <-> packed row by row ---------------------
  * packed[i (2n - i + 1) / 2 + (j - i)] = A[i][j], j >= i: what the Gram all-reduce of the
  * row-sharded path moves (n (n + 1) / 2 doubles instead of n^2).  unpack writes both triangles. */
