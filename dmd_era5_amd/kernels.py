@@ -778,6 +778,35 @@ class HipKernels:
         _lib.check(rc, "dmdx_treg_apply_f32")
         return Yt
 
+    # -- K22 ----------------------------------------------------------------
+    @property
+    def tfilt_max_taps(self) -> int:
+        return int(self._lib.dmdx_tfilt_max_taps())
+
+    def tfilt(self, Xt: torch.Tensor, h: torch.Tensor, stride: int = 1, out: torch.Tensor | None = None) -> torch.Tensor:
+        """A FIR filter along time with an output stride.  Xt: (T, m) fp32 (any row stride); h: (L,) fp64 contiguous
+        on the device, L <= :attr:`tfilt_max_taps` -> Yt (T_out, m) fp32, ``T_out = (T - L) // stride + 1`` (valid
+        windows only): ``Yt[u] = fp32(sum over j of fp64(Xt[u stride + j]) * h[j])``, an fp64 chain in ascending j
+        with every product rounded.  ``out``: a (T_out, m) fp32 view that does not overlap Xt (inner stride 1).  One
+        read of the windows of Xt, one write."""
+        if not isinstance(h, torch.Tensor) or h.dim() != 1:
+            raise _lib.DmdxError("tfilt: h must be an (L,) fp64 tensor")
+        L, stride = int(h.shape[0]), int(stride)
+        if not 1 <= L <= self.tfilt_max_taps or stride < 1:
+            raise _lib.DmdxError(f"tfilt: L = {L} outside 1..{self.tfilt_max_taps} or stride = {stride} < 1")
+        m, T = (int(Xt.shape[1]), int(Xt.shape[0])) if Xt.dim() == 2 else (-1, -1)
+        ldx = _check_snapshots(Xt, m, T, Xt.device, "tfilt")
+        _accumulator(h, (L,), torch.float64, Xt.device, "tfilt", "h")
+        if T < L:
+            raise _lib.DmdxError(f"tfilt: {T} snapshots are fewer than the {L} taps of one window")
+        T_out = (T - L) // stride + 1
+        Yt, ldy = _out_view(out, m, T_out, torch.float32, Xt.device, "tfilt")
+        rc = self._timed("tfilt", (m, T, L, stride), lambda: self._lib.dmdx_tfilt_f32(
+            _ptr(Xt), m, T, ldx, _ptr(h), L, stride, _ptr(Yt), T_out, ldy, self._stream()
+        ))
+        _lib.check(rc, "dmdx_tfilt_f32")
+        return Yt
+
     # -- K20 ----------------------------------------------------------------
     @staticmethod
     def _row_count(count, m: int, device, who: str) -> None:

@@ -667,6 +667,37 @@ int dmdx_treg_fit_f32(const float* X, int64_t m, int64_t T, int64_t ldx, const d
 int dmdx_treg_apply_f32(const float* X, int64_t m, int64_t T, int64_t ldx, const double* D, int p, int64_t ldd,
                         const float* coef, int64_t ldc, int restore, float* Y, int64_t ldy, void* stream);
 
+/* ---- K22: a FIR filter along time with an output stride: daily means, low-pass + decimation, band-pass ----------------
+ * The fourth preparation step on the device, before K18 and K21: a weighted sum over a sliding window of snapshots.  X
+ * and Y are row blocks as everywhere: snapshot t of X at X + t ldx, output snapshot u of Y at Y + u ldy, m floats each,
+ * ldx, ldy >= m.  h holds L <= dmdx_tfilt_max_taps() (2048) device doubles.  The caller chooses T_out with
+ * (T_out - 1) stride + L <= T: "valid" windows only, no padding, no reflection; a time slab with its halo is a pointer
+ * offset.  For row i and output u:
+ *     acc = +0.0; for j = 0 .. L - 1 ascending { q = fp64(X[i, u stride + j]) * h[j] (rounded); acc = acc + q; }
+ *     Y[i, u] = fp32(acc)
+ * all in fp64, never an FMA, one rounding to fp32; taps are not folded.  The launch geometry is not part of the result:
+ * a lane that walks the union window of a run of outputs adds every snapshot to each output whose window holds it, in
+ * ascending t, which is ascending j for every one of them.
+ * No workspace, no allocation, no atomics, no synchronisation: results are bit-wise reproducible.
+ * Memory: only the logical elements of X that some window addresses are read -- never the snapshots behind the last
+ * window, never the snapshots between two windows where stride > L -- and only h[0 .. L); only the logical m x T_out
+ * elements of Y are written.  No alignment is asked for beyond that of the element types: full chunks of 4 rows of Y go
+ * out as aligned 16-byte stores whatever Y and ldy are (the chunks of an output start at the 16-byte boundary at or
+ * before its row 0, the ragged first and last chunk element by element); X is read with 16-byte loads, 4 rows per lane,
+ * where ldx % 4 == 0 and X + u ldx shares the 16-byte phase of Y + u ldy (an aligned X and an aligned Y with ldx % 4 ==
+ * ldy % 4 == 0), element by element otherwise -- all with the same bits.
+ * Values: IEEE, nothing more.  A non-finite X[i, t] reaches exactly the outputs of row i whose window holds t -- under a
+ * zero tap too (Inf * 0 is NaN) -- and nothing else; a row of zeros gives +0.0 whatever the signs of h; 2^e X gives 2^e Y
+ * bit for bit (magnitudes as above); integer X with taps on a binary grid and sums below 2^53 come out exactly.
+ * A refused call (DMDX_E_INVALID: a null X, h or Y; a negative size; L < 1 or L > dmdx_tfilt_max_taps(); stride < 1;
+ * (T_out - 1) stride + L > T; ldx or ldy < m; m, T, T_out, stride or a leading dimension >= 2^31; (T - 1) ldx + m or
+ * (T_out - 1) ldy + m >= 2^60 elements (the overlap test works on byte extents that fit 64 bits); a pointer not aligned to
+ * its element; any overlap of the address ranges of X (all T snapshots) and Y: there is no in-place form) has written
+ * nothing.  m == 0 or T_out == 0 returns 0 after the checks without a launch. */
+int dmdx_tfilt_max_taps(void);
+int dmdx_tfilt_f32(const float* X, int64_t m, int64_t T, int64_t ldx, const double* h, int64_t L, int64_t stride,
+                   float* Y, int64_t T_out, int64_t ldy, void* stream);
+
 /* ---- upper triangle of a symmetric fp64 matrix <-> packed row by row ---------------------
  * packed[i (2n - i + 1) / 2 + (j - i)] = A[i][j], j >= i: what the Gram all-reduce of the
  * row-sharded path moves (n (n + 1) / 2 doubles instead of n^2).  unpack writes both triangles. */
