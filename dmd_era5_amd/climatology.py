@@ -21,6 +21,7 @@ from dataclasses import dataclass
 import numpy as np
 import torch
 
+from . import _timeaxis as ta
 from .labeled import Coord, DataArray, Dataset
 from .svd import _kern
 
@@ -34,13 +35,7 @@ _LEAP_CUM = np.array([0, 31, 60, 91, 121, 152, 182, 213, 244, 274, 305, 335], dt
 def _calendar(times):
     """-> (month 0..11, day of the year 0..365 in the LEAP calendar -- Feb 29 is 59, Mar 1 is 60 in every year --,
     hour 0..23) of datetime64 time stamps."""
-    t = np.atleast_1d(np.asarray(times))
-    if not np.issubdtype(t.dtype, np.datetime64):
-        raise TypeError(f"slots_of: times must be numpy.datetime64, got {t.dtype}")
-    if t.ndim != 1:
-        raise ValueError(f"slots_of: times must be one-dimensional, got {t.shape}")
-    if np.isnat(t).any():
-        raise ValueError("slots_of: times holds NaT")
+    t = ta.stamps(times, "slots_of", TypeError)
     days = t.astype("datetime64[D]")
     months = t.astype("datetime64[M]")
     month = months.astype(np.int64) % 12
@@ -94,15 +89,6 @@ def slots_of(times, kind: str, window_days: int = 0):
     return slot.astype(np.int32), order, start, S
 
 
-def _attr_int(v) -> int:
-    return int(np.asarray(v).reshape(-1)[0])
-
-
-def _attr_str(v) -> str:
-    v = np.asarray(v).reshape(-1)[0] if not isinstance(v, (str, bytes)) else v
-    return v.decode() if isinstance(v, bytes) else str(v)
-
-
 @dataclass
 class Climatology:
     """The slot climatology of a list of row blocks: ``mean`` (and ``sd``) hold one ``(S, rows)`` fp32 tensor per
@@ -131,13 +117,11 @@ class Climatology:
         kern = _kern(kern)
         _, order, start, S = slots_of(times, kind, window_days)
         T = int(np.atleast_1d(np.asarray(times)).shape[0])
-        lists, mean, sd = {}, [], []
+        orders, starts, mean, sd = ta.OnDevices(order), ta.OnDevices(start), [], []
         for b, X in enumerate(Xblocks):
             if X.shape[0] != T:
                 raise ValueError(f"Climatology.fit: block {b} holds {int(X.shape[0])} snapshots, times has {T}")
-            if X.device not in lists:
-                lists[X.device] = (torch.from_numpy(order).to(X.device), torch.from_numpy(start).to(X.device))
-            o, s = lists[X.device]
+            o, s = orders.on(X.device), starts.on(X.device)
             mean.append(kern.clim_mean(X, o, s))
             if with_std:
                 sd.append(kern.clim_std(X, o, s, mean[-1], ddof=ddof))
@@ -158,15 +142,13 @@ class Climatology:
         if len(Xblocks) != len(self.mean):
             raise ValueError(f"Climatology.{who}: {len(Xblocks)} blocks, the climatology holds {len(self.mean)}")
         kern = _kern(self.kern)
-        labels, res = {}, []
+        labels, res = ta.OnDevices(slot), []
         for b, X in enumerate(Xblocks):
             if tuple(X.shape) != (slot.shape[0], int(self.mean[b].shape[1])):
                 raise ValueError(f"Climatology.{who}: block {b} is {tuple(X.shape)}, {slot.shape[0]} times and "
                                  f"{int(self.mean[b].shape[1])} rows asked for")
-            if X.device not in labels:
-                labels[X.device] = torch.from_numpy(slot).to(X.device)
             sd = self.sd[b] if (use_sd and self.sd is not None) else None
-            res.append(kern.clim_apply_(X, labels[X.device], self.mean[b], sd, restore=restore,
+            res.append(kern.clim_apply_(X, labels.on(X.device), self.mean[b], sd, restore=restore,
                                         out=None if out is None else out[b]))
         return res
 
@@ -193,11 +175,7 @@ class Climatology:
         ``window_days``, ``ddof``; ``coords``: the per-row coordinates of the decomposed array (``space`` and what
         lives on it), taken over as they are.  ``io_netcdf.to_netcdf`` writes it."""
         S = self.n_slots
-        cds = {"slot": Coord("slot", np.arange(S, dtype=np.int64))}
-        for name, c in (coords or {}).items():
-            c = c if isinstance(c, Coord) else Coord(name, c)
-            if set(c.dims) <= {"space"} or name == "space":
-                cds[name] = c
+        cds = {"slot": Coord("slot", np.arange(S, dtype=np.int64)), **ta.row_coords(coords)}
         ds = Dataset(coords=cds, attrs={"kind": self.kind, "window_days": int(self.window_days), "ddof": int(self.ddof)})
         row = {k: v for k, v in cds.items() if k != "slot"}
 
@@ -216,25 +194,17 @@ class Climatology:
         counts of the blocks to cut the fields into (default: one block); ``device``: where they go (default: the
         GPU for the HIP provider)."""
         kern = _kern(kern)
-        if device is None:
-            device = torch.device("cuda" if getattr(kern, "name", "") == "hip" else "cpu")
-        kind = _attr_str(ds.attrs["kind"])
+        kind = ta.attr_str(ds.attrs["kind"])
         if kind not in KINDS:
             raise ValueError(f"Climatology.from_dataset: kind = {kind!r}")
         mean = np.ascontiguousarray(np.asarray(ds["clim_mean"].values), dtype=np.float32)
-        S, M = mean.shape
+        S = mean.shape[0]
         if S != KINDS[kind]:
             raise ValueError(f"Climatology.from_dataset: clim_mean holds {S} slots, kind {kind!r} has {KINDS[kind]}")
-        rows = [M] if rows is None else [int(r) for r in rows]
-        if sum(rows) != M:
-            raise ValueError(f"Climatology.from_dataset: rows sum to {sum(rows)}, the file holds {M}")
-        edges = np.concatenate([[0], np.cumsum(rows)]).astype(np.int64)
-
-        def cut(a):
-            return [torch.from_numpy(np.ascontiguousarray(a[:, i:j])).to(device) for i, j in zip(edges[:-1], edges[1:])]
-
+        mean = ta.cut_rows(mean, rows, device, kern, "Climatology.from_dataset")
         sd = None
         if "clim_std" in ds:
-            sd = cut(np.ascontiguousarray(np.asarray(ds["clim_std"].values), dtype=np.float32))
+            sd = ta.cut_rows(np.ascontiguousarray(np.asarray(ds["clim_std"].values), dtype=np.float32), rows, device,
+                             kern, "Climatology.from_dataset")
         counts = np.asarray(ds["clim_count"].values).astype(np.int64).reshape(-1)
-        return cls(kind, _attr_int(ds.attrs["window_days"]), cut(mean), sd, counts, _attr_int(ds.attrs["ddof"]), kern)
+        return cls(kind, ta.attr_int(ds.attrs["window_days"]), mean, sd, counts, ta.attr_int(ds.attrs["ddof"]), kern)

@@ -16,13 +16,12 @@
 // The lists are data, not arguments the host has checked: start is clamped to [0, n_order], an entry of order outside
 // [0, T) is skipped and not counted, a label outside [0, S) leaves its snapshot alone.  A wrong list gives wrong
 // means; it never addresses anything outside X, mean or sd.
-#include "dmdx_common.h"
+#include "time_rows.h"
 
 #pragma clang fp contract(off)
 
 namespace {
 
-constexpr unsigned kQuietNaN = 0x7FC00000u;
 constexpr int kInFlight = 8;       // snapshot loads issued before the 8 sequential adds
 
 // grid.x: chunks of 256 R rows, grid.y: slots (strided when S > gridDim.y).  A lane owns R consecutive rows and R
@@ -119,14 +118,6 @@ __global__ __launch_bounds__(256) void clim_stat_kernel(const float* __restrict_
     clim_stat_rows<R, STD, false>(X + r0, nr, T, ldx, order, n_order, start, S, mp, ldc, ddof, out + r0, ldo);
 }
 
-__device__ __forceinline__ f32x4 load4(const float* p) {
-  if (((uintptr_t)p & 15u) == 0) return *reinterpret_cast<const f32x4*>(p);
-  f32x4 v;
-#pragma unroll
-  for (int e = 0; e < 4; ++e) v[e] = p[e];
-  return v;
-}
-
 __device__ __forceinline__ float apply_one(float x, float mu, float sg, bool has_sd, bool restore) {
   if (restore) {
     const float y = has_sd ? x * sg : x;                        // two roundings: the file has no contraction
@@ -136,11 +127,10 @@ __device__ __forceinline__ float apply_one(float x, float mu, float sg, bool has
   return has_sd ? y / sg : y;                                   // correctly rounded fp32 divide (no fast-math), as K13
 }
 
-// grid.x: chunks of 4 consecutive rows per lane, grid.y: snapshots (strided when T > gridDim.y), as K14's kernel: the
-// chunks of snapshot t start `head` elements before row 0, so that every full chunk of Y goes out as one aligned
-// 16-byte store whatever Y and ldy are.  X, mean and sd are read with 16-byte loads where their address allows it and
-// dword by dword otherwise; both routes apply apply_one to the same values.  X and Y carry no __restrict__: Y == X is
-// the in-place case (a lane reads its own elements before it writes them).
+// grid.x: chunks of 4 consecutive rows per lane, head-shifted so that every full chunk of Y goes out as one aligned
+// 16-byte store (quad_at, time_rows.h); grid.y: snapshots (strided when T > gridDim.y).  X, mean and sd are read
+// with 16-byte loads where their address allows it and dword by dword otherwise; both routes apply apply_one to the
+// same values.  X and Y carry no __restrict__: Y == X is in place (a lane reads its own elements before it writes them).
 __global__ __launch_bounds__(256) void clim_apply_kernel(const float* X, int64_t m, int64_t T, int64_t ldx,
                                                          const int32_t* __restrict__ slot, int64_t S,
                                                          const float* __restrict__ mean, int64_t ldc,
@@ -155,26 +145,25 @@ __global__ __launch_bounds__(256) void clim_apply_kernel(const float* X, int64_t
     if (!has && inplace) continue;                              // a snapshot without a slot is not touched
     float* yt = Y + t * ldy;
     const float* xt = X + t * ldx;
-    const int head = (int)(((uintptr_t)yt >> 2) & 3u);         // elements of yt past a 16-byte boundary
-    const int64_t r = c * 4 - head;                            // first row of this lane's chunk
-    if (r >= m) continue;
-    const int lo = r < 0 ? (int)(-r) : 0;
-    const int hi = m - r < 4 ? (int)(m - r) : 4;
+    Quad<4> q = quad_at<4>(yt, c);
+    if (q.past(m)) continue;
+    q.clip(m);
+    const int64_t r = q.r;
     const float* mp = mean + (has ? (int64_t)sl * ldc : 0);
     const float* sp = has_sd ? sd + (has ? (int64_t)sl * lds : 0) : nullptr;
 
-    if (lo == 0 && hi == 4) {
-      f32x4 y = load4(xt + r);
+    if (q.full()) {
+      f32x4 y = ldq_any(xt + r);
       if (has) {
-        const f32x4 mu = load4(mp + r);
+        const f32x4 mu = ldq_any(mp + r);
         f32x4 sg = {1.f, 1.f, 1.f, 1.f};
-        if (has_sd) sg = load4(sp + r);
+        if (has_sd) sg = ldq_any(sp + r);
 #pragma unroll
         for (int e = 0; e < 4; ++e) y[e] = apply_one(y[e], mu[e], sg[e], has_sd, restore != 0);
       }
       *reinterpret_cast<f32x4*>(yt + r) = y;
     } else {
-      for (int e = lo; e < hi; ++e) {
+      for (int e = q.lo; e < q.hi; ++e) {
         float y = xt[r + e];
         if (has) y = apply_one(y, mp[r + e], has_sd ? sp[r + e] : 1.f, has_sd, restore != 0);
         yt[r + e] = y;
@@ -183,21 +172,12 @@ __global__ __launch_bounds__(256) void clim_apply_kernel(const float* X, int64_t
   }
 }
 
-constexpr int64_t kMaxSize = int64_t(1) << 31;
-
 int check_stat(const char* who, const float* X, int64_t m, int64_t T, int64_t ldx, const int32_t* order, int64_t n_order,
                const int32_t* start, int64_t S, const float* mean, int64_t ldc) {
   DMDX_CHECK_ARG(X && order && start && mean, "%s: null pointer", who);
-  DMDX_CHECK_ARG(m >= 0 && T >= 0 && n_order >= 0, "%s: negative size (m=%lld T=%lld n_order=%lld)", who, (long long)m,
-                 (long long)T, (long long)n_order);
-  DMDX_CHECK_ARG(S >= 1, "%s: S=%lld < 1", who, (long long)S);
-  DMDX_CHECK_ARG(m < kMaxSize && T < kMaxSize && ldx < kMaxSize && ldc < kMaxSize && S < kMaxSize && n_order < kMaxSize,
-                 "%s: a size >= 2^31 (m=%lld T=%lld ldx=%lld ldc=%lld S=%lld n_order=%lld)", who, (long long)m, (long long)T,
-                 (long long)ldx, (long long)ldc, (long long)S, (long long)n_order);
-  DMDX_CHECK_ARG(ldx >= m && ldc >= m, "%s: ldx=%lld or ldc=%lld < m=%lld", who, (long long)ldx, (long long)ldc, (long long)m);
-  DMDX_CHECK_ARG(((uintptr_t)X & 3u) == 0 && ((uintptr_t)mean & 3u) == 0 && ((uintptr_t)order & 3u) == 0 &&
-                     ((uintptr_t)start & 3u) == 0, "%s: a pointer is not aligned to its element", who);
-  return 0;
+  DMDX_CHECK_ARG(n_order >= 0 && n_order < kMaxSize, "%s: n_order=%lld outside 0..2^31-1", who, (long long)n_order);
+  DMDX_CHECK_ARG(S >= 1 && S < kMaxSize, "%s: S=%lld outside 1..2^31-1", who, (long long)S);
+  return check_block(who, m, T, {{"ldx", ldx}, {"ldc", ldc}}, {X, mean, order, start});
 }
 
 // 4 rows per lane when X allows 16-byte loads and the launch still has about 1024 workgroups (4 per CU): K5's
@@ -208,7 +188,7 @@ int launch_stat(const float* X, int64_t m, int64_t T, int64_t ldx, const int32_t
                 void* stream) {
   const bool quad = dmdx_aligned16(X) && ldx % 4 == 0 && S * ((m + 1023) / 1024) >= 1024;
   const int64_t rows_per_wg = quad ? 1024 : 256;
-  const dim3 grid((unsigned)((m + rows_per_wg - 1) / rows_per_wg), (unsigned)(S < 65535 ? S : 65535));
+  const dim3 grid((unsigned)((m + rows_per_wg - 1) / rows_per_wg), grid_rows(S));
   if (quad)
     hipLaunchKernelGGL((clim_stat_kernel<4, STD>), grid, dim3(256), 0, (hipStream_t)stream, X, m, T, ldx, order, n_order,
                        start, S, mean, ldc, ddof, out, ldo);
@@ -234,8 +214,7 @@ extern "C" int dmdx_clim_std_f32(const float* X, int64_t m, int64_t T, int64_t l
   if (int rc = check_stat("clim_std", X, m, T, ldx, order, n_order, start, S, mean, ldc)) return rc;
   DMDX_CHECK_ARG(sd, "clim_std: null sd");
   DMDX_CHECK_ARG(ddof == 0 || ddof == 1, "clim_std: ddof=%d outside 0..1", ddof);
-  DMDX_CHECK_ARG(lds >= m && lds < kMaxSize, "clim_std: lds=%lld < m=%lld or >= 2^31", (long long)lds, (long long)m);
-  DMDX_CHECK_ARG(((uintptr_t)sd & 3u) == 0, "clim_std: sd is not aligned to its element");
+  if (int rc = check_block("clim_std", m, T, {{"lds", lds}}, {sd})) return rc;
   if (m == 0) return 0;
   return launch_stat<true>(X, m, T, ldx, order, n_order, start, S, mean, ldc, ddof, sd, lds, stream);
 }
@@ -244,24 +223,13 @@ extern "C" int dmdx_clim_apply_f32(const float* X, int64_t m, int64_t T, int64_t
                                    const float* mean, int64_t ldc, const float* sd, int64_t lds, int restore, float* Y,
                                    int64_t ldy, void* stream) {
   DMDX_CHECK_ARG(X && slot && mean && Y, "clim_apply: null pointer");
-  DMDX_CHECK_ARG(m >= 0 && T >= 0, "clim_apply: negative size (m=%lld T=%lld)", (long long)m, (long long)T);
-  DMDX_CHECK_ARG(S >= 1, "clim_apply: S=%lld < 1", (long long)S);
-  DMDX_CHECK_ARG(m < kMaxSize && T < kMaxSize && ldx < kMaxSize && ldc < kMaxSize && ldy < kMaxSize && S < kMaxSize &&
-                     (!sd || lds < kMaxSize), "clim_apply: a size >= 2^31 (m=%lld T=%lld ldx=%lld ldc=%lld lds=%lld ldy=%lld S=%lld)",
-                 (long long)m, (long long)T, (long long)ldx, (long long)ldc, (long long)lds, (long long)ldy, (long long)S);
-  DMDX_CHECK_ARG(ldx >= m && ldc >= m && ldy >= m && (!sd || lds >= m),
-                 "clim_apply: a leading dimension < m=%lld (ldx=%lld ldc=%lld lds=%lld ldy=%lld)", (long long)m,
-                 (long long)ldx, (long long)ldc, (long long)lds, (long long)ldy);
-  DMDX_CHECK_ARG(((uintptr_t)X & 3u) == 0 && ((uintptr_t)Y & 3u) == 0 && ((uintptr_t)mean & 3u) == 0 &&
-                     ((uintptr_t)sd & 3u) == 0 && ((uintptr_t)slot & 3u) == 0, "clim_apply: a pointer is not aligned to its element");
+  DMDX_CHECK_ARG(S >= 1 && S < kMaxSize, "clim_apply: S=%lld outside 1..2^31-1", (long long)S);
+  if (int rc = check_block("clim_apply", m, T, {{"ldx", ldx}, {"ldc", ldc}, {"ldy", ldy}, {"lds", sd ? lds : ldc}},
+                           {X, Y, mean, sd, slot}))
+    return rc;
+  if (int rc = check_ranges("clim_apply", X, T, ldx, Y, T, ldy, m, true)) return rc;
   if (m == 0 || T == 0) return 0;
-  if (!(Y == X && ldy == ldx)) {                                // anything but the in-place case: the ranges must be disjoint
-    const uintptr_t x0 = (uintptr_t)X, x1 = x0 + 4 * (uintptr_t)((T - 1) * ldx + m);
-    const uintptr_t y0 = (uintptr_t)Y, y1 = y0 + 4 * (uintptr_t)((T - 1) * ldy + m);
-    DMDX_CHECK_ARG(x1 <= y0 || y1 <= x0, "clim_apply: X and Y overlap (only Y == X with ldy == ldx runs in place)");
-  }
-  const int64_t chunks = (m + 3 + 3) / 4;                       // + 3: the head shift of a column
-  const dim3 grid((unsigned)((chunks + 255) / 256), (unsigned)(T < 65535 ? T : 65535));
+  const dim3 grid((unsigned)((chunks_of<4>(m) + 255) / 256), grid_rows(T));
   hipLaunchKernelGGL(clim_apply_kernel, grid, dim3(256), 0, (hipStream_t)stream, X, m, T, ldx, slot, S, mean, ldc, sd, lds,
                      restore, Y, ldy);
   DMDX_LAUNCH_CHECK();

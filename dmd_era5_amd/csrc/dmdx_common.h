@@ -4,12 +4,10 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
-#include "../../include/dmdx.h"
+#include "dmdx_check.h"
 
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 typedef float f32x16 __attribute__((ext_vector_type(16)));
-
-void dmdx_set_error(const char* fmt, ...);
 
 // measurement aid (dmdx_set_clock_probe): 3 device uint64 the stamped kernels (K1 / K3 batch
 // launches, K2) add their core-clock cycles, reference ticks and workgroup count to; null = off
@@ -17,14 +15,6 @@ extern thread_local unsigned long long* dmdx_clock_probe_ptr;   // (per thread: 
 
 // compute units of the current device (cached per device; <= 0 if the query fails)
 int dmdx_device_cus();
-
-#define DMDX_CHECK_ARG(cond, ...)        \
-  do {                                   \
-    if (!(cond)) {                       \
-      dmdx_set_error(__VA_ARGS__);       \
-      return DMDX_E_INVALID;             \
-    }                                    \
-  } while (0)
 
 #define DMDX_HIP(expr)                                                        \
   do {                                                                        \

@@ -19,7 +19,6 @@ constexpr int kTX = 64, kTY = 4;                 // lanes of a workgroup: rows (
 constexpr int64_t kMinSplit = 64;                // a time split is never shorter than this many snapshots ...
 constexpr int64_t kTargetWorkgroups = 2048;      // ... and splits stop once the launch has 8 workgroups per CU
 constexpr int64_t kApplySplit = 64;               // snapshots per time split of apply (a multiple of kTY)
-constexpr int64_t kMaxSize = int64_t(1) << 31;
 
 __device__ __forceinline__ int not_finite(uint32_t bits) { return (bits & 0x7F800000u) == 0x7F800000u ? 1 : 0; }
 

@@ -17,7 +17,7 @@
 // ascending j.  Otherwise (block means: stride >= L, where every input feeds one output; or a Y whose rows change
 // their 16-byte phase from output to output) the lane forms its outputs one after another.  The tap h[t - u stride]
 // is the same for every lane of a launch: wave-uniform loads.
-#include "dmdx_common.h"
+#include "time_rows.h"
 
 #pragma clang fp contract(off)
 
@@ -29,8 +29,6 @@ constexpr int kMaxTaps = 2048;
 #endif
 constexpr int kRun = DMDX_TFILT_RUN;     // outputs per lane: kRun x 4 fp64 accumulators (MEASUREMENTS.md K22)
 constexpr int kInFlight = 4;             // snapshot loads issued before their adds (8 in the one-output walk)
-constexpr int64_t kMaxSize = int64_t(1) << 31;
-constexpr int64_t kMaxSpan = int64_t(1) << 60;   // elements from the first to the last of X or Y: 4 x that fits 64 bits
 
 // The quad of snapshot t: 4 floats at xp + t ldx.  VEC: one 16-byte load (the caller has checked the address);
 // FULL: all 4 rows exist; otherwise rows lo .. hi - 1 only, element by element, the others 0 (never stored).
@@ -172,9 +170,8 @@ __device__ __forceinline__ void tfilt_run(const float* __restrict__ xp, int lo, 
 }
 
 // grid.x: chunks of 4 consecutive rows per lane; grid.y: runs of kRun outputs (strided when there are more than
-// gridDim.y).  As in treg_apply_kernel / clim_apply_kernel the chunks of output u start `head` elements before row 0,
-// head = the elements of Y + u ldy past a 16-byte boundary, so that every full chunk of Y goes out as one aligned
-// 16-byte store whatever Y and ldy are.  X is read with 16-byte loads where ldx % 4 == 0 and the address of the
+// gridDim.y).  The chunks are head-shifted so that every full chunk of Y goes out as one aligned 16-byte store
+// (the geometry of Quad, time_rows.h).  X is read with 16-byte loads where ldx % 4 == 0 and the address of the
 // lane's quad allows it (an aligned X under a Y of phase 0), element by element otherwise.  RUN: ldy % 4 == 0, so the
 // head -- and with it the quad -- is the same for every output, and stride < L.
 template <bool RUN>
@@ -189,8 +186,8 @@ __global__ __launch_bounds__(256) void tfilt_kernel(const float* __restrict__ X,
     const int nout = T_out - u0 < kRun ? (int)(T_out - u0) : kRun;
     for (int k = 0; k < (RUN ? 1 : nout); ++k) {
       float* yu = Y + (u0 + k) * ldy;
-      const int head = (int)(((uintptr_t)yu >> 2) & 3u);
-      const int64_t r = c * 4 - head;                            // first row of this lane's chunk
+      const int head = (int)(((uintptr_t)yu >> 2) & 3u);       // Quad<4> of time_rows.h, spelled out: with quad_at
+      const int64_t r = c * 4 - head;                            // the compiler swaps the operands of one s_and_b64
       if (r >= m) continue;
       const int lo = r < 0 ? (int)(-r) : 0;
       const int hi = m - r < 4 ? (int)(m - r) : 4;
@@ -217,30 +214,16 @@ extern "C" int dmdx_tfilt_max_taps(void) { return kMaxTaps; }
 extern "C" int dmdx_tfilt_f32(const float* X, int64_t m, int64_t T, int64_t ldx, const double* h, int64_t L, int64_t stride,
                               float* Y, int64_t T_out, int64_t ldy, void* stream) {
   DMDX_CHECK_ARG(X && h && Y, "tfilt: null pointer");
-  DMDX_CHECK_ARG(m >= 0 && T >= 0 && T_out >= 0, "tfilt: negative size (m=%lld T=%lld T_out=%lld)", (long long)m,
-                 (long long)T, (long long)T_out);
   DMDX_CHECK_ARG(L >= 1 && L <= kMaxTaps, "tfilt: L=%lld outside 1..%d", (long long)L, kMaxTaps);
-  DMDX_CHECK_ARG(stride >= 1, "tfilt: stride=%lld < 1", (long long)stride);
-  DMDX_CHECK_ARG(m < kMaxSize && T < kMaxSize && T_out < kMaxSize && stride < kMaxSize && ldx < kMaxSize && ldy < kMaxSize,
-                 "tfilt: a size >= 2^31 (m=%lld T=%lld T_out=%lld stride=%lld ldx=%lld ldy=%lld)", (long long)m, (long long)T,
-                 (long long)T_out, (long long)stride, (long long)ldx, (long long)ldy);
+  DMDX_CHECK_ARG(stride >= 1 && stride < kMaxSize, "tfilt: stride=%lld outside 1..2^31-1", (long long)stride);
+  DMDX_CHECK_ARG(T_out >= 0 && T_out < kMaxSize, "tfilt: T_out=%lld outside 0..2^31-1", (long long)T_out);
+  if (int rc = check_block("tfilt", m, T, {{"ldx", ldx}, {"ldy", ldy}}, {X, Y}, {h})) return rc;
   DMDX_CHECK_ARG((T_out - 1) * stride + L <= T, "tfilt: the last window ends at (T_out - 1) stride + L = %lld > T=%lld",
                  (long long)((T_out - 1) * stride + L), (long long)T);
-  DMDX_CHECK_ARG(ldx >= m && ldy >= m, "tfilt: ldx=%lld or ldy=%lld < m=%lld", (long long)ldx, (long long)ldy, (long long)m);
-  DMDX_CHECK_ARG(((uintptr_t)X & 3u) == 0 && ((uintptr_t)Y & 3u) == 0 && ((uintptr_t)h & 7u) == 0,
-                 "tfilt: a pointer is not aligned to its element");
-  // the byte extents of X and Y as plain integers: (T - 1) ldx + m can reach 2^62 elements, and 4 times that wraps
-  DMDX_CHECK_ARG((T < 1 ? 0 : (T - 1) * ldx + m) < kMaxSpan && (T_out < 1 ? 0 : (T_out - 1) * ldy + m) < kMaxSpan,
-                 "tfilt: (T - 1) ldx + m or (T_out - 1) ldy + m >= 2^60 elements: no address range holds that");
+  if (int rc = check_ranges("tfilt", X, T, ldx, Y, T_out, ldy, m, false)) return rc;   // (there is no in-place form)
   if (m == 0 || T_out == 0) return 0;
-  {                                                             // T >= L >= 1 here; there is no in-place form
-    const uintptr_t x0 = (uintptr_t)X, x1 = x0 + 4 * (uintptr_t)((T - 1) * ldx + m);
-    const uintptr_t y0 = (uintptr_t)Y, y1 = y0 + 4 * (uintptr_t)((T_out - 1) * ldy + m);
-    DMDX_CHECK_ARG(x1 <= y0 || y1 <= x0, "tfilt: X and Y overlap (there is no in-place form)");
-  }
-  const int64_t chunks = (m + 3 + 3) / 4;                       // + 3: the head shift of an output
   const int64_t nrun = (T_out + kRun - 1) / kRun;
-  const dim3 grid((unsigned)((chunks + 255) / 256), (unsigned)(nrun < 65535 ? nrun : 65535));
+  const dim3 grid((unsigned)((chunks_of<4>(m) + 255) / 256), grid_rows(nrun));
   // every stride < L takes the union-window walk, also where the windows barely overlap ((kRun - 1) stride >= L: no
   // interior, every snapshot goes through the tested ramp); whether single outputs would be faster there is not measured
   if (stride < L && ldy % 4 == 0)

@@ -16,7 +16,7 @@
 //
 // All p accumulators of a row live in one lane (p is a template argument: the accumulators are registers), so X is
 // read once whatever p is.  W[., t] and D[t, .] are the same for every lane of a launch: wave-uniform loads.
-#include "dmdx_common.h"
+#include "time_rows.h"
 
 #pragma clang fp contract(off)
 
@@ -149,20 +149,11 @@ __global__ __launch_bounds__(256) void treg_combine_kernel(const double* __restr
   coef[j * ldc + i] = (float)tot;
 }
 
-__device__ __forceinline__ f32x4 load4(const float* p) {
-  if (((uintptr_t)p & 15u) == 0) return *reinterpret_cast<const f32x4*>(p);
-  f32x4 v;
-#pragma unroll
-  for (int e = 0; e < 4; ++e) v[e] = p[e];
-  return v;
-}
-
 // grid.x: chunks of 4 consecutive rows per lane, grid.y: runs of kApplyChunk snapshots (strided when there are more
-// than gridDim.y).  As clim_apply_kernel, the chunks of snapshot t start `head` elements before row 0, so that every
-// full chunk of Y goes out as one aligned 16-byte store whatever Y and ldy are.  A lane keeps the p coefficients of
-// its 4 rows in registers (as fp64) over the run and loads them again only when the head shift changes (never, when
-// ldy % 4 == 0): coef is read T / kApplyChunk times, not T times.  X and Y carry no __restrict__: Y == X is the
-// in-place case (a lane reads its own elements before it writes them).
+// than gridDim.y).  The chunks are head-shifted so that every full chunk of Y goes out as one aligned 16-byte store
+// (quad_at, time_rows.h).  A lane keeps the p coefficients of its 4 rows in registers (as fp64) over the run and loads
+// them again only when the head shift changes (never, when ldy % 4 == 0): coef is read T / kApplyChunk times, not T
+// times.  X and Y carry no __restrict__: Y == X is in place (a lane reads its own elements before it writes them).
 __global__ __launch_bounds__(256) void treg_apply_kernel(const float* X, int64_t m, int64_t T, int64_t ldx,
                                                          const double* __restrict__ D, int p, int64_t ldd,
                                                          const float* __restrict__ coef, int64_t ldc, int restore,
@@ -177,25 +168,24 @@ __global__ __launch_bounds__(256) void treg_apply_kernel(const float* X, int64_t
     for (int64_t t = t0; t < t1; ++t) {
       float* yt = Y + t * ldy;
       const float* xt = X + t * ldx;
-      const int head = (int)(((uintptr_t)yt >> 2) & 3u);       // elements of yt past a 16-byte boundary
-      const int64_t r = c * 4 - head;                          // first row of this lane's chunk
-      if (r >= m) continue;
-      const int lo = r < 0 ? (int)(-r) : 0;
-      const int hi = m - r < 4 ? (int)(m - r) : 4;
-      const bool full = lo == 0 && hi == 4;
-      if (head != have) {
-        have = head;
+      Quad<4> q = quad_at<4>(yt, c);
+      if (q.past(m)) continue;
+      q.clip(m);
+      const int64_t r = q.r;
+      const bool full = q.full();
+      if (q.head != have) {
+        have = q.head;
 #pragma unroll
         for (int j = 0; j < kMaxP; ++j) {
           if (j < p) {
             const float* cj = coef + j * ldc + r;
             if (full) {
-              const f32x4 v = load4(cj);
+              const f32x4 v = ldq_any(cj);
 #pragma unroll
               for (int e = 0; e < 4; ++e) cd[j][e] = (double)v[e];
             } else {
 #pragma unroll
-              for (int e = 0; e < 4; ++e) cd[j][e] = (e >= lo && e < hi) ? (double)cj[e] : 0.0;
+              for (int e = 0; e < 4; ++e) cd[j][e] = (e >= q.lo && e < q.hi) ? (double)cj[e] : 0.0;
             }
           }
         }
@@ -213,31 +203,20 @@ __global__ __launch_bounds__(256) void treg_apply_kernel(const float* X, int64_t
         }
       }
       if (full) {
-        f32x4 y = load4(xt + r);
+        f32x4 y = ldq_any(xt + r);
 #pragma unroll
         for (int e = 0; e < 4; ++e) y[e] = (float)(restore ? (double)y[e] + f[e] : (double)y[e] - f[e]);
         *reinterpret_cast<f32x4*>(yt + r) = y;
       } else {
 #pragma unroll
         for (int e = 0; e < 4; ++e)
-          if (e >= lo && e < hi) {
+          if (e >= q.lo && e < q.hi) {
             const double x = (double)xt[r + e];
             yt[r + e] = (float)(restore ? x + f[e] : x - f[e]);
           }
       }
     }
   }
-}
-
-constexpr int64_t kMaxSize = int64_t(1) << 31;
-
-int check_fit(const char* who, int64_t m, int64_t T, int64_t p, int64_t seg) {
-  DMDX_CHECK_ARG(m >= 0 && T >= 0, "%s: negative size (m=%lld T=%lld)", who, (long long)m, (long long)T);
-  DMDX_CHECK_ARG(p >= 1 && p <= kMaxP, "%s: p=%lld outside 1..%d", who, (long long)p, kMaxP);
-  DMDX_CHECK_ARG(seg >= 1, "%s: seg=%lld < 1", who, (long long)seg);
-  DMDX_CHECK_ARG(m < kMaxSize && T < kMaxSize && seg < kMaxSize, "%s: a size >= 2^31 (m=%lld T=%lld seg=%lld)", who,
-                 (long long)m, (long long)T, (long long)seg);
-  return 0;
 }
 
 // nseg p m doubles (the factors are below 2^31, 2^4 and 2^31: the product is formed in 128 bits and saturates)
@@ -253,7 +232,7 @@ int launch_fit(const float* X, int64_t m, int64_t T, int64_t ldx, const double* 
   const bool quad = dmdx_aligned16(X) && ldx % 4 == 0;
   const int64_t rows_per_wg = quad ? 1024 : 256;
   const unsigned gx = (unsigned)((m + rows_per_wg - 1) / rows_per_wg);
-  const dim3 grid(gx, ws ? (unsigned)(nseg < 65535 ? nseg : 65535) : 1u);
+  const dim3 grid(gx, ws ? grid_rows(nseg) : 1u);
   if (ws) {
     if (quad)
       hipLaunchKernelGGL((treg_fit_kernel<P, 4, true>), grid, dim3(256), 0, st, X, m, T, ldx, W, ldw, seg, nseg, ws, coef, ldc);
@@ -285,13 +264,10 @@ extern "C" int dmdx_treg_fit_f32(const float* X, int64_t m, int64_t T, int64_t l
                                  int64_t seg, float* coef, int64_t ldc, void* workspace, size_t workspace_bytes,
                                  void* stream) {
   DMDX_CHECK_ARG(X && W && coef, "treg_fit: null pointer");
-  if (int rc = check_fit("treg_fit", m, T, p, seg)) return rc;
-  DMDX_CHECK_ARG(ldx < kMaxSize && ldw < kMaxSize && ldc < kMaxSize, "treg_fit: a size >= 2^31 (ldx=%lld ldw=%lld ldc=%lld)",
-                 (long long)ldx, (long long)ldw, (long long)ldc);
-  DMDX_CHECK_ARG(ldx >= m && ldc >= m, "treg_fit: ldx=%lld or ldc=%lld < m=%lld", (long long)ldx, (long long)ldc, (long long)m);
-  DMDX_CHECK_ARG(ldw >= T, "treg_fit: ldw=%lld < T=%lld", (long long)ldw, (long long)T);
-  DMDX_CHECK_ARG(((uintptr_t)X & 3u) == 0 && ((uintptr_t)coef & 3u) == 0 && ((uintptr_t)W & 7u) == 0 &&
-                     ((uintptr_t)workspace & 7u) == 0, "treg_fit: a pointer is not aligned to its element");
+  DMDX_CHECK_ARG(p >= 1 && p <= kMaxP, "treg_fit: p=%d outside 1..%d", p, kMaxP);
+  DMDX_CHECK_ARG(seg >= 1 && seg < kMaxSize, "treg_fit: seg=%lld outside 1..2^31-1", (long long)seg);
+  if (int rc = check_block("treg_fit", m, T, {{"ldx", ldx}, {"ldc", ldc}}, {X, coef}, {W, workspace})) return rc;
+  DMDX_CHECK_ARG(ldw >= T && ldw < kMaxSize, "treg_fit: ldw=%lld < T=%lld or >= 2^31", (long long)ldw, (long long)T);
   const size_t need = fit_workspace_bytes(m, T, p, seg);
   DMDX_CHECK_ARG(!workspace || (need != SIZE_MAX && workspace_bytes >= need), "treg_fit: workspace of %zu bytes, %zu needed",
                  workspace_bytes, need);
@@ -314,25 +290,13 @@ extern "C" int dmdx_treg_fit_f32(const float* X, int64_t m, int64_t T, int64_t l
 extern "C" int dmdx_treg_apply_f32(const float* X, int64_t m, int64_t T, int64_t ldx, const double* D, int p, int64_t ldd,
                                    const float* coef, int64_t ldc, int restore, float* Y, int64_t ldy, void* stream) {
   DMDX_CHECK_ARG(X && D && coef && Y, "treg_apply: null pointer");
-  DMDX_CHECK_ARG(m >= 0 && T >= 0, "treg_apply: negative size (m=%lld T=%lld)", (long long)m, (long long)T);
   DMDX_CHECK_ARG(p >= 1 && p <= kMaxP, "treg_apply: p=%d outside 1..%d", p, kMaxP);
-  DMDX_CHECK_ARG(m < kMaxSize && T < kMaxSize && ldx < kMaxSize && ldc < kMaxSize && ldy < kMaxSize && ldd < kMaxSize,
-                 "treg_apply: a size >= 2^31 (m=%lld T=%lld ldx=%lld ldd=%lld ldc=%lld ldy=%lld)", (long long)m, (long long)T,
-                 (long long)ldx, (long long)ldd, (long long)ldc, (long long)ldy);
-  DMDX_CHECK_ARG(ldx >= m && ldc >= m && ldy >= m, "treg_apply: a leading dimension < m=%lld (ldx=%lld ldc=%lld ldy=%lld)",
-                 (long long)m, (long long)ldx, (long long)ldc, (long long)ldy);
-  DMDX_CHECK_ARG(ldd >= p, "treg_apply: ldd=%lld < p=%d", (long long)ldd, p);
-  DMDX_CHECK_ARG(((uintptr_t)X & 3u) == 0 && ((uintptr_t)Y & 3u) == 0 && ((uintptr_t)coef & 3u) == 0 &&
-                     ((uintptr_t)D & 7u) == 0, "treg_apply: a pointer is not aligned to its element");
+  if (int rc = check_block("treg_apply", m, T, {{"ldx", ldx}, {"ldc", ldc}, {"ldy", ldy}}, {X, Y, coef}, {D})) return rc;
+  DMDX_CHECK_ARG(ldd >= p && ldd < kMaxSize, "treg_apply: ldd=%lld < p=%d or >= 2^31", (long long)ldd, p);
+  if (int rc = check_ranges("treg_apply", X, T, ldx, Y, T, ldy, m, true)) return rc;
   if (m == 0 || T == 0) return 0;
-  if (!(Y == X && ldy == ldx)) {                                // anything but the in-place case: the ranges must be disjoint
-    const uintptr_t x0 = (uintptr_t)X, x1 = x0 + 4 * (uintptr_t)((T - 1) * ldx + m);
-    const uintptr_t y0 = (uintptr_t)Y, y1 = y0 + 4 * (uintptr_t)((T - 1) * ldy + m);
-    DMDX_CHECK_ARG(x1 <= y0 || y1 <= x0, "treg_apply: X and Y overlap (only Y == X with ldy == ldx runs in place)");
-  }
-  const int64_t chunks = (m + 3 + 3) / 4;                       // + 3: the head shift of a column
   const int64_t nrun = (T + kApplyChunk - 1) / kApplyChunk;
-  const dim3 grid((unsigned)((chunks + 255) / 256), (unsigned)(nrun < 65535 ? nrun : 65535));
+  const dim3 grid((unsigned)((chunks_of<4>(m) + 255) / 256), grid_rows(nrun));
   hipLaunchKernelGGL(treg_apply_kernel, grid, dim3(256), 0, (hipStream_t)stream, X, m, T, ldx, D, p, ldd, coef, ldc, restore,
                      Y, ldy);
   DMDX_LAUNCH_CHECK();

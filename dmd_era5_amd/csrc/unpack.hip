@@ -11,7 +11,7 @@
 // The multiply and the add are two roundings: the helper below switches contraction off, because
 // hipcc contracts a * b + c to an FMA by default (also through __dmul_rn / __dadd_rn, which are
 // plain operators in this toolchain).
-#include "dmdx_common.h"
+#include "time_rows.h"
 
 namespace {
 
@@ -20,7 +20,6 @@ struct UnpackSegs {
 };
 
 constexpr int kChunk = 8;          // codes per lane: one 16-byte load, two 16-byte stores
-constexpr unsigned kQuietNaN = 0x7FC00000u;
 
 __device__ __forceinline__ float unpack_value(int q, double sf, double ao) {
 #pragma clang fp contract(off)
@@ -30,8 +29,8 @@ __device__ __forceinline__ float unpack_value(int q, double sf, double ao) {
 }
 
 // grid.x: chunks of 8 consecutive rows (256 lanes per workgroup), grid.y: snapshots (strided when
-// T > gridDim.y).  The chunks of snapshot j start `head` elements before row 0, so that every full
-// chunk is stored with two aligned 16-byte stores whatever X and ldx are; the ragged chunks at both
+// T > gridDim.y).  The chunks are head-shifted (quad_at, time_rows.h), so that every full chunk is
+// stored with two aligned 16-byte stores whatever X and ldx are; the ragged chunks at both
 // ends of a column, the chunks that straddle two segments and the sources that are not 16-byte
 // aligned go element by element.  Both routes apply unpack_value to the same codes.
 __global__ __launch_bounds__(256) void unpack_i16_kernel(const int16_t* __restrict__ S, int64_t lds, int64_t T,
@@ -51,17 +50,16 @@ __global__ __launch_bounds__(256) void unpack_i16_kernel(const int16_t* __restri
 
   for (int64_t j = blockIdx.y; j < T; j += gridDim.y) {
     float* xj = X + j * ldx;
-    const int head = (int)(((uintptr_t)xj >> 2) & 3u);       // elements of xj past a 16-byte boundary
-    const int64_t r = c * kChunk - head;                      // first row of this lane's chunk
-    if (r >= rows) continue;
-    const int lo = r < 0 ? (int)(-r) : 0;
-    const int hi = rows - r < kChunk ? (int)(rows - r) : kChunk;
+    Quad<kChunk> q = quad_at<kChunk>(xj, c);
+    if (q.past(rows)) continue;
+    q.clip(rows);
+    const int64_t r = q.r;
     const int16_t* sj = S + j * tstep * lds;
-    const uint32_t g = row0 + (uint32_t)(r + lo);             // row inside the variable (< 2^31, host-checked)
+    const uint32_t g = row0 + (uint32_t)(r + q.lo);             // row inside the variable (< 2^31, host-checked)
     uint32_t sg = g / plane;
     uint32_t p = g - sg * plane;
 
-    if (lo == 0 && hi == kChunk && p + kChunk <= plane) {
+    if (q.full() && p + kChunk <= plane) {
       const int16_t* sp = sj + segs.off[sg] + p;
       short q[kChunk];
       if (((uintptr_t)sp & 15u) == 0) {
@@ -82,7 +80,7 @@ __global__ __launch_bounds__(256) void unpack_i16_kernel(const int16_t* __restri
       *reinterpret_cast<f32x4*>(xj + r) = a;
       *reinterpret_cast<f32x4*>(xj + r + 4) = b;
     } else {
-      for (int e = lo; e < hi; ++e) {
+      for (int e = q.lo; e < q.hi; ++e) {
         while (p >= plane) {                                  // into the next segment(s)
           p -= plane;
           ++sg;
@@ -129,8 +127,7 @@ extern "C" int dmdx_unpack_i16_f32(const int16_t* S, int64_t lds, int64_t T, int
   if (T == 0 || rows == 0) return 0;
   DMDX_CHECK_ARG(S && X, "unpack_i16: null pointer");
   DMDX_CHECK_ARG(((uintptr_t)X & 3u) == 0 && ((uintptr_t)S & 1u) == 0, "unpack_i16: S / X not aligned to their element");
-  const int64_t chunks = (rows + 3 + kChunk - 1) / kChunk;    // + 3: the head shift of a column
-  const dim3 grid((unsigned)((chunks + 255) / 256), (unsigned)(T < 65535 ? T : 65535));
+  const dim3 grid((unsigned)((chunks_of<kChunk>(rows) + 255) / 256), grid_rows(T));
   hipLaunchKernelGGL(unpack_i16_kernel, grid, dim3(256), 0, (hipStream_t)stream, S, lds, T, tstep, rows, (uint32_t)row0,
                      (uint32_t)plane, segs, scale_factor, add_offset, nfill, fill0, fill1, X, ldx, fill_count);
   DMDX_LAUNCH_CHECK();

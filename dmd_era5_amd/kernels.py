@@ -45,23 +45,34 @@ def _check_vec(v: torch.Tensor | None, m: int, device, who: str, name: str) -> N
         raise _lib.DmdxError(f"{who}: {name} must be a contiguous fp32 vector of length {m} on {device}")
 
 
+def _check_ivec(v, device, who: str, name: str, n: int | None = None) -> int:
+    """A device int32 vector (contiguous; ``n`` entries if given) -> its length."""
+    if (not isinstance(v, torch.Tensor) or v.dtype != torch.int32 or v.dim() != 1 or v.device != device
+            or not v.is_contiguous() or (n is not None and v.numel() != n)):
+        raise _lib.DmdxError(f"{who}: {name} must be a contiguous int32 vector"
+                             f"{'' if n is None else f' of length {n}'} on {device}")
+    return int(v.numel())
+
+
+def _check_field(t: torch.Tensor, m: int, T: int, dtype, device, who: str, name: str, kind: str = "") -> int:
+    """A (T, m) field on `device` (inner stride 1, any row stride) -> its leading dimension.  ``kind``: what the
+    message adds to the shape (" int16")."""
+    mt, Tt, ld = _check_mat(t, dtype, f"{who} {name}")
+    if (mt, Tt) != (m, T) or t.device != device:
+        raise _lib.DmdxError(f"{who}: {name} must be ({T}, {m}){kind} on {device}, got {tuple(t.shape)}")
+    return ld
+
+
 def _check_snapshots(Xt: torch.Tensor, m: int, T: int, device, who: str) -> int:
-    """The snapshots a score is taken against: (T, m) fp32 on `device` (any row stride) -> ldx."""
-    mx, Tx, ldx = _check_mat(Xt, torch.float32, f"{who} X")
-    if (mx, Tx) != (m, T) or Xt.device != device:
-        raise _lib.DmdxError(f"{who}: X must be ({T}, {m}) on {device}, got {tuple(Xt.shape)}")
-    return ldx
+    """The snapshots a kernel reads: (T, m) fp32 on `device` (any row stride) -> ldx."""
+    return _check_field(Xt, m, T, torch.float32, device, who, "X")
 
 
 def _out_view(out: torch.Tensor | None, m: int, T: int, dtype, device, who: str, kind: str = ""):
-    """The (T, m) field a kernel writes: ``out`` (inner stride 1, any row stride) or a fresh tensor -> (tensor, ld).
-    ``kind``: what the message adds to the shape (" int16")."""
+    """The (T, m) field a kernel writes: ``out`` (as :func:`_check_field`) or a fresh tensor -> (tensor, ld)."""
     if out is None:
         return torch.empty((T, m), dtype=dtype, device=device), m
-    mo, To, ld = _check_mat(out, dtype, f"{who} out")
-    if (mo, To) != (m, T) or out.device != device:
-        raise _lib.DmdxError(f"{who}: out must be ({T}, {m}){kind} on {device}, got {tuple(out.shape)}")
-    return out, ld
+    return out, _check_field(out, m, T, dtype, device, who, "out", kind)
 
 
 _DTYPE_NAME = {torch.float64: "fp64", torch.int64: "int64"}
@@ -639,21 +650,14 @@ class HipKernels:
 
     # -- K18 ----------------------------------------------------------------
     @staticmethod
-    def _clim_list(v: torch.Tensor, device, who: str, name: str, n: int | None = None) -> int:
-        """A device int32 vector of the slot lists (contiguous; ``n`` entries if given) -> its length."""
-        if (not isinstance(v, torch.Tensor) or v.dtype != torch.int32 or v.dim() != 1 or v.device != device
-                or not v.is_contiguous() or (n is not None and v.numel() != n)):
-            raise _lib.DmdxError(f"{who}: {name} must be a contiguous int32 vector"
-                                 f"{'' if n is None else f' of length {n}'} on {device}")
-        return int(v.numel())
-
-    @staticmethod
-    def _clim_field(t, S, m, device, who, name):
-        """An (S, m) fp32 climatology field with a row stride -> its leading dimension."""
-        mm, SS, ld = _check_mat(t, torch.float32, f"{who} {name}")
-        if (mm, SS) != (m, S) or t.device != device:
-            raise _lib.DmdxError(f"{who}: {name} must be ({S}, {m}) fp32 on {device}, got {tuple(t.shape)}")
-        return ld
+    def _clim_lists(Xt, order, start, who: str):
+        """X and the CSR slot lists of clim_mean / clim_std -> (m, T, ldx, n_order, S)."""
+        m, T, ldx = _check_mat(Xt, torch.float32, f"{who} X")
+        n_order = _check_ivec(order, Xt.device, who, "order")
+        S = _check_ivec(start, Xt.device, who, "start") - 1
+        if S < 1:
+            raise _lib.DmdxError(f"{who}: start must hold S + 1 >= 2 offsets")
+        return m, T, ldx, n_order, S
 
     def clim_mean(self, Xt: torch.Tensor, order: torch.Tensor, start: torch.Tensor,
                   out: torch.Tensor | None = None) -> torch.Tensor:
@@ -662,13 +666,8 @@ class HipKernels:
         ``start`` has S + 1 entries) -> mean (S, m) fp32: the fp64 sum over the list, in its order, divided by the
         number of entries inside [0, T) and rounded once; NaN for a slot without one.  ``out``: an (S, m) fp32 view
         to write into (inner stride 1)."""
-        m, T, ldx = _check_mat(Xt, torch.float32, "clim_mean X")
-        n_order = self._clim_list(order, Xt.device, "clim_mean", "order")
-        S = self._clim_list(start, Xt.device, "clim_mean", "start") - 1
-        if S < 1:
-            raise _lib.DmdxError("clim_mean: start must hold S + 1 >= 2 offsets")
-        mean = out if out is not None else torch.empty((S, m), dtype=torch.float32, device=Xt.device)
-        ldc = self._clim_field(mean, S, m, Xt.device, "clim_mean", "out")
+        m, T, ldx, n_order, S = self._clim_lists(Xt, order, start, "clim_mean")
+        mean, ldc = _out_view(out, m, S, torch.float32, Xt.device, "clim_mean")
         rc = self._timed("clim_mean", (m, T, S), lambda: self._lib.dmdx_clim_mean_f32(
             _ptr(Xt), m, T, ldx, _ptr(order), n_order, _ptr(start), S, _ptr(mean), ldc, self._stream()
         ))
@@ -680,14 +679,9 @@ class HipKernels:
         """The slot standard deviations about ``mean`` ((S, m) fp32 of :meth:`clim_mean`): the fp64 sum of the
         squared fp64 differences in the order of the list, divided by n_s - ddof, the correctly rounded root, one
         rounding to fp32; NaN where n_s - ddof <= 0.  Operands and ``out`` as :meth:`clim_mean`."""
-        m, T, ldx = _check_mat(Xt, torch.float32, "clim_std X")
-        n_order = self._clim_list(order, Xt.device, "clim_std", "order")
-        S = self._clim_list(start, Xt.device, "clim_std", "start") - 1
-        if S < 1:
-            raise _lib.DmdxError("clim_std: start must hold S + 1 >= 2 offsets")
-        ldc = self._clim_field(mean, S, m, Xt.device, "clim_std", "mean")
-        sd = out if out is not None else torch.empty((S, m), dtype=torch.float32, device=Xt.device)
-        lds = self._clim_field(sd, S, m, Xt.device, "clim_std", "out")
+        m, T, ldx, n_order, S = self._clim_lists(Xt, order, start, "clim_std")
+        ldc = _check_field(mean, m, S, torch.float32, Xt.device, "clim_std", "mean")
+        sd, lds = _out_view(out, m, S, torch.float32, Xt.device, "clim_std")
         rc = self._timed("clim_std", (m, T, S), lambda: self._lib.dmdx_clim_std_f32(
             _ptr(Xt), m, T, ldx, _ptr(order), n_order, _ptr(start), S, _ptr(mean), ldc, int(ddof), _ptr(sd), lds,
             self._stream()
@@ -702,18 +696,13 @@ class HipKernels:
         ``x [* sd] + mean`` (two roundings).  A label outside 0 .. S - 1 (-1) leaves its snapshot as it is.  In
         place by default; ``out``: a (T, m) fp32 view that does not overlap Xt.  -> the tensor written."""
         m, T, ldx = _check_mat(Xt, torch.float32, "clim_apply X")
-        self._clim_list(slot, Xt.device, "clim_apply", "slot", T)
+        _check_ivec(slot, Xt.device, "clim_apply", "slot", T)
         if mean.dim() != 2:
             raise _lib.DmdxError(f"clim_apply: mean must be (S, {m}) fp32, got {tuple(mean.shape)}")
         S = int(mean.shape[0])
-        ldc = self._clim_field(mean, S, m, Xt.device, "clim_apply", "mean")
-        lds = 0 if sd is None else self._clim_field(sd, S, m, Xt.device, "clim_apply", "sd")
-        Yt, ldy = Xt, ldx
-        if out is not None:
-            mo, To, ldy = _check_mat(out, torch.float32, "clim_apply out")
-            if (mo, To) != (m, T) or out.device != Xt.device:
-                raise _lib.DmdxError(f"clim_apply: out must be ({T}, {m}) fp32 on {Xt.device}, got {tuple(out.shape)}")
-            Yt = out
+        ldc = _check_field(mean, m, S, torch.float32, Xt.device, "clim_apply", "mean")
+        lds = 0 if sd is None else _check_field(sd, m, S, torch.float32, Xt.device, "clim_apply", "sd")
+        Yt, ldy = (Xt, ldx) if out is None else _out_view(out, m, T, torch.float32, Xt.device, "clim_apply")
         rc = self._timed("clim_apply", (m, T, S), lambda: self._lib.dmdx_clim_apply_f32(
             _ptr(Xt), m, T, ldx, _ptr(slot), S, _ptr(mean), ldc, _ptr(sd), lds, int(bool(restore)), _ptr(Yt), ldy,
             self._stream()
@@ -770,7 +759,7 @@ class HipKernels:
         m = int(Xt.shape[1]) if Xt.dim() == 2 else -1
         ldx = _check_snapshots(Xt, m, T, Xt.device, "treg_apply")
         _accumulator(D, (T, p), torch.float64, Xt.device, "treg_apply", "D")
-        _, ldc = _out_view(coef, m, p, torch.float32, Xt.device, "treg_apply coef")
+        ldc = _check_field(coef, m, p, torch.float32, Xt.device, "treg_apply", "coef")
         Yt, ldy = (Xt, ldx) if out is None else _out_view(out, m, T, torch.float32, Xt.device, "treg_apply")
         rc = self._timed("treg_apply", (m, T, p), lambda: self._lib.dmdx_treg_apply_f32(
             _ptr(Xt), m, T, ldx, _ptr(D), p, p, _ptr(coef), ldc, int(bool(restore)), _ptr(Yt), ldy, self._stream()
@@ -808,19 +797,13 @@ class HipKernels:
         return Yt
 
     # -- K20 ----------------------------------------------------------------
-    @staticmethod
-    def _row_count(count, m: int, device, who: str) -> None:
-        if (not isinstance(count, torch.Tensor) or count.dtype != torch.int32 or count.dim() != 1 or count.numel() != m
-                or count.device != device or not count.is_contiguous()):
-            raise _lib.DmdxError(f"{who}: count must be a contiguous int32 vector of length {m} on {device}")
-
     def row_missing_count(self, Xt: torch.Tensor, out: torch.Tensor | None = None) -> torch.Tensor:
         """How many snapshots of every row of a block are not finite (NaN of any payload, +-Inf; tested on the
         bits).  Xt: (n, m) fp32 (any row stride) -> count (m,) int32.  ``out``: a device int32 vector the counts
         are ADDED to (time slabs accumulate); a fresh one starts at zero.  One read of Xt, no temporary."""
         m, n, ldx = _check_mat(Xt, torch.float32, "row_missing_count X")
         count = out if out is not None else torch.zeros(m, dtype=torch.int32, device=Xt.device)
-        self._row_count(count, m, Xt.device, "row_missing_count")
+        _check_ivec(count, Xt.device, "row_missing_count", "count", m)
         rc = self._timed("row_missing_count", (m, n), lambda: self._lib.dmdx_row_missing_count_f32(
             _ptr(Xt), n, m, ldx, _ptr(count), self._stream()
         ))
@@ -832,7 +815,7 @@ class HipKernels:
         ``value`` (its bits: -0.0, NaN); the other rows are neither read nor written.  Xt may be a block of
         snapshots, a (k, rows) block of U^T or a stored field.  -> Xt."""
         m, n, ldx = _check_mat(Xt, torch.float32, "row_mask_apply X")
-        self._row_count(count, m, Xt.device, "row_mask_apply")
+        _check_ivec(count, Xt.device, "row_mask_apply", "count", m)
         rc = self._timed("row_mask_apply", (m, n), lambda: self._lib.dmdx_row_mask_apply_f32(
             _ptr(Xt), n, m, ldx, _ptr(count), float(value), self._stream()
         ))

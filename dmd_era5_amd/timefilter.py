@@ -20,9 +20,8 @@ from __future__ import annotations
 import math
 
 import numpy as np
-import torch
 
-from .climatology import _attr_int, _attr_str
+from . import _timeaxis as ta
 from .labeled import Coord, DataArray, Dataset
 from .svd import _kern
 
@@ -81,14 +80,7 @@ def response(taps, freq) -> np.ndarray:
 # ---- time stamps ----------------------------------------------------------------------------------------------------
 def _even_stamps(times, who: str) -> tuple[np.ndarray, int]:
     """-> (the stamps as datetime64[ns], their step in ns); anything but evenly spaced datetime64 is a ValueError."""
-    t = np.atleast_1d(np.asarray(times))
-    if not np.issubdtype(t.dtype, np.datetime64):
-        raise ValueError(f"{who}: times must be numpy.datetime64, got {t.dtype}")
-    if t.ndim != 1:
-        raise ValueError(f"{who}: times must be one-dimensional, got {t.shape}")
-    if np.isnat(t).any():
-        raise ValueError(f"{who}: times holds NaT")
-    t = t.astype("datetime64[ns]")
+    t = ta.stamps(times, who).astype("datetime64[ns]")
     if t.shape[0] < 2:
         return t, 0
     d = np.diff(t.astype(np.int64))
@@ -170,12 +162,9 @@ class TimeFilter:
                 if tuple(Y.shape) != (n, int(X.shape[1])):
                     raise ValueError(f"TimeFilter.apply: out[{b}] is {tuple(Y.shape)}, ({n}, {int(X.shape[1])}) asked for")
         kern = _kern(self.kern)
-        h = torch.from_numpy(self.taps)
-        hdev, res = {}, []
-        for b, X in enumerate(Xblocks):
-            if X.device not in hdev:
-                hdev[X.device] = h.to(X.device)
-            res.append(kern.tfilt(X, hdev[X.device], self.stride, out=None if out is None else out[b]))
+        h = ta.OnDevices(self.taps)
+        res = [kern.tfilt(X, h.on(X.device), self.stride, out=None if out is None else out[b])
+               for b, X in enumerate(Xblocks)]
         return res, t_out
 
     # -- constructors in physical units ---------------------------------------------------------------------------
@@ -237,4 +226,4 @@ class TimeFilter:
     def from_dataset(cls, ds: Dataset, kern=None) -> "TimeFilter":
         """The filter :meth:`to_dataset` stored (``io_netcdf.open_dataset`` of its file): the taps bit for bit."""
         taps = np.asarray(ds["filter_taps"].values, dtype=np.float64)
-        return cls(taps, _attr_int(ds.attrs["stride"]), _attr_str(ds.attrs["label"]), kern)
+        return cls(taps, ta.attr_int(ds.attrs["stride"]), ta.attr_str(ds.attrs["label"]), kern)

@@ -25,7 +25,7 @@ from dataclasses import dataclass
 import numpy as np
 import torch
 
-from .climatology import _attr_int, _attr_str
+from . import _timeaxis as ta
 from .labeled import Coord, DataArray, Dataset
 from .svd import _kern
 
@@ -37,17 +37,6 @@ SEGMENT = 1024
 MAX_TERMS = 8
 MAX_COND = 1e8
 _NS_PER_DAY = 86400.0e9
-
-
-def _stamps(times, who: str) -> np.ndarray:
-    t = np.atleast_1d(np.asarray(times))
-    if not np.issubdtype(t.dtype, np.datetime64):
-        raise ValueError(f"{who}: times must be numpy.datetime64, got {t.dtype}")
-    if t.ndim != 1:
-        raise ValueError(f"{who}: times must be one-dimensional, got {t.shape}")
-    if np.isnat(t).any():
-        raise ValueError(f"{who}: times holds NaT")
-    return t.astype("datetime64[ns]")
 
 
 def _extra(extra, T: int, who: str) -> np.ndarray:
@@ -67,7 +56,7 @@ def design(times, origin, half_span_days: float, degree: int = 1, harmonics: int
     ``cos, sin`` of ``2 pi h days / period_days`` for h = 1 .. ``harmonics``, ``days`` the days since ``origin``; the
     daily ``cos, sin`` of ``2 pi h days`` for h = 1 .. ``diurnal``; the columns of ``extra`` ((T,) or (T, q): user
     series, an ENSO index).  At most 8 columns."""
-    t = _stamps(times, "design")
+    t = ta.stamps(times, "design").astype("datetime64[ns]")
     degree, harmonics, diurnal = int(degree), int(harmonics), int(diurnal)
     if degree < 0 or harmonics < 0 or diurnal < 0:
         raise ValueError(f"design: degree = {degree}, harmonics = {harmonics}, diurnal = {diurnal} must be >= 0")
@@ -139,7 +128,7 @@ class Trend:
         ``times`` (T datetime64 stamps, evenly spaced or not) on :func:`design` with ``origin`` the mid-point of the
         fitted period and ``half_span_days`` half its length: one read of every block.  A design whose condition
         number exceeds 1e8 is a ValueError before any launch."""
-        t = _stamps(times, "Trend.fit")
+        t = ta.stamps(times, "Trend.fit").astype("datetime64[ns]")
         T = int(t.shape[0])
         if T < 1:
             raise ValueError("Trend.fit: no time stamps")
@@ -149,35 +138,29 @@ class Trend:
         half = half if half > 0.0 else 1.0
         ex = _extra(extra, T, "Trend.fit")
         D = design(t, origin, half, degree, harmonics, diurnal, period_days, extra)
-        W = torch.from_numpy(weights(D))
+        W = ta.OnDevices(weights(D))
         kern = _kern(kern)
-        Wdev, coef = {}, []
+        coef = []
         for b, X in enumerate(Xblocks):
             if X.shape[0] != T:
                 raise ValueError(f"Trend.fit: block {b} holds {int(X.shape[0])} snapshots, times has {T}")
-            if X.device not in Wdev:
-                Wdev[X.device] = W.to(X.device)
-            coef.append(kern.treg_fit(X, Wdev[X.device], SEGMENT))
+            coef.append(kern.treg_fit(X, W.on(X.device), SEGMENT))
         return cls(origin, half, int(degree), int(harmonics), int(diurnal), float(period_days), int(ex.shape[1]), coef, kern)
 
     # -- apply ----------------------------------------------------------------------------------------------------
     def _apply(self, Xblocks, times, extra, out, restore: bool, who: str) -> list:
-        D = torch.from_numpy(self.design(times, extra, who))        # (raises before any launch)
+        D = ta.OnDevices(self.design(times, extra, who))            # (raises before any launch)
+        T = int(D.host.shape[0])
         Xblocks = list(Xblocks)
         if len(Xblocks) != len(self.coef):
             raise ValueError(f"Trend.{who}: {len(Xblocks)} blocks, the trend holds {len(self.coef)}")
         for b, X in enumerate(Xblocks):
-            if tuple(X.shape) != (D.shape[0], int(self.coef[b].shape[1])):
-                raise ValueError(f"Trend.{who}: block {b} is {tuple(X.shape)}, {D.shape[0]} times and "
+            if tuple(X.shape) != (T, int(self.coef[b].shape[1])):
+                raise ValueError(f"Trend.{who}: block {b} is {tuple(X.shape)}, {T} times and "
                                  f"{int(self.coef[b].shape[1])} rows asked for")
         kern = _kern(self.kern)
-        Ddev, res = {}, []
-        for b, X in enumerate(Xblocks):
-            if X.device not in Ddev:
-                Ddev[X.device] = D.to(X.device)
-            res.append(kern.treg_apply_(X, Ddev[X.device], self.coef[b], restore=restore,
-                                        out=None if out is None else out[b]))
-        return res
+        return [kern.treg_apply_(X, D.on(X.device), self.coef[b], restore=restore, out=None if out is None else out[b])
+                for b, X in enumerate(Xblocks)]
 
     def remove_(self, Xblocks, times, out=None, extra=None) -> list:
         """``X <- fp32(fp64(X) - D(t) coef)`` for the snapshots taken at ``times``, one launch per block; in place, or
@@ -209,11 +192,7 @@ class Trend:
         ``half_span_days`` and ``period_days`` (``repr`` of the fp64: an exact round trip), ``degree``, ``harmonics``,
         ``diurnal``, ``n_extra``; ``coords``: the per-row coordinates of the decomposed array, taken over as they
         are.  ``io_netcdf.to_netcdf`` writes it."""
-        cds = {"term": Coord("term", np.arange(self.n_terms, dtype=np.int64))}
-        for name, c in (coords or {}).items():
-            c = c if isinstance(c, Coord) else Coord(name, c)
-            if set(c.dims) <= {"space"} or name == "space":
-                cds[name] = c
+        cds = {"term": Coord("term", np.arange(self.n_terms, dtype=np.int64)), **ta.row_coords(coords)}
         ds = Dataset(coords=cds, attrs={
             "origin": str(np.datetime64(self.origin, "ns")), "half_span_days": repr(float(self.half_span_days)),
             "period_days": repr(float(self.period_days)), "degree": int(self.degree), "harmonics": int(self.harmonics),
@@ -229,19 +208,13 @@ class Trend:
         the blocks to cut the coefficients into (default: one block); ``device``: where they go (default: the GPU for
         the HIP provider)."""
         kern = _kern(kern)
-        if device is None:
-            device = torch.device("cuda" if getattr(kern, "name", "") == "hip" else "cpu")
         coef = np.ascontiguousarray(np.asarray(ds["trend_coef"].values), dtype=np.float32)
-        p, M = coef.shape
-        rows = [M] if rows is None else [int(r) for r in rows]
-        if sum(rows) != M:
-            raise ValueError(f"Trend.from_dataset: rows sum to {sum(rows)}, the file holds {M}")
-        edges = np.concatenate([[0], np.cumsum(rows)]).astype(np.int64)
-        blocks = [torch.from_numpy(np.ascontiguousarray(coef[:, i:j])).to(device) for i, j in zip(edges[:-1], edges[1:])]
+        p = coef.shape[0]
+        blocks = ta.cut_rows(coef, rows, device, kern, "Trend.from_dataset")
         a = ds.attrs
-        res = cls(np.datetime64(_attr_str(a["origin"]), "ns"), float(_attr_str(a["half_span_days"])), _attr_int(a["degree"]),
-                  _attr_int(a["harmonics"]), _attr_int(a["diurnal"]), float(_attr_str(a["period_days"])),
-                  _attr_int(a["n_extra"]), blocks, kern)
+        res = cls(np.datetime64(ta.attr_str(a["origin"]), "ns"), float(ta.attr_str(a["half_span_days"])),
+                  ta.attr_int(a["degree"]), ta.attr_int(a["harmonics"]), ta.attr_int(a["diurnal"]),
+                  float(ta.attr_str(a["period_days"])), ta.attr_int(a["n_extra"]), blocks, kern)
         if res.n_terms != p:
             raise ValueError(f"Trend.from_dataset: trend_coef holds {p} terms, the attributes describe {res.n_terms}")
         return res

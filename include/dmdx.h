@@ -596,7 +596,8 @@ int dmdx_pack_f32_i16(const float* X, int64_t m, int64_t T, int64_t ldx, double 
  * apply 2^e on X and mean scales Y by 2^e bit for bit (magnitudes as above).
  * A refused call (DMDX_E_INVALID: a null X, order, start, mean, sd of dmdx_clim_std_f32, slot or Y; S < 1; ldx, ldc, ldy
  * or -- with sd given -- lds < m; ddof outside 0 .. 1; a negative size; a size >= 2^31; X and Y overlapping other than in
- * place) has written nothing.  m == 0 or T == 0 returns 0 after the checks; mean and std still fill their S x m output
+ * place) has written nothing.  dmdx_clim_apply_f32 also refuses, in place too, (T - 1) ldx + m or (T - 1) ldy + m >= 2^60
+ * elements, as K22 does.  m == 0 or T == 0 returns 0 after the checks; mean and std still fill their S x m output
  * (with NaN) when T == 0 and m > 0. */
 int dmdx_clim_mean_f32(const float* X, int64_t m, int64_t T, int64_t ldx, const int32_t* order, int64_t n_order,
                        const int32_t* start, int64_t S, float* mean, int64_t ldc, void* stream);
@@ -658,7 +659,8 @@ int dmdx_row_mask_apply_f32(float* X, int64_t n, int64_t m, int64_t ldx, const i
  * coefficients of +0.0 whatever the signs of W; integer X with W on a binary grid and sums below 2^53 come out exactly.
  * A refused call (DMDX_E_INVALID: a null X, W, D, coef or Y; a negative size; m, T, seg or a leading dimension >= 2^31;
  * ldx, ldc or ldy < m; ldw < T; ldd < p; p outside 1 .. 8; seg < 1; a pointer not aligned to its element; a workspace
- * smaller than asked for; X and Y overlapping other than in place) has written nothing.  m == 0 or T == 0 returns 0
+ * smaller than asked for; X and Y overlapping other than in place) has written nothing.  dmdx_treg_apply_f32 also
+ * refuses, in place too, (T - 1) ldx + m or (T - 1) ldy + m >= 2^60 elements, as K22 does.  m == 0 or T == 0 returns 0
  * after the checks without a launch: coef of T == 0 is not written. */
 int dmdx_treg_max_p(void);
 size_t dmdx_treg_fit_workspace_bytes(int64_t m, int64_t T, int64_t p, int64_t seg);

@@ -361,7 +361,10 @@ def test_refusals_write_nothing(L):
     good = dict(X=xp, m=m, T=T0, ldx=ld, slot=lp, S=S0, mean=gMin.ptr, ldc=ld, sd=None, lds=0, restore=0, Y=gY.ptr, ldy=ld)
     bad = [dict(X=None), dict(slot=None), dict(mean=None), dict(Y=None), dict(S=0), dict(ldx=m - 1), dict(ldc=m - 1),
            dict(ldy=m - 1), dict(sd=gMin.ptr, lds=m - 1), dict(m=big, ldx=big, ldc=big, ldy=big), dict(T=big),
-           dict(ldx=big), dict(ldc=big), dict(ldy=big), dict(sd=gMin.ptr, lds=big), dict(S=big), dict(m=-1), dict(T=-1)]
+           dict(ldx=big), dict(ldc=big), dict(ldy=big), dict(sd=gMin.ptr, lds=big), dict(S=big), dict(m=-1), dict(T=-1),
+           # sizes below 2^31 each whose extent (T - 1) ld + m does not fit the overlap test: out of place, in place, one side
+           dict(T=big - 1, ldx=big - 1, ldy=big - 1), dict(T=big - 1, ldx=big - 1, ldy=big - 1, Y=xp),
+           dict(T=big - 1, ldx=big - 1), dict(T=big - 1, ldy=big - 1)]
     for change in bad:
         assert L.dmdx_clim_apply_f32(*{**good, **change}.values(), st) == E_INVALID, change
     # sizes of zero: the checks, then nothing to do -- but mean / std of no snapshots are S x m NaN

@@ -356,7 +356,10 @@ def test_refusals_write_nothing(L):
     bad_a = [dict(X=None), dict(D=None), dict(coef=None), dict(Y=None), dict(m=-1), dict(T=-1), dict(ldx=m - 1),
              dict(ldc=m - 1), dict(ldy=m - 1), dict(ldd=p - 1), dict(p=0), dict(p=9), dict(m=big, ldx=big, ldc=big, ldy=big),
              dict(T=big), dict(ldx=big), dict(ldc=big), dict(ldy=big), dict(ldd=big), dict(X=gX.ptr + 2),
-             dict(Y=gY.ptr + 3), dict(coef=gCin.ptr + 1), dict(D=gD.ptr + 4)]
+             dict(Y=gY.ptr + 3), dict(coef=gCin.ptr + 1), dict(D=gD.ptr + 4),
+             # sizes below 2^31 each whose extent (T - 1) ld + m does not fit the overlap test: out of place, in place, one side
+             dict(T=big - 1, ldx=big - 1, ldy=big - 1), dict(T=big - 1, ldx=big - 1, ldy=big - 1, Y=gX.ptr),
+             dict(T=big - 1, ldx=big - 1), dict(T=big - 1, ldy=big - 1)]
     for change in bad_a:
         assert L.dmdx_treg_apply_f32(*{**good_a, **change}.values(), st) == E_INVALID, change
         assert L.dmdx_last_error()
