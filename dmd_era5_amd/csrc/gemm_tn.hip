@@ -23,6 +23,18 @@
 //   atomics => deterministic); a second kernel sums the K-splits in fp64 and
 //   writes D (both triangles in SYRK mode).  Row blocks are accumulated into D
 //   in fp64 (`accumulate`).
+//   K1's full 128 x 128 SYRK tiles (n > 96) run the same products on the bf16 matrix core instead (tn_unit with
+//   PL = 1, bf16_split.h): every fp32 value is split exactly into three bf16 planes h + m + l and six of the nine
+//   plane products (h h, h m, m h, h l, m m, l h) go as v_mfma_f32_32x32x16_bf16 into the same accumulator -- 24
+//   MFMAs of 8 passes per 16 k and wave instead of 32 of 16 passes.  The three dropped products stay below
+//   2^-21 |a b| per pair, about 2^-23 sum |a b| over a sum.  The bf16 MFMA truncates its sum a few bits below the
+//   fp32 ulp of its accumulator (one-signed: it shows on the diagonal of a Gram), so this body keeps its MFMA chains to
+//   ONE chunk of 32 rows and adds every chunk result into the second accumulator with rounded fp32 adds: at most
+//   2048 of them per unit, the same order as the 4096-row chain bound.  Inf / NaN keep numpy's classes (the class
+//   rule of bf16_split.h, on a wave-uniform slow path behind a detector; it assumes normal fp32 partners: Inf times
+//   a subnormal below 2^-133 gives NaN, not Inf).  Planes of values below ~2^-103 turn
+//   subnormal and lose bits; the host's magnitude guard rescales such data before it gets here.  K3, K3s, the 32- to
+//   112-row tiles and the small-n Gram stay on the fp32 MFMA; DMDX_K1_ARITH=f32 keeps K1 there too.
 //
 //   Chunk pipeline: both stages filled up front; chunk c runs k-steps 0..2, then the
 //   barrier, then k-step 3 (its fragments are already in registers), the refill of the
@@ -40,7 +52,7 @@
 // that sums the K-splits; dmdx_gemm_tn_blocks_f32 alone also takes the small-l kernel (K3s).
 // Environment knobs (tuning / A-B only, no result changes beyond rounding): DMDX_TN_MAX_CPS (chunks
 // per unit, default 2048), DMDX_TN_ROUNDS (rounds of 512 workgroups the K-splits aim at),
-// DMDX_TN_FORCE_TM, DMDX_TN_NO_TAILFIT, DMDX_NO_K3S, DMDX_K3S_32.  The timing-only ablations of
+// DMDX_TN_FORCE_TM, DMDX_TN_NO_TAILFIT, DMDX_NO_K3S, DMDX_K3S_32, DMDX_K1_ARITH (f32: K1 on the fp32 MFMA).  The timing-only ablations of
 // tn_unit (results are wrong) are a compile-time macro of the diagnostic build, DMDX_TN_ABL
 // (`make stamps ABL=2`): the product library has no such switch.
 #include <stdarg.h>
@@ -50,6 +62,7 @@
 #include <algorithm>
 #include <vector>
 
+#include "bf16_split.h"
 #include "dmdx_common.h"
 
 thread_local unsigned long long* dmdx_clock_probe_ptr = nullptr;  // dmdx_set_clock_probe (measurement aid)
@@ -71,6 +84,8 @@ constexpr int BT = 128;            // output tile edge
 constexpr int BK = 32;             // K rows per stage
 constexpr int FOLD = 128;          // chunks per fp32 chain (128 * 32 = 4096 rows) before it is folded into acc2
 constexpr int NTH = 256;
+typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
+typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
 
 struct TnParams {
   const float* A;   // MFMA "A" operand source: D rows
@@ -184,6 +199,14 @@ __device__ unsigned long long dmdx_stamp[12];   // [8] unit prologue, [9] partia
 #define DMDX_STAMP(var) do { } while (0)
 #endif
 
+// The lane's index, derived where it is asked for (two VALU instructions) and not carried in a register from
+// the kernel's entry: the plane k-step of tn_unit has none to spare across its chunk loop.
+__device__ __forceinline__ int lane_now() {
+  unsigned z = 0u;
+  asm volatile("" : "+v"(z));   // (not hoisted out of a loop, not merged with an earlier one)
+  return (int)__builtin_amdgcn_mbcnt_hi(~0u, __builtin_amdgcn_mbcnt_lo(~0u, z));
+}
+
 #define DMDX_LDS_PTR(p) ((__attribute__((address_space(3))) void*)(p))
 #define DMDX_GLB_PTR(p) ((const __attribute__((address_space(1))) void*)(p))
 
@@ -207,10 +230,20 @@ __device__ unsigned long long dmdx_stamp[12];   // [8] unit prologue, [9] partia
 //   contracts k = 16 u + 4 kk + e, two MFMAs per k-step and 16-column half of the wave's 32 columns).
 //   (8-byte reads per k-step -- the first version -- were two-way bank-conflicted: columns 2j and 2j + 1
 //   share a bank group under the piece swizzle; PMC: 27 % of the LDS-active cycles.)
-template <bool DMA, int ABL, int SK, int H16 = 0>
+// PL ("planes", the 128 x 128 SYRK tiles of K1 only): the k-step runs on the bf16 matrix core.  The same
+//   ds_read_b128 pieces feed two groups of 16 k per chunk: a lane's 8 k-values of group g are its pieces of
+//   the k-steps 2g and 2g + 1 (k = 16g + 4h + e and 16g + 8 + 4h + e, the same on both operands); every
+//   value is split into three bf16 planes (bf16_split.h) and the six products h h, h' m, m h', h' l, m m,
+//   l h' of a 32 x 32 block go as v_mfma_f32_32x32x16_bf16 into the same `acc` (its 16-register layout is
+//   that of the fp32 instruction).  Non-finite input: a running fma(x, 0, s) per group, one unordered
+//   compare, and a wave-uniform branch to the class-safe split; both give the same planes on finite values.
+//   Everything outside the k-step (staging, barrier, refill order, fold, commit) is that of the fp32 body.
+//   ABL 16 (timing only): no detector and no slow path.
+template <bool DMA, int ABL, int SK, int H16 = 0, int PL = 0>
 __device__ __forceinline__ void tn_unit(const TnParams& p, const int split, const int row0, const int col0,
                                         double* Pt, float* lds) {
   static_assert(!H16 || SK >= 1, "a 16-row block only below at least one 32-row block");
+  static_assert(!PL || (SK == 0 && H16 == 0), "the plane k-step is built for the 128 x 128 tile only");
 #ifdef DMDX_STAMPS
   unsigned long long pt0;
   asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(pt0)::"memory");
@@ -304,6 +337,9 @@ __device__ __forceinline__ void tn_unit(const TnParams& p, const int split, cons
   // into an fp64 tile in HBM instead cost 4.6 % -- ~115 VALU/VMEM instructions per fold,
   // each of which waits for an MFMA slot while the SIMD's other wave streams MFMAs.)
   // At the end of the unit acc + acc2 is stored once, as fp64, into the unit's partial tile.
+  // (All of the above is the fp32 k-step.  The plane k-step, PL, folds all four blocks after EVERY chunk: acc holds
+  // the 12 bf16 MFMAs of one chunk, 32 rows, and acc2 sums up to max_cps = 2048 chunk results with rounded fp32
+  // adds -- the bf16 MFMA cuts its sum below the ulp of a grown accumulator, one-signed; see the file header.)
   f32x16 acc2[MI][NI];
 #pragma unroll
   for (int mi = 0; mi < MI; ++mi)
@@ -315,6 +351,9 @@ __device__ __forceinline__ void tn_unit(const TnParams& p, const int split, cons
   f32x4 acch[2] = {{0.f, 0.f, 0.f, 0.f}, {0.f, 0.f, 0.f, 0.f}}, acch2[2] = {{0.f, 0.f, 0.f, 0.f}, {0.f, 0.f, 0.f, 0.f}};
   const int l15 = lane & 15, lkk = lane >> 4;
   const int lane_off = (64 * wr + 4 * lh) * BT + (SK ? 32 : 64) * wc + l31;
+  // (the commit's copy: the plane k-step derives it where it commits, from lane_now())
+  auto lane_off_of = [&](int ln) { return (64 * wr + 4 * (ln >> 5)) * BT + (SK ? 32 : 64) * wc + (ln & 31); };
+  int lane_off_c = PL ? 0 : lane_off;
 #define DMDX_BLOCK_OFF(mi, ni, r) ((32 * (mi) + ((r) & 3) + 8 * ((r) >> 2)) * BT + 32 * (ni))
 #define DMDX_FOLD(mi, ni)                                                         \
   do {                                                                            \
@@ -323,7 +362,7 @@ __device__ __forceinline__ void tn_unit(const TnParams& p, const int split, cons
   } while (0)
 #define DMDX_COMMIT(mi, ni)                                                       \
   do {                                                                            \
-    double* q_ = Pt + lane_off;                                                   \
+    double* q_ = Pt + lane_off_c;                                                 \
     _Pragma("unroll") for (int r = 0; r < 16; ++r)                                \
         __builtin_nontemporal_store((double)(acc[mi][ni][r] + acc2[mi][ni][r]),   \
                                     q_ + DMDX_BLOCK_OFF(mi, ni, r));              \
@@ -348,33 +387,71 @@ __device__ __forceinline__ void tn_unit(const TnParams& p, const int split, cons
   } while (0)
 
   if (nchunks <= 0) {  // empty split: the partial tile must still be defined
+    if constexpr (PL != 0) lane_off_c = lane_off_of(lane_now());
     DMDX_COMMIT_ALL();
     return;
   }
 
   // ---- global -> LDS for one chunk into stage st
-  auto stage_regs = [&](int chunk, int st, bool tail) {  // register path (tail / unaligned)
+  // (the lambdas take the DMA byte offsets as arguments: the plane k-step hands in the copies it parks in LDS)
+  auto stage_regs = [&](int chunk, int st, bool tail, const unsigned (&aoffb)[NPA], const unsigned (&boffb)[4]) {  // register path (tail / unaligned)
     const int64_t k0 = (int64_t)chunk * BK;
     f32x4 ra[NPA], rb[4];
+    // (plane k-step: no registers to spare for these offsets over the whole loop -- the LDS-DMA path needs them
+    // for its one tail chunk only.  The same values are derived here: from the DMA byte offsets and the lane's
+    // position, or, on the register path, as in the staging assignment above)
+    unsigned boff_[4], aoff_[NPA];
+    int stsb_[4], kqb_[4], stsa_[NPA], kqa_[NPA];
+    int tid_ = tid;
+    if constexpr (PL != 0) tid_ = 64 * wave + lane_now();   // (derived HERE: not hoisted out of the chunk loop again)
+    const int lane_ = tid_ & 63;
 #pragma unroll
     for (int i = 0; i < 4; ++i) {
-      const float* pb = Bbase + k0 + boff[i];
-      rb[i] = tail ? load4_tail(pb, k0 + kqb[i], kend) : f32x4{pb[0], pb[1], pb[2], pb[3]};
+      if constexpr (PL != 0 && DMA) {
+        const int lcb = 32 * wave + 8 * i + (lane_ >> 3), lca = (TM / 4) * wave + 8 * i + (lane_ >> 3);
+        kqb_[i] = 4 * ((lane_ & 7) ^ swz(lcb));
+        kqa_[i] = 4 * ((lane_ & 7) ^ swz(lca));
+        stsb_[i] = lcb * BK + 4 * (lane_ & 7);
+        stsa_[i] = lca * BK + 4 * (lane_ & 7);
+        boff_[i] = (boffb[i] - 3072u + 1024u * i) >> 2;
+        aoff_[i] = (aoffb[i] - 3072u + 1024u * i) >> 2;
+        asm volatile("" : "+v"(boff_[i]), "+v"(aoff_[i]));   // (no per-piece 64-bit pointer carried along the loop)
+      } else if constexpr (PL != 0) {
+        const int lc = (tid_ >> 3) + 32 * i, q = tid_ & 7;
+        int cb = col0 + lc, ca = row0 + lc;
+        cb = cb < p.ncol ? cb : p.ncol - 1;
+        ca = ca < p.nrow ? ca : p.nrow - 1;
+        boff_[i] = (unsigned)((int64_t)(cb - cb0) * p.ldb + 4 * q);
+        aoff_[i] = (unsigned)((int64_t)(ca - ra0) * p.lda + 4 * q);
+        stsb_[i] = stsa_[i] = lc * BK + 4 * (q ^ swz(lc));
+        kqb_[i] = kqa_[i] = 4 * q;
+      } else {
+        boff_[i] = boff[i]; stsb_[i] = stsb[i]; kqb_[i] = kqb[i];
+        if (i < NPA) {
+          const int ia = i < NPA ? i : 0;   // (the clamp is for the compiler's array-bounds warning alone: NPA < 4 for the short tiles)
+          aoff_[ia] = aoff[ia]; stsa_[ia] = stsa[ia]; kqa_[ia] = kqa[ia];
+        }
+      }
+    }
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+      const float* pb = Bbase + k0 + boff_[i];
+      rb[i] = tail ? load4_tail(pb, k0 + kqb_[i], kend) : f32x4{pb[0], pb[1], pb[2], pb[3]};
     }
 #pragma unroll
     for (int i = 0; i < NPA; ++i) {
-      const float* pa = Abase + k0 + aoff[i];
-      ra[i] = tail ? load4_tail(pa, k0 + kqa[i], kend) : f32x4{pa[0], pa[1], pa[2], pa[3]};
+      const float* pa = Abase + k0 + aoff_[i];
+      ra[i] = tail ? load4_tail(pa, k0 + kqa_[i], kend) : f32x4{pa[0], pa[1], pa[2], pa[3]};
     }
     // (H16: the last piece / the last group of 32 columns is only half inside the panel)
     const bool a_last_ok = !H16 || (DMA ? wave + 4 * (NPA - 1) < NPIECE : (tid >> 3) + 32 * (NPA - 1) < TM);
     float* as = lds + st * STG;
     float* bs = lds + st * STG + OPA;
 #pragma unroll
-    for (int i = 0; i < 4; ++i) *reinterpret_cast<f32x4*>(bs + stsb[i]) = rb[i];
+    for (int i = 0; i < 4; ++i) *reinterpret_cast<f32x4*>(bs + stsb_[i]) = rb[i];
 #pragma unroll
     for (int i = 0; i < NPA; ++i)
-      if (i + 1 < NPA || a_last_ok) *reinterpret_cast<f32x4*>(as + stsa[i]) = ra[i];
+      if (i + 1 < NPA || a_last_ok) *reinterpret_cast<f32x4*>(as + stsa_[i]) = ra[i];
   };
 // The 8 pieces of the next chunk in one asm block: 2 SALU (M0) + 8 VMEM, no VALU.  A wave
 // whose SIMD partner streams MFMAs gets ~one instruction issued per MFMA slot (stamps:
@@ -421,21 +498,23 @@ __device__ __forceinline__ void tn_unit(const TnParams& p, const int split, cons
     DMDX_DMA_A(ap, la);               \
     DMDX_DMA_B(bp, lb);               \
   } while (0)
-  auto stage_dma = [&](int chunk, int st) {
+  auto stage_dma = [&](int chunk, int st, const unsigned (&aoffb)[NPA], const unsigned (&boffb)[4]) {
     const int64_t k0 = (int64_t)chunk * BK;
     float* as = lds + st * STG + (H16 ? 8 * wave : (TM / 4) * wave) * BK;
     float* bs = lds + st * STG + OPA + (32 * wave) * BK;
-    DMDX_DMA_NEXT(Adma + 4 * k0, Bdma + 4 * k0, (unsigned)(uintptr_t)DMDX_LDS_PTR(as),
-                  (unsigned)(uintptr_t)DMDX_LDS_PTR(bs));
+    // (readfirstlane: wave-uniform by construction, but the "s" constraint of the asm block does not make it an SGPR)
+    DMDX_DMA_NEXT(Adma + 4 * k0, Bdma + 4 * k0, __builtin_amdgcn_readfirstlane((unsigned)(uintptr_t)DMDX_LDS_PTR(as)),
+                  __builtin_amdgcn_readfirstlane((unsigned)(uintptr_t)DMDX_LDS_PTR(bs)));
   };
-  auto stage = [&](int chunk, int st) {
+  auto stage_with = [&](int chunk, int st, const unsigned (&ao)[NPA], const unsigned (&bo)[4]) {
     if (DMA) {
-      if (chunk != tail_chunk) stage_dma(chunk, st);
-      else stage_regs(chunk, st, true);
+      if (chunk != tail_chunk) stage_dma(chunk, st, ao, bo);
+      else stage_regs(chunk, st, true, ao, bo);
     } else {
-      stage_regs(chunk, st, chunk == tail_chunk);
+      stage_regs(chunk, st, chunk == tail_chunk, ao, bo);
     }
   };
+  auto stage = [&](int chunk, int st) { stage_with(chunk, st, aoffb, boffb); };
 
   // ---- MFMA operand fragments, two register sets: the set for k-step t+1 is read from
   // LDS while the 16 MFMAs of k-step t run.  Lane (r = lane&31, h = lane>>5) reads, for
@@ -514,6 +593,147 @@ __device__ __forceinline__ void tn_unit(const TnParams& p, const int split, cons
   unsigned long long st0 = 0, st1 = 0, st2 = 0, st2b = 0, st3 = 0, st4 = 0, sa0 = 0, sa1 = 0, sa2 = 0, sa3 = 0, sa5 = 0;
 #endif
   int cur = 0;
+  if constexpr (PL != 0) {
+    // ---- plane k-step.  Blocks 0, 1: the A fragments (mi), 2, 3: the B fragments (ni).  One raw set: fa0 / fb0
+    // hold the piece of k-step 2g, fa1 / fb1 that of k-step 2g + 1; the next group's pieces are read once the
+    // planes (and the detector's verdict) of this one are there, and land behind its 24 MFMAs.
+    unsigned PH[4][4], PM[4][4], PLo[4][4];
+#define DMDX_SPLIT_GROUP(g)                                                                      \
+  do {                                                                                           \
+    __builtin_amdgcn_sched_barrier(0);  /* not among the MFMAs before it: two plane sets do not fit */ \
+    bf16split::f32x2_t d_ = {0.f, 0.f};                                                          \
+    _Pragma("unroll") for (int b_ = 0; b_ < 4; ++b_) {                                           \
+      const f32x4 e_ = b_ < 2 ? fa0[b_ & 1] : fb0[b_ & 1], o_ = b_ < 2 ? fa1[b_ & 1] : fb1[b_ & 1]; \
+      _Pragma("unroll") for (int q_ = 0; q_ < 4; ++q_) {                                         \
+        const bf16split::f32x2_t x_ = q_ < 2 ? bf16split::f32x2_t{e_[2 * (q_ & 1)], e_[2 * (q_ & 1) + 1]} \
+                                             : bf16split::f32x2_t{o_[2 * (q_ & 1)], o_[2 * (q_ & 1) + 1]}; \
+        unsigned h_, m_, l_;                                                                     \
+        bf16split::split2_fast_pair(x_, h_, m_, l_);                                             \
+        PH[b_][q_] = h_; PM[b_][q_] = m_; PLo[b_][q_] = l_;                                      \
+        if (!(ABL & 16)) d_ = bf16split::detect_pair(x_, d_);                                    \
+      }                                                                                          \
+    }                                                                                            \
+    bad = !(ABL & 16) && __builtin_amdgcn_ballot_w64(__builtin_isunordered(d_[0], d_[1])) != 0ull;   \
+    if (bad) {  /* rare, wave-uniform: the pieces once more, block by block (the scheduling barriers keep its */ \
+      /* register need below that of the fast path), and the class rule applied to the planes in place        */ \
+      _Pragma("unroll") for (int b_ = 0; b_ < 4; ++b_) {                                         \
+        const float* s_ = lds + cur * STG + (b_ < 2 ? frag_a : OPA + frag_b) + (b_ & 1) * 32 * BK; \
+        __builtin_amdgcn_sched_barrier(0);                                                       \
+        int f0_ = foff[0];                                                                       \
+        asm volatile("" : "+v"(f0_));  /* (derived here, see DMDX_GROUP_MFMA) */                  \
+        const f32x4 e_ = *reinterpret_cast<const f32x4*>(s_ + (f0_ ^ (8 * (2 * (g)))));          \
+        const f32x4 o_ = *reinterpret_cast<const f32x4*>(s_ + (f0_ ^ (8 * (2 * (g) + 1))));      \
+        _Pragma("unroll") for (int q_ = 0; q_ < 4; ++q_) {                                       \
+          const float x0_ = q_ < 2 ? e_[2 * (q_ & 1)] : o_[2 * (q_ & 1)];                        \
+          const float x1_ = q_ < 2 ? e_[2 * (q_ & 1) + 1] : o_[2 * (q_ & 1) + 1];                \
+          unsigned h_ = PH[b_][q_], m_ = PM[b_][q_], l_ = PLo[b_][q_];                           \
+          bf16split::make_safe2(x0_, x1_, h_, m_, l_);                                           \
+          PH[b_][q_] = h_; PM[b_][q_] = m_; PLo[b_][q_] = l_;                                    \
+        }                                                                                        \
+        __builtin_amdgcn_sched_barrier(0);                                                       \
+      }                                                                                          \
+    }                                                                                            \
+  } while (0)
+#define DMDX_PLANE(P, b) __builtin_bit_cast(bf16x8, (u32x4){P[b][0], P[b][1], P[b][2], P[b][3]})
+#define DMDX_MFMA_PL(PA, PB)                                                                     \
+  do {                                                                                           \
+    _Pragma("unroll") for (int mi_ = 0; mi_ < 2; ++mi_)                                          \
+        _Pragma("unroll") for (int ni_ = 0; ni_ < 2; ++ni_) acc[mi_][ni_] =                      \
+            __builtin_amdgcn_mfma_f32_32x32x16_bf16(DMDX_PLANE(PA, mi_), DMDX_PLANE(PB, 2 + ni_), acc[mi_][ni_], 0, 0, 0); \
+  } while (0)
+    // The 24 MFMAs of a group.  h h sees the raw h, the cross products the copy with 0 in place of a non-finite
+    // value (PH in place).  The l products come first: their registers take the B pieces of the next group
+    // (rd: read the pieces of k-steps t0, t0 + 1 of stage st for it -- the A pieces up front).
+#define DMDX_GROUP_MFMA(rd, st, t0, fresh)                                                            \
+  do {                                                                                           \
+    /* (foff[t] = foff[0] ^ 8 t -- the k-chunk index sits in bits 2 .. 4 -- derived here: one register, not four) */ \
+    int f0_ = foff[0];                                                                           \
+    asm volatile("" : "+v"(f0_));                                                                \
+    const int fe_ = f0_ ^ (8 * (t0)), fo_ = f0_ ^ (8 * ((t0) + 1));                              \
+    if (rd) {                                                                                    \
+      const float* as_ = lds + (st) * STG + frag_a;                                              \
+      fa0[0] = *reinterpret_cast<const f32x4*>(as_ + fe_);                                       \
+      fa0[1] = *reinterpret_cast<const f32x4*>(as_ + fe_ + 32 * BK);                             \
+      fa1[0] = *reinterpret_cast<const f32x4*>(as_ + fo_);                                       \
+      fa1[1] = *reinterpret_cast<const f32x4*>(as_ + fo_ + 32 * BK);                             \
+    }                                                                                            \
+    if (fresh) {  /* the chunk's first products start from zero: acc was folded into acc2 behind the last chunk */ \
+      _Pragma("unroll") for (int mi_ = 0; mi_ < 2; ++mi_)                                        \
+          _Pragma("unroll") for (int ni_ = 0; ni_ < 2; ++ni_) acc[mi_][ni_] =                    \
+              __builtin_amdgcn_mfma_f32_32x32x16_bf16(DMDX_PLANE(PH, mi_), DMDX_PLANE(PH, 2 + ni_), f32x16(0.f), 0, 0, 0); \
+    } else {                                                                                     \
+      DMDX_MFMA_PL(PH, PH);                                                                      \
+    }                                                                                            \
+    if (bad) {                                                                                   \
+      _Pragma("unroll") for (int b_ = 0; b_ < 4; ++b_)                                           \
+          _Pragma("unroll") for (int q_ = 0; q_ < 4; ++q_) PH[b_][q_] = bf16split::sanitise2(PH[b_][q_]); \
+    }                                                                                            \
+    DMDX_MFMA_PL(PH, PLo);                                                                       \
+    DMDX_MFMA_PL(PLo, PH);                                                                       \
+    __builtin_amdgcn_sched_barrier(0);                                                           \
+    if (rd) {                                                                                    \
+      const float* bs_ = lds + (st) * STG + OPA + frag_b;                                        \
+      fb0[0] = *reinterpret_cast<const f32x4*>(bs_ + fe_);                                       \
+      fb0[1] = *reinterpret_cast<const f32x4*>(bs_ + fe_ + 32 * BK);                             \
+      fb1[0] = *reinterpret_cast<const f32x4*>(bs_ + fo_);                                       \
+      fb1[1] = *reinterpret_cast<const f32x4*>(bs_ + fo_ + 32 * BK);                             \
+    }                                                                                            \
+    DMDX_MFMA_PL(PH, PM);                                                                        \
+    DMDX_MFMA_PL(PM, PH);                                                                        \
+    DMDX_MFMA_PL(PM, PM);                                                                        \
+  } while (0)
+    bool bad = false;
+    DMDX_READ_FRAGS(fa1, fb1, 0, 1);
+    // The DMA byte offsets do not fit into the registers next to the planes: every thread parks its eight in LDS
+    // behind the stages (its own 32 bytes: no synchronisation) and reads them back ahead of every refill.
+    if constexpr (DMA) {
+      u32x4* park = reinterpret_cast<u32x4*>(lds + 2 * STG) + 2 * tid;
+      park[0] = u32x4{aoffb[0], aoffb[1], aoffb[2], aoffb[3]};
+      park[1] = u32x4{boffb[0], boffb[1], boffb[2], boffb[3]};
+    }
+    for (int c = 0; c < nchunks; ++c) {
+      DMDX_STAMP(st0);
+      const bool has_next = (c + 1 < nchunks) && !(ABL & 1);
+      DMDX_STAMP(st1);
+      DMDX_SPLIT_GROUP(0);
+      DMDX_GROUP_MFMA(true, cur, 2, true);
+      DMDX_SPLIT_GROUP(1);
+      DMDX_STAMP(st2);
+      unsigned pa[NPA] = {0u, 0u, 0u, 0u}, pb[4] = {0u, 0u, 0u, 0u};
+      if (DMA && c + 2 < nchunks) {
+        const u32x4* park = reinterpret_cast<const u32x4*>(lds + 2 * STG) + 2 * (64 * wave + lane_now());
+        const u32x4 a_ = park[0], b_ = park[1];
+        pa[0] = a_[0]; pa[1] = a_[1]; pa[2] = a_[2]; pa[3] = a_[3];
+        pb[0] = b_[0]; pb[1] = b_[1]; pb[2] = b_[2]; pb[3] = b_[3];
+      }
+
+      if (DMA) __builtin_amdgcn_s_waitcnt(0x0f70);  // vmcnt(0): the asm LDS-DMA pieces are invisible to the compiler's counters
+      DMDX_STAMP(st2b);
+      if (!(ABL & 2)) __syncthreads();
+      if (c + 2 < nchunks && !(ABL & 1)) stage_with(c_begin + c + 2, cur, pa, pb);
+      cur ^= 1;
+      DMDX_STAMP(st3);
+      DMDX_GROUP_MFMA(has_next, cur, 0, false);
+      // The bf16 MFMA truncates its sum a few bits below the fp32 ulp of the accumulator (measured: a one-signed
+      // 6e-7 on the diagonal of a Gram with 1312-row chains, growing with the chain), so the plane body keeps its
+      // MFMA chains to ONE chunk: every chunk's 32-row result is added into acc2 by rounded fp32 adds (32 packed
+      // adds per chunk) and the next chunk starts from zero.  acc2 then sums at most 2048 chunk results.
+      if (!(ABL & 8)) {
+        DMDX_FOLD(0, 0); DMDX_FOLD(0, NI - 1); DMDX_FOLD(MI - 1, 0); DMDX_FOLD(MI - 1, NI - 1);
+      }
+#ifdef DMDX_STAMPS
+      DMDX_STAMP(st4);
+      sa0 += st1 - st0; sa1 += st2 - st1; sa2 += st3 - st2b; sa3 += st4 - st3; sa5 += st2b - st2;
+#endif
+    }
+    {  // (no register held across the loop for the commit)
+      lane_off_c = lane_off_of(lane_now());
+    }
+#undef DMDX_GROUP_MFMA
+#undef DMDX_MFMA_PL
+#undef DMDX_PLANE
+#undef DMDX_SPLIT_GROUP
+  } else {
   for (int c = 0; c < nchunks; ++c) {
     DMDX_STAMP(st0);
     const bool has_next = (c + 1 < nchunks) && !(ABL & 1);
@@ -563,6 +783,7 @@ __device__ __forceinline__ void tn_unit(const TnParams& p, const int split, cons
     DMDX_STAMP(st4);
     sa0 += st1 - st0; sa1 += st2 - st1; sa2 += st3 - st2b; sa3 += st4 - st3; sa5 += st2b - st2;
 #endif
+  }
   }
 #ifdef DMDX_STAMPS
   if (lane == 0) {
@@ -617,10 +838,12 @@ __device__ __forceinline__ int xcd_unit(int b, int total) {
 // D (+)= sum_j A_j^T B_j over a batch of row blocks (TnBatch); p carries what the blocks share
 // (shape of D, tiles, P).  SYRK: A_j == B_j, triangle tiles.  A single product is the batch of one
 // block: unit_begin = {0, units}, slab_begin = {0, nsplit}, no padding.
-template <bool DMA, int SK = 0, int H16 = 0>
+// PL: the plane k-step of tn_unit (the 128 x 128 SYRK tiles of K1, unless DMDX_K1_ARITH=f32).
+template <bool DMA, int SK = 0, int H16 = 0, int PL = 0>
 __global__ __launch_bounds__(NTH, 2) void syrk_batch_kernel(TnParams p, TnBatch bt) {
   constexpr int TM = SK ? 32 * SK + 16 * H16 : BT;
-  __shared__ __attribute__((aligned(16))) float lds[2 * (TM + BT) * BK];
+  // (plane k-step on the LDS-DMA path: + 32 bytes per thread for its parked DMA offsets; 72 KiB, two workgroups per CU)
+  __shared__ __attribute__((aligned(16))) float lds[2 * (TM + BT) * BK + (PL && DMA ? 8 * NTH : 0)];
   const int b = blockIdx.x;
   int j = 0;
   while (j + 1 < bt.nblocks && b >= bt.unit_begin[j + 1]) ++j;
@@ -643,14 +866,15 @@ __global__ __launch_bounds__(NTH, 2) void syrk_batch_kernel(TnParams p, TnBatch 
   // (measurement aid: two scalar clock reads around the unit, three atomics per workgroup; the
   // sustained core clock of the launch = 100 MHz * sum(cycles) / sum(ticks))
   unsigned long long c0 = 0, r0 = 0;
+  const int wave0 = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);   // (an SGPR: no VGPR held across the unit for the probe)
   if (bt.clk != nullptr) {
     c0 = __builtin_amdgcn_s_memtime();
     r0 = __builtin_amdgcn_s_memrealtime();
   }
-  tn_unit<DMA, DMDX_TN_ABL, SK, H16>(p, split, ta * TM, tb * BT, Pt, lds);
+  tn_unit<DMA, DMDX_TN_ABL, SK, H16, PL>(p, split, ta * TM, tb * BT, Pt, lds);
   if (bt.clk != nullptr) {
     const unsigned long long c1 = __builtin_amdgcn_s_memtime(), r1 = __builtin_amdgcn_s_memrealtime();
-    if (threadIdx.x == 0) {
+    if (wave0 == 0 && lane_now() == 0) {
       atomicAdd(&bt.clk[0], c1 - c0);
       atomicAdd(&bt.clk[1], r1 - r0);
       atomicAdd(&bt.clk[2], 1ull);
@@ -872,6 +1096,12 @@ int run_batch(const float* const* A, const int64_t* lda, const float* const* B, 
     p.nsplit = slabs;
     p.P = reinterpret_cast<double*>(ws);
     const dim3 grid((unsigned)units);
+    // K1's full tiles run the bf16-plane k-step; DMDX_K1_ARITH=f32 keeps them on the fp32 MFMA (A/B, rounding only)
+    const char* arith = getenv("DMDX_K1_ARITH");
+    if (pl.tm == BT && pl.syrk && !(arith != nullptr && strcmp(arith, "f32") == 0)) {
+      if (aligned) hipLaunchKernelGGL((syrk_batch_kernel<true, 0, 0, 1>), grid, dim3(NTH), 0, stream, p, bt);
+      else hipLaunchKernelGGL((syrk_batch_kernel<false, 0, 0, 1>), grid, dim3(NTH), 0, stream, p, bt);
+    } else
     switch (pl.tm) {
 #define DMDX_TN_CASE(TMV, SKV, HV)                                                                          \
       case TMV:                                                                                             \

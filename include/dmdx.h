@@ -103,7 +103,17 @@
  *     power-of-two factor commutes with every rounding: K1 / K3 of 2^e X equal 2^2e times the result for
  *     X bit for bit, K2 of 2^e X gives 2^e Y and 2^2e G.  All-positive (un-centred) data keep the error
  *     bound of one fp32 chain of at most 4096 rows + a blocked fp32 sum of at most 16 chain results + fp64
- *     beyond: ((min(K, 4096) / 2 + 18) 2^-24) sum |a||b|, whatever K is;
+ *     beyond: ((min(K, 4096) / 2 + 18) 2^-24) sum |a||b|, whatever K is.  K1 for n > 96 forms the products from
+ *     three bf16 planes per value on the bf16 matrix core and has a bound of its own, (c + 26) 2^-24 sum |a||b|
+ *     with c the chunks of 32 rows per work unit (at most 2048 unless DMDX_TN_MAX_CPS raises it): c - 1 rounded
+ *     fp32 adds of the chunk results, 13 for the 12 matrix instructions of a chunk (each rounds its sum and
+ *     cuts it five to six bits below the ulp first: (1 + 2^-4) 2^-24), 8 for the three dropped plane products
+ *     (at most 2^-21 |a||b| a pair), 2 for the fp32 copy and the fp64 sums, 4 to spare.  At c = 2048 that is
+ *     8 units of 2^-24 above the fp32 bodies' bound and inside what the tests hold both to (1.01 times
+ *     (2048 + 18) 2^-24); DMDX_K1_ARITH=f32 selects the fp32 products.  The class rule of the plane products
+ *     (Inf times a non-zero value stays Inf) needs the partner's leading plane to be non-zero: normal fp32
+ *     partners, which the magnitude interval above guarantees; a subnormal partner below 2^-133 truncates to
+ *     a zero plane and gives NaN where numpy has Inf;
  *   - small integers are exact: while a_A a_B K < 2^24 for operands with integer entries |a| <= a_A,
  *     |b| <= a_B (K2: n a_X a_W < 2^24; its fused Gram: max|y|^2 m < 2^24) every partial sum is an
  *     exactly representable integer in any order, and K1 / K3 / K2 return the integer result bit for bit
