@@ -796,6 +796,53 @@ class HipKernels:
         _lib.check(rc, "dmdx_tfilt_f32")
         return Yt
 
+    # -- K23 ----------------------------------------------------------------
+    @property
+    def coarsen_max_factor(self) -> int:
+        return int(self._lib.dmdx_coarsen_max_factor())
+
+    def coarsen(self, Xt: torch.Tensor, planes: int, nlat: int, nlon: int, w: torch.Tensor, fy: int, fx: int, *,
+                ldp: int | None = None, lat0: int = 0, lon0: int = 0, n_lat_out: int | None = None,
+                n_lon_out: int | None = None, skipna: bool = False, min_frac: float = 0.0,
+                out: torch.Tensor | None = None, ldq: int | None = None) -> torch.Tensor:
+        """The area-weighted block mean over ``fy x fx`` cells of the latitude / longitude grid.  Xt: (T, m) fp32 (any
+        row stride), every snapshot ``planes`` planes of ``nlat x nlon`` points, plane p at ``p * ldp`` (default
+        ``nlat * nlon``; rows beyond the last plane are pad and are not read); w: (nlat,) fp64 contiguous on the
+        device, the weight of every fine latitude row -> Yt (T, rows_out) fp32, ``rows_out = (planes - 1) ldq + NLAT
+        NLON``, plane p at ``p * ldq`` (default ``NLAT * NLON``), cell (I, J) at ``I * NLON + J``: the weighted mean
+        of the fine rows ``lat0 + I fy ..`` and longitudes ``lon0 + J fx ..``, an fp64 chain in ascending order with one
+        rounding to fp32 (include/dmdx.h, K23).  ``n_lat_out`` / ``n_lon_out``: fewer cells than fit (default: all
+        whole cells).  ``skipna``: values that are not finite are left out of a cell, and a cell whose kept weight is
+        below ``min_frac`` of its full weight is NaN.  ``out``: a (T, rows_out) fp32 view that does not overlap Xt
+        (inner stride 1).  One read of the cells of Xt, one write."""
+        planes, nlat, nlon, fy, fx, lat0, lon0 = (int(v) for v in (planes, nlat, nlon, fy, fx, lat0, lon0))
+        fmax = self.coarsen_max_factor
+        if not (1 <= fy <= fmax and 1 <= fx <= fmax) or min(planes, nlat, nlon, lat0, lon0) < 0:
+            raise _lib.DmdxError(f"coarsen: fy = {fy} or fx = {fx} outside 1..{fmax}, or a negative size or offset")
+        NLAT = max(0, (nlat - lat0) // fy) if n_lat_out is None else int(n_lat_out)
+        NLON = max(0, (nlon - lon0) // fx) if n_lon_out is None else int(n_lon_out)
+        ldp = nlat * nlon if ldp is None else int(ldp)
+        ldq = NLAT * NLON if ldq is None else int(ldq)
+        if NLAT < 0 or NLON < 0 or ldp < nlat * nlon or ldq < NLAT * NLON:
+            raise _lib.DmdxError(f"coarsen: NLAT = {NLAT} or NLON = {NLON} negative, ldp = {ldp} < nlat nlon or "
+                                 f"ldq = {ldq} < NLAT NLON")
+        m, T = (int(Xt.shape[1]), int(Xt.shape[0])) if Xt.dim() == 2 else (-1, -1)
+        ldx = _check_snapshots(Xt, m, T, Xt.device, "coarsen")
+        need = (planes - 1) * ldp + nlat * nlon if planes else 0
+        if m < need:
+            raise _lib.DmdxError(f"coarsen: X holds {m} rows, {planes} planes of {nlat} x {nlon} (ldp = {ldp}) need {need}")
+        if not isinstance(w, torch.Tensor):
+            raise _lib.DmdxError("coarsen: w must be an (nlat,) fp64 tensor")
+        _accumulator(w, (nlat,), torch.float64, Xt.device, "coarsen", "w")
+        rows_out = (planes - 1) * ldq + NLAT * NLON if planes else 0
+        Yt, ldy = _out_view(out, rows_out, T, torch.float32, Xt.device, "coarsen")
+        rc = self._timed("coarsen", (planes, nlat, nlon, T, fy, fx), lambda: self._lib.dmdx_coarsen_f32(
+            _ptr(Xt), T, ldx, planes, ldp, nlat, nlon, _ptr(w), fy, fx, lat0, lon0, NLAT, NLON,
+            int(bool(skipna)), float(min_frac), _ptr(Yt), ldy, ldq, self._stream()
+        ))
+        _lib.check(rc, "dmdx_coarsen_f32")
+        return Yt
+
     # -- K20 ----------------------------------------------------------------
     def row_missing_count(self, Xt: torch.Tensor, out: torch.Tensor | None = None) -> torch.Tensor:
         """How many snapshots of every row of a block are not finite (NaN of any payload, +-Inf; tested on the

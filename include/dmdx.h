@@ -710,6 +710,45 @@ int dmdx_tfilt_max_taps(void);
 int dmdx_tfilt_f32(const float* X, int64_t m, int64_t T, int64_t ldx, const double* h, int64_t L, int64_t stride,
                    float* Y, int64_t T_out, int64_t ldy, void* stream);
 
+/* ---- K23: the area-weighted block mean over fy x fx cells of the latitude / longitude grid (coarsening) -----------------
+ * The preparation step of the space axis, before K22: ERA5 at 0.25 degrees becomes the 1 degree grid a DMD is fitted on,
+ * with one read of X and one write of X / (fy fx).  X is a row block as everywhere: snapshot t at X + t ldx.  A snapshot
+ * holds P planes (variable x level), plane p at p ldp, ldp >= nlat nlon; the slack is pad (that of pad4) and is never
+ * read.  Inside a plane latitude row i and longitude j sit at i nlon + j, the project's flatten order.  Y is laid out the
+ * same way: Y[t ldy + p ldq + I NLON + J], ldq >= NLAT NLON.  Output cell (I, J) covers the fine rows lat0 + I fy .. + fy - 1
+ * and the longitudes lon0 + J fx .. + fx - 1: whole cells only, as K22 has valid windows only -- the caller chooses NLAT and
+ * NLON with lat0 + NLAT fy <= nlat and lon0 + NLON fx <= nlon, and rows and longitudes outside the cells are not looked at
+ * (721 latitudes and fy = 4: one pole row is dropped).  w holds nlat device doubles, one weight per fine latitude row of
+ * the plane (cos of the latitude, an exact band area, or ones; the host forms it).  Per snapshot t, plane p, cell (I, J):
+ *     num = +0.0; den = +0.0; full = +0.0
+ *     for a = 0 .. fy - 1 ascending, i = lat0 + I fy + a:
+ *         r = +0.0; c = 0
+ *         for b = 0 .. fx - 1 ascending: x = X[t, p, i, lon0 + J fx + b];
+ *                                        if (!skipna || finite(x)) { r = r + fp64(x); c = c + 1; }
+ *         num = num + w[i] * r; den = den + w[i] * fp64(c); full = full + w[i] * fp64(fx);   (products rounded, then the sums)
+ *     Y = (den == 0 || den < min_frac * full) ? quiet NaN (0x7fc00000) : fp32(num / den)
+ * all in fp64, never an FMA, one rounding to fp32.  finite(x) is K20's test of the bit pattern: an exponent of all ones is
+ * not finite.  With skipna == 0, den == full, and a non-finite x reaches its own cell by IEEE arithmetic and nothing else.
+ * The launch geometry is not part of the result: a cell is formed by one lane; no atomics, no workspace, no allocation, no
+ * synchronisation: results are bit-wise reproducible.  So a constant field comes out constant bit for bit, 2^e X gives
+ * 2^e Y, a cell of zeros of either sign gives +0.0, and integer X with unit weights and fy fx a power of two gives the
+ * exact mean.
+ * Memory: only elements of X inside some cell are read -- no dropped trailing rows or longitudes, nothing before lat0 or
+ * lon0, no plane pad, nothing between (P - 1) ldp + nlat nlon and ldx -- and only w[lat0 .. lat0 + NLAT fy); only the
+ * logical P NLAT NLON x T elements of Y are written.  No alignment is asked for beyond that of the element types: the fx
+ * floats of a cell's fine row are read with 16-byte loads (fx = 4, 8; at fx = 2 a lane forms four neighbouring cells of a
+ * coarse row from two such loads and stores them with 16 bytes) where the addresses allow it, and element by element
+ * otherwise and for every other fx; a wave stores 64 (256) consecutive cells.  All give the same bits.
+ * A refused call (DMDX_E_INVALID: a null X, w or Y; a negative size; fy or fx outside 1 .. dmdx_coarsen_max_factor() (64);
+ * lat0 or lon0 negative, or cells that do not fit; ldp < nlat nlon or ldq < NLAT NLON; ldx < (P - 1) ldp + nlat nlon or
+ * ldy < (P - 1) ldq + NLAT NLON; any size or leading dimension >= 2^31; an extent >= 2^60 elements; min_frac outside [0, 1]
+ * or NaN; a pointer not aligned to its element; any overlap of the address ranges of X and Y: there is no in-place form)
+ * has written nothing and made no HIP call.  T, P, NLAT or NLON == 0 returns 0 after the checks without a launch. */
+int dmdx_coarsen_max_factor(void);
+int dmdx_coarsen_f32(const float* X, int64_t T, int64_t ldx, int64_t P, int64_t ldp, int64_t nlat, int64_t nlon,
+                     const double* w, int fy, int fx, int64_t lat0, int64_t lon0, int64_t NLAT, int64_t NLON, int skipna,
+                     double min_frac, float* Y, int64_t ldy, int64_t ldq, void* stream);
+
 /* ---- upper triangle of a symmetric fp64 matrix <-> packed row by row ---------------------
  * packed[i (2n - i + 1) / 2 + (j - i)] = A[i][j], j >= i: what the Gram all-reduce of the
  * row-sharded path moves (n (n + 1) / 2 doubles instead of n^2).  unpack writes both triangles. */
