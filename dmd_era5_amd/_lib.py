@@ -79,6 +79,14 @@ SIGNATURES = {
     "dmdx_crps_workspace_bytes": (_sz, [_i64, _i64, _i64, _i64]),
     "dmdx_crps_f32": (C.c_int, [_p, _i64, _i64, _i64, _p, _i64, _i64, _i64, _p, _p, _p, _i64, _p, _p, _i64, _p, _i64, _p,
                                 C.c_int, _p, _sz, _p]),
+    "dmdx_exceed_max_k": (C.c_int, []),
+    "dmdx_exceed_max_members": (C.c_int, []),
+    "dmdx_exceed_max_thresholds": (C.c_int, []),
+    "dmdx_exceed_prob_f32": (C.c_int, [_p, _i64, _i64, _i64, _p, _i64, _i64, _i64, _p, _p, _p, _i64, _i64, _i64, _p,
+                                       C.c_int, _p, _i64, _i64, _p]),
+    "dmdx_exceed_score_workspace_bytes": (_sz, [_i64, _i64, _i64, _i64, _i64]),
+    "dmdx_exceed_score_f32": (C.c_int, [_p, _i64, _i64, _i64, _p, _i64, _i64, _i64, _p, _p, _p, _i64, _i64, _i64, _p,
+                                        C.c_int, _p, _i64, _p, _p, _i64, _p, _i64, _p, C.c_int, _p, _sz, _p]),
     "dmdx_unpack_i16_f32": (C.c_int, [_p, _i64, _i64, _i64, _i64, _i64, _i64, C.c_int, _p, C.c_double, C.c_double,
                                       C.c_int, C.c_int, C.c_int, _p, _i64, _p, _p]),
     "dmdx_pack_max_k": (C.c_int, []),

@@ -169,6 +169,31 @@ class Climatology:
         Z = [torch.zeros((T, int(M.shape[1])), dtype=torch.float32, device=M.device) for M in self.mean]
         return self._apply(Z, times, None, True, False, "at")
 
+    # -- thresholds of an exceedance forecast (K24) ---------------------------------------------------------------
+    def slots(self, times) -> np.ndarray:
+        """The slot of every time as int32 labels 0 .. S - 1: the ``slot`` of ``forecast.exceed_blocks`` /
+        ``exceed_prob_blocks`` for thresholds from :meth:`thresholds`.  A time whose slot was fitted from no snapshot
+        is a ValueError."""
+        return self._labels(times, "slots").astype(np.int32)
+
+    def thresholds(self, z, anomaly: bool = True) -> list:
+        """Climatological thresholds for every slot and row: per block a (J, S, rows) fp32 tensor, ``z[j] * sd`` with
+        ``anomaly`` (for a model and an analysis the slot means were removed from, not divided by ``sd``) and
+        ``mean + z[j] * sd`` otherwise, each operation rounded to fp32 -- z = 1.2816 is the upper decile of a normal
+        climate.  A slot that was fitted from no snapshot has NaN thresholds (no event).  Without ``sd`` a
+        ValueError."""
+        if self.sd is None:
+            raise ValueError("Climatology.thresholds: the climatology holds no standard deviation (fit with with_std=True)")
+        zs = [float(v) for v in np.atleast_1d(np.asarray(z, dtype=np.float64))]
+        if not zs or not all(np.isfinite(zs)):
+            raise ValueError(f"Climatology.thresholds: z must hold at least one finite factor, got {z!r}")
+        res = []
+        for M, D in zip(self.mean, self.sd):
+            zt = torch.tensor(zs, dtype=torch.float32, device=D.device)[:, None, None]
+            th = zt * D[None]
+            res.append((th if anomaly else M[None] + th).contiguous())
+        return res
+
     # -- persistence ----------------------------------------------------------------------------------------------
     def to_dataset(self, coords=None) -> Dataset:
         """``clim_mean(slot, space)``, ``clim_std`` if there is one, ``clim_count(slot)`` and the attributes ``kind``,

@@ -202,22 +202,6 @@ __global__ __launch_bounds__(256, 1) void crps_kernel(
   }
 }
 
-// hist[r] (+)= sum over the workgroups' slots of histpart[slot][r], r = blockIdx.x: integers, any order
-__global__ __launch_bounds__(256) void reduce_hist_kernel(const long long* __restrict__ histpart, int64_t nslot, int nbin,
-                                                          long long* __restrict__ hist, int accumulate) {
-  __shared__ long long part[256];
-  const int r = blockIdx.x;
-  long long s = 0;
-  for (int64_t j = threadIdx.x; j < nslot; j += 256) s += histpart[j * nbin + r];
-  part[threadIdx.x] = s;
-  __syncthreads();
-  for (int half = 128; half >= 1; half >>= 1) {
-    if ((int)threadIdx.x < half) part[threadIdx.x] += part[threadIdx.x + half];
-    __syncthreads();
-  }
-  if (threadIdx.x == 0) hist[r] = accumulate ? hist[r] + part[0] : part[0];
-}
-
 // [score workspace of 2 quantities, both with row sums][histpart: row blocks x T splits x (B + 1) int64]; the score
 // part is a multiple of 8 bytes past its 16-byte boundary (colpart holds 2 floats per (row block, t))
 inline size_t hist_offset(int64_t m, int64_t T) { return score_ws_bytes(m, T, NQ, NQ); }

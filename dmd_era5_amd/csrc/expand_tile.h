@@ -240,6 +240,22 @@ __global__ __launch_bounds__(256) void reduce_rows_kernel(const double* __restri
   out[(int64_t)q * ldout + i] = s;
 }
 
+// Integer counts (K19, K24): hist[r] (+)= sum over the workgroups' slots of histpart[slot][r], r = blockIdx.x: integers, any order
+__global__ __launch_bounds__(256) void reduce_hist_kernel(const long long* __restrict__ histpart, int64_t nslot, int nbin,
+                                                          long long* __restrict__ hist, int accumulate) {
+  __shared__ long long part[256];
+  const int r = blockIdx.x;
+  long long s = 0;
+  for (int64_t j = threadIdx.x; j < nslot; j += 256) s += histpart[j * nbin + r];
+  part[threadIdx.x] = s;
+  __syncthreads();
+  for (int half = 128; half >= 1; half >>= 1) {
+    if ((int)threadIdx.x < half) part[threadIdx.x] += part[threadIdx.x + half];
+    __syncthreads();
+  }
+  if (threadIdx.x == 0) hist[r] = accumulate ? hist[r] + part[0] : part[0];
+}
+
 // ---------------------------------------------------------------- host
 // the T axis is split over blockIdx.y until the launch has ~2048 workgroups (8 per CU); a function of the
 // shapes only, so that the partial sums -- and with them the results -- do not depend on the device

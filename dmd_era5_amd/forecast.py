@@ -30,7 +30,10 @@ A trend and harmonic regression that was removed as well (K21, :mod:`trend`) tak
 and shares ``times=``: out after the climatology, back before it.
 The members of a bagged fit as an ensemble forecast -- the continuous ranked probability score, area-weighted per group,
 and the rank histogram -- are K19 (``HipKernels.crps``, csrc/crps.hip): :func:`member_coefficients`,
-:func:`crps_blocks` and ``DmdForecast.ensemble_crps``; no member field is stored there either.
+:func:`crps_blocks` and ``DmdForecast.ensemble_crps``; no member field is stored there either.  The same members as
+the probability that a field exceeds a threshold, and that probability scored -- Brier score, reliability diagram, ROC
+area -- are K24 (``HipKernels.exceed_prob`` / ``exceed_score``, csrc/exceed.hip): :func:`exceed_prob_blocks`,
+:func:`exceed_blocks`, ``DmdForecast.exceedance_fields`` and ``DmdForecast.ensemble_exceedance``.
 
 Layout as everywhere in the package (kernels.py): a column-major matrix is held as its row-major
 transpose -- U blocks are ``(k, rows)`` (``SvdResult.Ut``), coefficients ``Ct`` are ``(T, k)``,
@@ -38,7 +41,7 @@ fields and snapshots ``(T, rows)``.  A delay-embedded U block is ``(k, d * rows)
 columns ``[j * rows, (j + 1) * rows)`` (svd._assemble_rows).
 
 The drivers that sum a score over the grid -- :func:`score_blocks`, :func:`spread_score_blocks`, :func:`verify_blocks`,
-:func:`crps_blocks` -- are one loop, :func:`_grid_sums`: U resident, X consumed block by block, the launches of a block
+:func:`crps_blocks`, :func:`exceed_blocks` -- are one loop, :func:`_grid_sums`: U resident, X consumed block by block, the launches of a block
 from :func:`_group_pieces`, one ``allreduce_sum_`` per call; a driver states its accumulators, the kernel call on one
 row range and its score formulas.  :func:`project_blocks` keeps a loop of its own (it learns T and k from the first
 block and writes into the snapshot blocks).
@@ -58,8 +61,8 @@ from .svd import Comm, _kern, _pitched, embed_view, free_device_bytes, row_mask_
 
 __all__ = ["svd_coefficients", "dmd_coefficients", "ensemble_coefficients", "expand_blocks", "iter_fields",
            "score_blocks", "project_blocks", "spread_blocks", "spread_score_blocks", "area_weights", "verify_blocks",
-           "member_coefficients", "crps_blocks", "pack_blocks", "pack_field_blocks", "range_blocks",
-           "range_field_blocks", "mask_weights", "DmdForecast"]
+           "member_coefficients", "crps_blocks", "exceed_blocks", "exceed_prob_blocks", "pack_blocks",
+           "pack_field_blocks", "range_blocks", "range_field_blocks", "mask_weights", "DmdForecast"]
 
 
 # ---------------------------------------------------------------------------
@@ -234,6 +237,66 @@ def _crps(kern, Ut, Cm, Xt, mean, std, weight, out, hist, want_rows):
     return cols, (Q.sum(dim=1) if want_rows else None), counts
 
 
+def _exceed_elements(Ut, Cm, thr, slot, above, mean, std):
+    """The torch fp64 form of K24's elements: (c (J, T, rows) int64, the thresholds (J, T, rows) fp64, finite (T, rows))."""
+    P = Cm.to(torch.float64) @ Ut.to(torch.float64)                 # (B, T, rows)
+    if std is not None:
+        P = P * std.to(torch.float64)
+    if mean is not None:
+        P = P + mean.to(torch.float64)
+    th = (thr if thr.dim() == 3 else thr.unsqueeze(1)).to(torch.float64)
+    T = int(Cm.shape[1])
+    sl = torch.zeros(T, dtype=torch.long, device=th.device) if slot is None else slot.to(torch.long)
+    th = th[:, sl, :]                                               # (J, T, rows)
+    ev = P[None] > th[:, None] if above else P[None] < th[:, None]
+    return ev.sum(dim=1), th, torch.isfinite(P).all(dim=0)
+
+
+def _exceed_prob(kern, Ut, Cm, thr, slot, above, mean, std, out=None):
+    """K24's probability planes of one row range: (J, T, rows) fp32."""
+    f = getattr(kern, "exceed_prob", None)
+    if f is not None:
+        return f(Ut, Cm, thr, slot, above, mean, std, out=out)
+    c, _, fin = _exceed_elements(Ut, Cm, thr, slot, above, mean, std)
+    p = (c.to(torch.float64) / int(Cm.shape[0])).to(torch.float32)
+    p = torch.where(fin[None], p, torch.full_like(p, float("nan")))
+    if out is None:
+        return p
+    out.copy_(p)
+    return out
+
+
+def _exceed(kern, Ut, Cm, Xt, thr, slot, above, mean, std, weight, out, counts, want_rows):
+    """K24's score of one row range: (cols (J, 4, T) fp64, rows (J, 4, m) fp64 | None, counts (J, 2, B + 1) int64);
+    ``out`` / ``counts`` are added to."""
+    f = getattr(kern, "exceed_score", None)
+    if f is not None:
+        return f(Ut, Cm, Xt, thr, slot, above, mean, std, weight, out=out, counts=counts, want_rows=want_rows)
+    B = int(Cm.shape[0])
+    c, th, fin = _exceed_elements(Ut, Cm, thr, slot, above, mean, std)
+    X = Xt.to(torch.float64)
+    fin = fin & torch.isfinite(X)
+    o = (X[None] > th) if above else (X[None] < th)                 # (J, T, rows)
+    of = o.to(torch.float64)
+    p = (c.to(torch.float64) / B).to(torch.float32).to(torch.float64)
+    Q = torch.stack([(p - of) ** 2, of, p, p * p], dim=1)           # (J, 4, T, rows)
+    Q = torch.where(fin[None, None], Q, torch.full_like(Q, float("nan")))
+    if weight is None:
+        cols, sel = Q.sum(dim=3), fin
+    else:                                                           # weight 0 leaves the row out: no 0 * NaN
+        keep = weight != 0
+        cols = (Q[:, :, :, keep] * weight[keep].to(torch.float64)).sum(dim=3)
+        sel = fin & keep
+    J = int(c.shape[0])
+    cnt = torch.stack([torch.bincount((o[j].to(torch.long) * (B + 1) + c[j])[sel].reshape(-1), minlength=2 * (B + 1))
+                       for j in range(J)]).reshape(J, 2, B + 1).to(torch.int64)
+    if out is not None:
+        out += cols
+        counts += cnt
+        cols, cnt = out, counts
+    return cols, (Q.sum(dim=2) if want_rows else None), cnt
+
+
 def _merge_range(P: torch.Tensor, out):
     """(range (2,) fp32, count (1,) int64) of the fp32 field P, merged into the pair ``out`` of an earlier call."""
     fin = torch.isfinite(P)
@@ -353,10 +416,15 @@ def _pitched_dev(kern, Dev: torch.Tensor) -> torch.Tensor:
 
 
 def _vec(v, b, reps, device):
-    """Block b of a list of per-row vectors (or None) as fp32 on ``device``, repeated for every delay."""
+    """Block b of a list of per-row vectors (or None) as fp32 on ``device``, repeated for every delay.  An entry with
+    three dimensions is a table (..., rows) per row -- K24's thresholds -- and keeps its shape: the rows are its last
+    axis."""
     if v is None:
         return None
-    x = torch.as_tensor(v[b]).to(device=device, dtype=torch.float32).reshape(-1)
+    x = torch.as_tensor(v[b]).to(device=device, dtype=torch.float32)
+    if x.dim() == 3:
+        return (x.repeat(1, 1, reps) if reps > 1 else x).contiguous()
+    x = x.reshape(-1)
     return (x.repeat(reps) if reps > 1 else x).contiguous()
 
 
@@ -444,8 +512,9 @@ def _block_vecs(vecs: dict, b, reps, mb, device, who) -> dict:
     out = {}
     for name, v in vecs.items():
         out[name] = x = _vec(v, b, reps, device)
-        if x is not None and x.numel() != reps * mb:
-            raise ValueError(f"{who}: {name}[{b}] has {x.numel() // reps} entries, the block {mb} rows")
+        if x is not None and (x.shape[-1] if x.dim() == 3 else x.numel()) != reps * mb:
+            raise ValueError(f"{who}: {name}[{b}] has {(x.shape[-1] if x.dim() == 3 else x.numel()) // reps} entries, the "
+                             f"block {mb} rows")
     return out
 
 
@@ -457,7 +526,8 @@ def _grid_sums(who, tag, comm, Ublocks, Xblocks, T, delay, device, vecs: dict, z
 
     ``Ublocks`` is resident (a list is made of it); ``Xblocks`` -- None for a score without snapshots -- is consumed
     once, in order, one block alive at a time, and its embedded view must be (T, d * rows).  ``vecs``: name ->
-    list of per-row vectors of the physical rows, or None (``means``, ``stds``, ...).  A ``weights`` entry makes the
+    list of per-row vectors of the physical rows (or of three-dimensional tables with the rows last), or None
+    (``means``, ``stds``, ...).  A ``weights`` entry makes the
     score a weighted one: it is validated (:func:`_check_weights`), and the sum of the weights W -- per run on the
     host in fp64, times the delay -- and the rows with weight 0 travel with the row count.
     ``zeros(G, device)`` -> the tuple of zero accumulators (made at the first block, or on ``device`` by a rank
@@ -497,7 +567,7 @@ def _grid_sums(who, tag, comm, Ublocks, Xblocks, T, delay, device, vecs: dict, z
         R = None
         for s, e, g in pieces[b]:
             r = launch(acc, U[:, s:e], None if E is None else E[:, s:e],
-                       {name: None if x is None else x[s:e] for name, x in v.items()}, g)
+                       {name: None if x is None else x[..., s:e] for name, x in v.items()}, g)
             if want_rows:
                 if R is None:
                     R = r.new_zeros(r.shape[:-1] + (delay * mb,))
@@ -726,6 +796,150 @@ def crps_blocks(Ublocks, Cm: torch.Tensor, Xblocks, means=None, stds=None, weigh
     if want_rows:
         div = npairs if fair else float(B * B)
         res["row_crps"] = [R[0] / (B * T) - R[1] / (div * T) for R in row_sums]
+    return res
+
+
+def _threshold_tables(thresholds, nblocks, who):
+    """The per-block threshold tables as (J, S, rows) fp32 (a (J, rows) table has one slot) -> (tables, J, S).  A
+    rank without blocks has no table to learn J from and passes the number J itself."""
+    if isinstance(thresholds, int):
+        if nblocks or thresholds < 1:
+            raise ValueError(f"{who}: thresholds = {thresholds}: the number J >= 1 stands for the tables only where there "
+                             "are no blocks")
+        return [], int(thresholds), 1
+    tabs = [torch.as_tensor(t).to(torch.float32) for t in thresholds]
+    tabs = [t.unsqueeze(1) if t.dim() == 2 else t for t in tabs]
+    if len(tabs) != nblocks:
+        raise ValueError(f"{who}: {len(tabs)} threshold tables for {nblocks} blocks")
+    if any(t.dim() != 3 or t.shape[:2] != tabs[0].shape[:2] or t.shape[0] < 1 or t.shape[1] < 1 for t in tabs):
+        raise ValueError(f"{who}: every threshold table must be (J, S, rows) or (J, rows) with the same J >= 1 and S >= 1, "
+                         f"got {[tuple(t.shape) for t in tabs]}")
+    if not tabs:
+        raise ValueError(f"{who}: no threshold table: a rank without blocks passes the number of thresholds J")
+    return tabs, int(tabs[0].shape[0]), int(tabs[0].shape[1])
+
+
+def _slot_labels(slot, S, T, device, who):
+    """The slot of every snapshot as device int32, or None for one slot; labels outside 0 .. S - 1 are a ValueError."""
+    if slot is None:
+        if S != 1:
+            raise ValueError(f"{who}: the thresholds have {S} slots, so slot must name one per snapshot")
+        return None
+    sl = torch.as_tensor(slot).reshape(-1).cpu()
+    if sl.dtype.is_floating_point or sl.numel() != T or int(sl.min()) < 0 or int(sl.max()) >= S:
+        raise ValueError(f"{who}: slot must hold {T} integer labels in 0 .. {S - 1}")
+    return sl.to(device=device, dtype=torch.int32).contiguous()
+
+
+def exceed_prob_blocks(Ublocks, Cm: torch.Tensor, thresholds, slot=None, above: bool = True, means=None, stds=None,
+                       delay_block: int | None = None, out=None, delay: int = 1, kern=None) -> list[torch.Tensor]:
+    """The exceedance probability of every row block: a list of (J, T, rows) fp32 tensors, the share of the B member
+    fields ``mean + std * (U Cm[b])`` above (``above=False``: below) threshold j -- per grid point and time (K24; no
+    member field is stored).  NaN where a member is not finite.  ``thresholds``: per block a (J, S, rows) or (J, rows)
+    table over the PHYSICAL rows (``Climatology.thresholds``), ``slot``: the slot 0 .. S - 1 of every snapshot of
+    ``Cm`` (None with one slot).  The comparison is strict: a member that equals the threshold is no event.
+    ``means``, ``stds``, ``delay``, ``delay_block`` as in :func:`expand_blocks`; ``out``: a list of contiguous
+    (J, T, rows) fp32 tensors to write into.  ``[P[j] for P in result]`` is an ``Xblocks`` of
+    :func:`pack_field_blocks`."""
+    kern = _kern(kern)
+    Ublocks = list(Ublocks)
+    tabs, J, S = _threshold_tables(thresholds, len(Ublocks), "exceed_prob_blocks")
+    Cp = _pitched_dev(kern, Cm)
+    sl = _slot_labels(slot, S, int(Cm.shape[1]), Cm.device, "exceed_prob_blocks")
+    res = []
+    for b, U in enumerate(Ublocks):
+        Ub, reps = _block_rows(U, delay, delay_block)
+        th = tabs[b].to(Ub.device)
+        th = (th.repeat(1, 1, reps) if reps > 1 else th).contiguous()
+        if th.shape[2] != Ub.shape[1]:
+            raise ValueError(f"exceed_prob_blocks: thresholds[{b}] has {int(tabs[b].shape[2])} rows, the block "
+                             f"{int(Ub.shape[1]) // reps}")
+        res.append(_exceed_prob(kern, Ub, Cp, th, sl, above, _vec(means, b, reps, Ub.device),
+                                _vec(stds, b, reps, Ub.device), out=None if out is None else out[b]))
+    return res
+
+
+def exceed_blocks(Ublocks, Cm: torch.Tensor, Xblocks, thresholds, slot=None, above: bool = True, means=None, stds=None,
+                  weights=None, groups=None, delay: int = 1, comm: Comm | None = None, want_rows: bool = False, kern=None,
+                  n_groups: int | None = None) -> dict:
+    """The exceedance probability p = (members beyond the threshold) / B of the B member forecasts
+    ``mean + std * (U c_b)`` scored against the snapshots ``Xblocks`` (the analysis) on the grid, without storing a
+    member field (K24): Brier score, reliability diagram and ROC area, per group of rows and threshold.
+
+    ``Cm``: (B, T, k) fp32, :func:`member_coefficients`.  ``thresholds``: per block a (J, S, rows) or (J, rows) table
+    over the PHYSICAL rows (``Climatology.thresholds``), repeated for every delay like ``means`` (a rank without
+    blocks passes the number J instead: the collective needs it); ``slot``: the slot 0 .. S - 1 of every (embedded)
+    snapshot, None with one slot; ``above``: the event is value > threshold, otherwise value < threshold -- strict, a
+    tie is no event, a NaN threshold gives none.  ``Xblocks``, ``means``, ``stds``, ``weights``, ``groups``,
+    ``delay``, ``n_groups`` exactly as in :func:`verify_blocks`.
+
+    With o the outcome (1 where the analysis is in the event), S0 .. S3 = sum w ((p - o)^2, o, p, p^2) over the rows
+    of a group and W = the sum of its weights, returns per group, threshold and snapshot (G, J, T)
+      ``brier`` = S0 / W, ``brier_fair`` = S0 / W - (S2 - S3) / ((B - 1) W) (Ferro's correction for the ensemble
+      size: unbiased for the score of the underlying probability; NaN for B = 1), ``base_rate`` = S1 / W,
+      ``forecast_rate`` = S2 / W, ``brier_skill`` = 1 - brier / (base_rate (1 - base_rate)),
+    the same over all snapshots as ``*_total`` (G, J), and from the counts N[o, c] of selected, finite elements with
+    outcome o and c members in the event (``counts`` (G, J, 2, B + 1) int64, unweighted):
+      ``bin_counts`` = N_c = N[0, c] + N[1, c] and ``reliability`` = N[1, c] / N_c (G, J, B + 1): the observed
+      frequency where c / B was forecast (NaN for an empty bin),
+      ``reliability_term`` = sum_c N_c (c / B - O_c / N_c)^2 / N, ``resolution_term`` = sum_c N_c (O_c / N_c - O / N)^2
+      / N and ``uncertainty`` = (O / N) (1 - O / N) (G, J): Murphy's decomposition, Brier = reliability - resolution +
+      uncertainty for unit weights,
+      ``roc_area`` (G, J): the area under the hit rate against the false alarm rate of the B + 1 decisions "at least
+      c members", joined by trapezoids from (0, 0) to (1, 1) (NaN unless both outcomes occur),
+    the raw ``sums`` (G, J, 4, T), ``weight`` (G,), ``rows`` and ``masked_rows`` (G,) as :func:`verify_blocks`, and
+    with ``want_rows`` the list ``row_brier`` of (J, rows) tensors of the local blocks: the Brier score over time of
+    every grid point (unweighted).
+
+    Row shards: ONE ``comm.allreduce_sum_`` of the stacked ``[sums, counts, W, rows, masked]`` per call.  A rank
+    without blocks still takes part.  The counts travel as fp64: exact below 2^53 per bin."""
+    kern = _kern(kern)
+    if Cm.dim() != 3:
+        raise ValueError(f"exceed_blocks: Cm must be (B, T, k), got {tuple(Cm.shape)}")
+    B, T = int(Cm.shape[0]), int(Cm.shape[1])
+    Ublocks = list(Ublocks)
+    tabs, J, S = _threshold_tables(thresholds, len(Ublocks), "exceed_blocks")
+    sl = _slot_labels(slot, S, T, Cm.device, "exceed_blocks") if Ublocks else None
+    Cp = _pitched_dev(kern, Cm)
+    vecs = {"means": means, "stds": stds, "weights": weights, "thresholds": tabs}
+
+    def launch(acc, U, E, v, g):        # (the row range of the table is copied once: the kernel takes a dense one)
+        return _exceed(kern, U, Cp, E, v["thresholds"].contiguous(), sl, above, v["means"], v["stds"], v["weights"],
+                       acc[0][g], acc[1][g], want_rows)[1]
+
+    (sums, counts), (W, rows, masked), row_sums = _grid_sums(
+        "exceed_blocks", "exceed_allreduce", comm, Ublocks, Xblocks, T, delay, Cm.device, vecs,
+        lambda G, dev: (torch.zeros((G, J, 4, T), dtype=torch.float64, device=dev),
+                        torch.zeros((G, J, 2, B + 1), dtype=torch.int64, device=dev)),
+        launch, groups, n_groups, want_rows)
+    counts = counts.round().to(torch.int64)          # (the counts travelled as fp64)
+
+    def scores(Sm, Wn):
+        S0, S1, S2, S3 = (Sm[:, :, q] for q in range(4))
+        brier, base = S0 / Wn, S1 / Wn
+        fair = brier - (S2 - S3) / ((B - 1) * Wn) if B > 1 else torch.full_like(brier, float("nan"))
+        return {"brier": brier, "brier_fair": fair, "base_rate": base, "forecast_rate": S2 / Wn,
+                "brier_skill": 1.0 - brier / (base * (1.0 - base))}
+
+    res = scores(sums, W[:, None, None])
+    res.update({f"{key}_total": v for key, v in scores(sums.sum(dim=3), (W * T)[:, None]).items()})
+    N = counts.to(torch.float64)
+    Nc, Oc = N.sum(dim=2), N[:, :, 1]
+    Ntot, freq = Nc.sum(dim=2), Oc / Nc                                  # (an empty bin: 0 / 0 = NaN)
+    obar = Oc.sum(dim=2) / Ntot
+    f0 = torch.where(Nc > 0, freq, torch.zeros_like(freq))
+    pc = torch.arange(B + 1, dtype=torch.float64, device=N.device) / B
+    z = torch.zeros(N.shape[:2] + (1,), dtype=torch.float64, device=N.device)
+    far = torch.cat([z, torch.cumsum(N[:, :, 0].flip(2), dim=2) / N[:, :, 0].sum(dim=2, keepdim=True)], dim=2)
+    hit = torch.cat([z, torch.cumsum(N[:, :, 1].flip(2), dim=2) / N[:, :, 1].sum(dim=2, keepdim=True)], dim=2)
+    res.update(reliability=freq, bin_counts=Nc.to(torch.int64),
+               reliability_term=(Nc * (pc - f0) ** 2).sum(dim=2) / Ntot,
+               resolution_term=(Nc * (f0 - obar[:, :, None]) ** 2).sum(dim=2) / Ntot,
+               uncertainty=obar * (1.0 - obar),
+               roc_area=(0.5 * (hit[:, :, 1:] + hit[:, :, :-1]) * (far[:, :, 1:] - far[:, :, :-1])).sum(dim=2),
+               sums=sums, counts=counts, weight=W, rows=rows.to(torch.int64), masked_rows=masked.to(torch.int64))
+    if want_rows:
+        res["row_brier"] = [R[:, 0] / T for R in row_sums]
     return res
 
 
@@ -1191,6 +1405,32 @@ class DmdForecast:
                           fair, self.kern, n_groups)
         res["imag_ratio"] = imag
         return res
+
+    def ensemble_exceedance(self, Xblocks, t, thresholds, slot=None, above: bool = True, weights=None, groups=None,
+                            comm: Comm | None = None, want_rows: bool = False, n_groups: int | None = None) -> dict:
+        """:func:`exceed_blocks` of the trials of a bagged fit, as an ensemble forecast, against the snapshots
+        ``Xblocks`` at the times ``t`` (with a delay d the blocks hold len(t) + d - 1 snapshots): the Brier score of
+        the exceedance probability per group and threshold, the reliability diagram and the ROC area, one launch per
+        block and group run, one collective.  ``thresholds`` / ``slot``: per block the (J, S, rows) table and the slot
+        of every time (``Climatology.thresholds`` / ``Climatology.slots``); a model fitted on anomalies takes
+        thresholds of the anomalies (``anomaly=True``) and the anomalised analysis.  ``imag_ratio`` is added to the
+        result."""
+        Cm, imag = self.member_coefficients(t)
+        res = exceed_blocks(self.Ublocks, Cm, Xblocks, thresholds, slot, above, self.means, self.stds, weights, groups,
+                            self.delay, comm, want_rows, self.kern, n_groups)
+        res["imag_ratio"] = imag
+        return res
+
+    def exceedance_fields(self, t, thresholds, slot=None, above: bool = True, delay_block: int | None = 0,
+                          out=None) -> list[torch.Tensor]:
+        """:func:`exceed_prob_blocks` of the trials of a bagged fit at the times ``t``: per block the (J, T, rows)
+        fp32 probability that the forecast field is beyond threshold j, the physical rows by default
+        (``delay_block`` as in :meth:`fields`)."""
+        Cm, _ = self.member_coefficients(t)
+        if self.delay == 1:
+            delay_block = None
+        return exceed_prob_blocks(self.Ublocks, Cm, thresholds, slot, above, self.means, self.stds, delay_block, out,
+                                  self.delay, self.kern)
 
     def reconstruct_svd(self, n_components: int | None = None, cols=None, delay_block: int | None = 0,
                         out=None) -> list[torch.Tensor]:

@@ -480,6 +480,99 @@ class HipKernels:
         _lib.check(rc, "dmdx_crps_f32")
         return cols, rows, counts
 
+    # -- K24 ----------------------------------------------------------------
+    @property
+    def exceed_max_k(self) -> int:
+        return int(self._lib.dmdx_exceed_max_k())
+
+    @property
+    def exceed_max_members(self) -> int:
+        return int(self._lib.dmdx_exceed_max_members())
+
+    @property
+    def exceed_max_thresholds(self) -> int:
+        return int(self._lib.dmdx_exceed_max_thresholds())
+
+    def _exceed_args(self, Ut, Cm, thr, slot, mean, std, who):
+        """-> (m, k, ldu, T, B, Dt, ldc, thr3, J, S): the members as :meth:`crps` takes them, ``thr`` as the
+        contiguous (J, S, m) table, ``slot`` checked against it (a device read: the labels must lie in 0 .. S - 1)."""
+        m, k, ldu, T, B, Dt, ldc = self._spread_args(Ut, Cm, std, who)
+        if B > self.exceed_max_members:
+            raise _lib.DmdxError(f"{who}: {B} members, at most {self.exceed_max_members}")
+        _check_vec(mean, m, Ut.device, who, "mean")
+        if (not isinstance(thr, torch.Tensor) or thr.dtype != torch.float32 or thr.dim() not in (2, 3)
+                or thr.device != Ut.device or thr.shape[-1] != m or not thr.is_contiguous()):
+            raise _lib.DmdxError(f"{who}: thr must be a contiguous (J, S, {m}) or (J, {m}) fp32 tensor on {Ut.device}")
+        thr3 = thr if thr.dim() == 3 else thr.unsqueeze(1)
+        J, S = int(thr3.shape[0]), int(thr3.shape[1])
+        if not 1 <= J <= self.exceed_max_thresholds or S < 1:
+            raise _lib.DmdxError(f"{who}: {J} thresholds in {S} slots; 1 .. {self.exceed_max_thresholds} thresholds and "
+                                 f"at least one slot asked for")
+        if slot is None:
+            if S != 1:
+                raise _lib.DmdxError(f"{who}: thr has {S} slots, so slot must name one per snapshot")
+        else:
+            _check_ivec(slot, Ut.device, who, "slot", T)
+            lo, hi = int(slot.min()), int(slot.max())
+            if lo < 0 or hi >= S:
+                raise _lib.DmdxError(f"{who}: slot labels {lo} .. {hi} outside 0 .. {S - 1}")
+        return m, k, ldu, T, B, Dt, ldc, thr3, J, S
+
+    def exceed_prob(self, Ut: torch.Tensor, Cm: torch.Tensor, thr: torch.Tensor, slot: torch.Tensor | None = None,
+                    above: bool = True, mean: torch.Tensor | None = None, std: torch.Tensor | None = None,
+                    out: torch.Tensor | None = None) -> torch.Tensor:
+        """The share of the B member fields x_b = mean + std * (U c_b) beyond a threshold, no member field stored.
+        Ut: (k, m), Cm: (B, T, k) fp32 (as :meth:`crps`), thr: (J, S, m) or (J, m) fp32, threshold j of every row for
+        slot s, J <= ``exceed_max_thresholds``; slot: (T,) device int32 labels in 0 .. S - 1, or None (S = 1);
+        ``above``: the event is x > thr, otherwise x < thr (strict: a tie is no event, a NaN threshold gives none)
+        -> P (J, T, m) fp32: the fp32 nearest to c / B with c the number of members in the event, NaN where a member
+        is not finite.
+
+        ``out``: a contiguous (J, T, m) fp32 tensor to write into."""
+        m, k, ldu, T, B, Dt, ldc, thr3, J, S = self._exceed_args(Ut, Cm, thr, slot, mean, std, "exceed_prob")
+        if out is not None and (out.shape != (J, T, m) or out.dtype != torch.float32 or not out.is_contiguous()
+                                or out.device != Ut.device):
+            raise _lib.DmdxError(f"exceed_prob: out must be a contiguous ({J}, {T}, {m}) fp32 tensor on {Ut.device}")
+        P = torch.empty((J, T, m), dtype=torch.float32, device=Ut.device) if out is None else out
+        rc = self._timed("exceed_prob", (m, k, T, B, J), lambda: self._lib.dmdx_exceed_prob_f32(
+            _ptr(Ut), m, k, ldu, _ptr(Dt), ldc, T, B, _ptr(mean), _ptr(std), _ptr(thr3), m, J, S, _ptr(slot),
+            int(bool(above)), _ptr(P), m, T * m, self._stream()
+        ))
+        _lib.check(rc, "dmdx_exceed_prob_f32")
+        return P
+
+    def exceed_score(self, Ut: torch.Tensor, Cm: torch.Tensor, Xt: torch.Tensor, thr: torch.Tensor,
+                     slot: torch.Tensor | None = None, above: bool = True, mean: torch.Tensor | None = None,
+                     std: torch.Tensor | None = None, weight: torch.Tensor | None = None,
+                     out: torch.Tensor | None = None, counts: torch.Tensor | None = None, want_rows: bool = False):
+        """The sums behind the Brier score and the counts behind the reliability diagram and the ROC curve of the
+        exceedance probability p of :meth:`exceed_prob` against X, nothing stored.  Operands as :meth:`exceed_prob`,
+        Xt: (T, m) fp32 (the delay view included), weight: (m,) fp32 or None (1).  With o = 1 where X is in the event
+        and 0 otherwise -> (cols, rows, counts): ``cols`` a (J, 4, T) fp64 tensor of sum_i w ((p - o)^2, o, p, p^2)
+        over the rows with w != 0 (a row with weight 0 is left out whatever it holds); ``rows`` the (J, 4, m) fp64
+        sums of the same quantities over t, unweighted, or None; ``counts`` the (J, 2, B + 1) int64 numbers of
+        selected, finite elements with outcome o and c members in the event.  An element with a non-finite member
+        or X makes its sums NaN and enters no count.
+
+        ``out`` / ``counts``: a contiguous (J, 4, T) fp64 and a contiguous (J, 2, B + 1) int64 tensor the sums and
+        the counts are ADDED to (row blocks, groups of rows); both or neither."""
+        m, k, ldu, T, B, Dt, ldc, thr3, J, S = self._exceed_args(Ut, Cm, thr, slot, mean, std, "exceed_score")
+        ldx = _check_snapshots(Xt, m, T, Ut.device, "exceed_score")
+        _check_vec(weight, m, Ut.device, "exceed_score", "weight")
+        if (out is None) != (counts is None):
+            raise _lib.DmdxError("exceed_score: out and counts are accumulated into together: pass both or neither")
+        cols = _accumulator(out, (J, 4, T), torch.float64, Ut.device, "exceed_score")
+        cnt = _accumulator(counts, (J, 2, B + 1), torch.int64, Ut.device, "exceed_score", "counts")
+        rows = torch.empty((J, 4, m), dtype=torch.float64, device=Ut.device) if want_rows else None
+        ws = self._workspace(Ut.device, self._lib.dmdx_exceed_score_workspace_bytes(m, k, T, B, J))
+        rc = self._timed("exceed_score", (m, k, T, B, J), lambda: self._lib.dmdx_exceed_score_f32(
+            _ptr(Ut), m, k, ldu, _ptr(Dt), ldc, T, B, _ptr(mean), _ptr(std), _ptr(thr3), m, J, S, _ptr(slot),
+            int(bool(above)), _ptr(Xt), ldx, _ptr(weight), _ptr(cols), T, _ptr(rows), m, _ptr(cnt),
+            int(out is not None), _ptr(ws), ws.numel(), self._stream()
+        ))
+        _lib.check(rc, "dmdx_exceed_score_f32")
+        return cols, rows, cnt
+
     # -- K13 ----------------------------------------------------------------
     @property
     def project_max_k(self) -> int:

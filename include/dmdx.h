@@ -69,7 +69,10 @@
  *     dimension must be < 2^31 (DMDX_E_INVALID beyond, before anything is written);
  *   - K19 (dmdx_crps_f32): U, C (k x (B T)), mu, sigma, X and w are only read, inside their logical elements; every
  *     logical element of row and -- with accumulate == 0 -- of col and hist is written, nothing else; addressing
- *     and alignment as K15.
+ *     and alignment as K15;
+ *   - K24 (dmdx_exceed_prob_f32, dmdx_exceed_score_f32): as K19, with thr (m x (J S)) and slot (T) only read, inside
+ *     their logical elements and, for thr, only in the columns slot names; every logical element of the J planes of
+ *     P, of row and -- with accumulate == 0 -- of col and cnt is written, nothing else.
  *
  * Value contract (tests/test_gpu_value_domain.py holds every fp32 entry point to it)
  *   - NaN / Inf propagate like IEEE arithmetic on the logical operands, nothing more and nothing less:
@@ -494,6 +497,78 @@ int dmdx_crps_f32(const float* U, int64_t m, int64_t k, int64_t ldu, const float
                   const float* mu, const float* sigma, const float* X, int64_t ldx, const float* w,
                   double* col, int64_t ldcol, double* row, int64_t ldrow, int64_t* hist, int accumulate,
                   void* workspace, size_t workspace_bytes, void* stream);
+
+/* ---- K24: exceedance probability and Brier sums of B member fields on the grid ---------------------------------
+ * What an ensemble forecast is consumed as besides its mean and spread: the probability that a field exceeds (or
+ * falls below) a threshold -- the share of the members that do -- and what that probability is scored with: the
+ * Brier score, the reliability diagram and the ROC curve.  No member field is stored.  The shared operands are
+ * K19's: U (m x k, ldu), C (k x (B T), ldc; column b T + t holds the coefficients of member b at snapshot t), mu /
+ * sigma (m floats each, nullable: 0 / 1).  1 <= k <= dmdx_exceed_max_k() (256), 1 <= B <= dmdx_exceed_max_members()
+ * = DMDX_EXCEED_MAX_B (256).  New operands:
+ *   thr    m x (J S) floats, ldthr >= m: column j S + s holds threshold j of every row for slot s (a slot is a class
+ *          of the calendar, K18's); 1 <= J <= dmdx_exceed_max_thresholds() = DMDX_EXCEED_MAX_THR (4), S >= 1
+ *   slot   T int32, nullable (every snapshot in slot 0): the slot of snapshot t.  As in dmdx_clim_apply_f32 a value
+ *          outside 0 .. S - 1 means "no slot": nothing of thr is read for that snapshot and its thresholds are NaN
+ *          (no event); the host refuses such values before the call
+ *   above  != 0: the event is value > thr;  0: the event is value < thr.  A strict IEEE comparison: a tie is no
+ *          event, a NaN threshold gives no event.
+ * Per element (i, t) and threshold j, fp32, no fused operation:
+ *   x_b = sigma * acc_b + mu         K12's chain over k for the columns of member b and K12's two-step epilogue:
+ *                                    member b's field is bit for bit what dmdx_expand_f32 gives for C_b
+ *   c   = #{ b : x_b <> thr }        an integer in 0 .. B; <> is the comparison `above` selects
+ *   p   = the fp32 nearest to c / B  (for c <= B <= 256: fp32(fp64(c) / fp64(B)))
+ * The element is FINITE iff all B members are finite; the score wants a finite y = X[i, t] as well.  All J
+ * thresholds are counted in one pass of B chains per element: the cost does not grow with J but for the epilogue.
+ *
+ * dmdx_exceed_prob_f32 writes J planes: P[j * pstride + t * ldp + i] = p, or NaN where the element is not finite
+ * (ldp >= m; the planes must not overlap: pstride >= (T - 1) ldp + m unless J == 1).  Every logical element of the J
+ * planes is written and nothing else; no X, no workspace, no reduce kernel.
+ *
+ * dmdx_exceed_score_f32 adds X (m x T, ldx; rows > ldx allowed, the zero-copy delay view) and w (m floats,
+ * nullable: 1).  Per element and threshold:   o = (y <> thr) ? 1 : 0     d = fl(p - o)   and the DMDX_EXCEED_NQ = 4
+ * quantities   0: fl(d d)   1: o   2: p   3: fl(p p);   a non-finite element makes all four NaN for every j.
+ *   col[(4 j + q) * ldcol + t] (+)= sum over the rows i with w[i] != 0 of fl(w[i] * quantity_q[i, t])   ldcol >= T
+ *   row[(4 j + q) * ldrow + i]  =  sum_t quantity_q[i, t]     nullable, ldrow >= m, unweighted, always overwritten
+ *   cnt[(2 j + o) * (B + 1) + c] (+)= number of elements (i, t) with w[i] != 0 that are finite, have outcome o and
+ *                                  count c;  2 J (B + 1) int64, nullable
+ * With w == NULL there is no multiply.  The host forms the scores: Brier = col0 / W, its fair (ensemble-size
+ * corrected) form col0 / W - (col2 - col3) / ((B - 1) W), the base rate col1 / W, the forecast rate col2 / W, W = sum
+ * of the weights; reliability O_c / N_c and the ROC curve come from cnt.
+ * A row with w[i] == 0 is SELECTED out of col and cnt, whatever it holds; its `row` sums are the plain sums.  With
+ * every w == 0 col is +0.0 and cnt is 0.  accumulate != 0 adds to col and cnt (row blocks; a group of rows is a
+ * pointer offset); otherwise every logical element of col and cnt is written and none read.
+ * Sums as K16's / K19's: fp32 over at most DMDX_EXCEED_FP32_ROWS rows (columns: the rows of one workgroup; rows: 16
+ * snapshots), fp64 beyond, through per-workgroup partial slots in the workspace and reduce kernels.  No
+ * floating-point atomics: the order of every fp sum depends on (m, T, J) only, two calls give the same bits.  The
+ * counts are integers: a workgroup counts a tile in 32-bit LDS counters (integer atomics; a tile has 128 x 32 = 4096
+ * elements, and the counters are emptied into 64-bit registers after every tile, so no width overflows for any T),
+ * writes its 64-bit counts to its own slot of the workspace, and a reduce kernel adds the slots.
+ * Values: every quantity lies in [0, 1], so only the sums round.  A non-finite X[i, t] with w[i] != 0 makes column t
+ * of all 4 J sums NaN and row i of `row`; that element enters no bin.  A non-finite U[i, j], mu[i] or sigma[i] does
+ * the same to row i and, if w[i] != 0, to every column; a non-finite C[j, b T + t] to column t and every row.
+ * Everything else keeps its bits; (2^e U, 2^-e C) changes no bit.  A NaN threshold gives c = 0 and o = 0, finite.
+ * Memory as for K19: only logical elements are read or written, the workspace is exactly
+ * dmdx_exceed_score_workspace_bytes(m, k, T, B, J) and needs no initialisation, no alignment is required.  m, T, B T,
+ * J S, S and the leading dimensions must be < 2^31.  A refused call (DMDX_E_INVALID: a null U, C, thr, P (prob), X or
+ * col (score), k outside 1 .. 256, B outside 1 .. DMDX_EXCEED_MAX_B, J outside 1 .. DMDX_EXCEED_MAX_THR, S < 1, ldu < m,
+ * ldc < k, ldthr < m, ldp < m, overlapping planes, ldx < 1, ldcol < T, ldrow < m with row given, a size >= 2^31;
+ * DMDX_E_WORKSPACE: a null or short workspace) has written nothing. */
+#define DMDX_EXCEED_NQ 4
+#define DMDX_EXCEED_FP32_ROWS 128
+#define DMDX_EXCEED_MAX_B 256
+#define DMDX_EXCEED_MAX_THR 4
+int dmdx_exceed_max_k(void);
+int dmdx_exceed_max_members(void);
+int dmdx_exceed_max_thresholds(void);
+int dmdx_exceed_prob_f32(const float* U, int64_t m, int64_t k, int64_t ldu, const float* C, int64_t ldc, int64_t T, int64_t B,
+                         const float* mu, const float* sigma, const float* thr, int64_t ldthr, int64_t J, int64_t S,
+                         const int32_t* slot, int above, float* P, int64_t ldp, int64_t pstride, void* stream);
+size_t dmdx_exceed_score_workspace_bytes(int64_t m, int64_t k, int64_t T, int64_t B, int64_t J);
+int dmdx_exceed_score_f32(const float* U, int64_t m, int64_t k, int64_t ldu, const float* C, int64_t ldc, int64_t T, int64_t B,
+                          const float* mu, const float* sigma, const float* thr, int64_t ldthr, int64_t J, int64_t S,
+                          const int32_t* slot, int above, const float* X, int64_t ldx, const float* w,
+                          double* col, int64_t ldcol, double* row, int64_t ldrow, int64_t* cnt, int accumulate,
+                          void* workspace, size_t workspace_bytes, void* stream);
 
 /* ---- K14: CF-packed int16 codes -> fp32 snapshots of one row block ---------------------------------------------
  * What xr.open_dataset's mask_and_scale decoding (reference era5_svd.py:132 through retrieve_era5_slice) does to a
