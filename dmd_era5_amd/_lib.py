@@ -100,6 +100,9 @@ SIGNATURES = {
     "dmdx_clim_mean_f32": (C.c_int, [_p, _i64, _i64, _i64, _p, _i64, _p, _i64, _p, _i64, _p]),
     "dmdx_clim_std_f32": (C.c_int, [_p, _i64, _i64, _i64, _p, _i64, _p, _i64, _p, _i64, C.c_int, _p, _i64, _p]),
     "dmdx_clim_apply_f32": (C.c_int, [_p, _i64, _i64, _i64, _p, _i64, _p, _i64, _p, _i64, C.c_int, _p, _i64, _p]),
+    "dmdx_clim_quantile_max_q": (C.c_int, []),
+    "dmdx_clim_quantile_max_staged": (C.c_int, []),
+    "dmdx_clim_quantile_f32": (C.c_int, [_p, _i64, _i64, _i64, _p, _i64, _p, _i64, _p, _i64, C.c_int, C.c_int, _p, _i64, _p]),
     "dmdx_row_missing_count_f32": (C.c_int, [_p, _i64, _i64, _i64, _p, _p]),
     "dmdx_row_mask_apply_f32": (C.c_int, [_p, _i64, _i64, _i64, _p, C.c_float, _p]),
     "dmdx_treg_max_p": (C.c_int, []),

@@ -89,10 +89,25 @@ def slots_of(times, kind: str, window_days: int = 0):
     return slot.astype(np.int32), order, start, S
 
 
+QUANTILE_METHODS = ("linear", "lower", "higher")
+
+
+def _probabilities(quantiles, method: str, who: str) -> tuple:
+    """``quantiles`` as a tuple of 1 .. 4 floats in [0, 1] (K25 takes as many as K24 takes thresholds)."""
+    qs = tuple(float(v) for v in np.atleast_1d(np.asarray(quantiles, dtype=np.float64)).reshape(-1))
+    if not 1 <= len(qs) <= 4 or not all(0.0 <= v <= 1.0 for v in qs):
+        raise ValueError(f"{who}: quantiles must hold 1 .. 4 values in [0, 1], got {quantiles!r}")
+    if method not in QUANTILE_METHODS:
+        raise ValueError(f"{who}: method = {method!r}, expected one of {QUANTILE_METHODS}")
+    return qs
+
+
 @dataclass
 class Climatology:
     """The slot climatology of a list of row blocks: ``mean`` (and ``sd``) hold one ``(S, rows)`` fp32 tensor per
-    block, ``counts`` (S,) the snapshots every slot was formed from, ``ddof`` the one of ``sd``."""
+    block, ``counts`` (S,) the snapshots every slot was formed from, ``ddof`` the one of ``sd``.  With quantiles (K25):
+    ``q`` the J probabilities, ``quant`` one ``(J, S, rows)`` fp32 tensor per block, ``method`` how a position between
+    two members was resolved."""
 
     kind: str
     window_days: int
@@ -101,6 +116,9 @@ class Climatology:
     counts: np.ndarray
     ddof: int = 0
     kern: object = None
+    q: tuple | None = None
+    quant: list | None = None
+    method: str = "linear"
 
     @property
     def n_slots(self) -> int:
@@ -109,15 +127,19 @@ class Climatology:
     # -- fit ------------------------------------------------------------------------------------------------------
     @classmethod
     def fit(cls, Xblocks, times, kind: str, window_days: int = 0, with_std: bool = False, ddof: int = 0,
-            kern=None) -> "Climatology":
+            kern=None, quantiles=None, method: str = "linear") -> "Climatology":
         """The climatology of the snapshots ``Xblocks`` ((T, rows) fp32 per block, any iterable consumed once) taken
-        at ``times`` (T datetime64 stamps): one read of every block for the mean, one more with ``with_std``."""
+        at ``times`` (T datetime64 stamps): one read of every block for the mean, one more with ``with_std``, one
+        more with ``quantiles`` (1 .. 4 probabilities in [0, 1]: the empirical quantiles of every slot and row, K25;
+        ``method``: ``"linear"``, ``"lower"`` or ``"higher"``, numpy's names) -- the percentile thresholds of
+        :meth:`quantile_thresholds`."""
         if ddof not in (0, 1):
             raise ValueError(f"Climatology.fit: ddof = {ddof}, expected 0 or 1")
+        qs = None if quantiles is None else _probabilities(quantiles, method, "Climatology.fit")
         kern = _kern(kern)
         _, order, start, S = slots_of(times, kind, window_days)
         T = int(np.atleast_1d(np.asarray(times)).shape[0])
-        orders, starts, mean, sd = ta.OnDevices(order), ta.OnDevices(start), [], []
+        orders, starts, mean, sd, quant = ta.OnDevices(order), ta.OnDevices(start), [], [], []
         for b, X in enumerate(Xblocks):
             if X.shape[0] != T:
                 raise ValueError(f"Climatology.fit: block {b} holds {int(X.shape[0])} snapshots, times has {T}")
@@ -125,7 +147,10 @@ class Climatology:
             mean.append(kern.clim_mean(X, o, s))
             if with_std:
                 sd.append(kern.clim_std(X, o, s, mean[-1], ddof=ddof))
-        return cls(kind, int(window_days), mean, sd if with_std else None, np.diff(start.astype(np.int64)), int(ddof), kern)
+            if qs is not None:
+                quant.append(kern.clim_quantile(X, o, s, qs, method=method))
+        return cls(kind, int(window_days), mean, sd if with_std else None, np.diff(start.astype(np.int64)), int(ddof), kern,
+                   qs, quant if qs is not None else None, method if qs is not None else "linear")
 
     # -- apply ----------------------------------------------------------------------------------------------------
     def _labels(self, times, who: str) -> np.ndarray:
@@ -194,6 +219,18 @@ class Climatology:
             res.append((th if anomaly else M[None] + th).contiguous())
         return res
 
+    def quantile_thresholds(self, anomaly: bool = False) -> list:
+        """The empirical quantiles as thresholds: per block the (J, S, rows) fp32 table ``exceed_blocks`` /
+        ``exceed_prob_blocks`` / ``DmdForecast.ensemble_exceedance`` take, threshold j = quantile ``q[j]`` of the
+        slot.  ``anomaly``: ``quant - mean`` rounded once, for a model fitted on anomalies whose climatology was
+        fitted on the full fields.  A slot that was fitted from no snapshot has NaN thresholds (no event).  Without
+        quantiles a ValueError."""
+        if self.quant is None:
+            raise ValueError("Climatology.quantile_thresholds: the climatology holds no quantiles (fit with quantiles=)")
+        if not anomaly:
+            return [Q.contiguous() for Q in self.quant]
+        return [(Q - M[None]).contiguous() for Q, M in zip(self.quant, self.mean)]
+
     # -- persistence ----------------------------------------------------------------------------------------------
     def to_dataset(self, coords=None) -> Dataset:
         """``clim_mean(slot, space)``, ``clim_std`` if there is one, ``clim_count(slot)`` and the attributes ``kind``,
@@ -211,6 +248,12 @@ class Climatology:
         if self.sd is not None:
             ds["clim_std"] = DataArray(field(self.sd), ("slot", "space"), {"slot": cds["slot"], **row})
         ds["clim_count"] = DataArray(np.asarray(self.counts, dtype=np.int64), ("slot",), {"slot": cds["slot"]})
+        if self.quant is not None:
+            qc = Coord("quantile", np.asarray(self.q, dtype=np.float64))
+            ds.coords["quantile"] = qc
+            ds.attrs["quantile_method"] = self.method
+            ds["clim_quantile"] = DataArray(np.concatenate([B.detach().cpu().numpy() for B in self.quant], axis=2),
+                                            ("quantile", "slot", "space"), {"quantile": qc, "slot": cds["slot"], **row})
         return ds
 
     @classmethod
@@ -232,4 +275,17 @@ class Climatology:
             sd = ta.cut_rows(np.ascontiguousarray(np.asarray(ds["clim_std"].values), dtype=np.float32), rows, device,
                              kern, "Climatology.from_dataset")
         counts = np.asarray(ds["clim_count"].values).astype(np.int64).reshape(-1)
-        return cls(kind, ta.attr_int(ds.attrs["window_days"]), mean, sd, counts, ta.attr_int(ds.attrs["ddof"]), kern)
+        qs, quant, method = None, None, "linear"
+        if "clim_quantile" in ds:
+            table = np.ascontiguousarray(np.asarray(ds["clim_quantile"].values), dtype=np.float32)
+            J = int(table.shape[0])
+            method = ta.attr_str(ds.attrs["quantile_method"])
+            qs = _probabilities(np.asarray(ds.coords["quantile"].values, dtype=np.float64), method,
+                                "Climatology.from_dataset")
+            if table.shape[:2] != (len(qs), S):
+                raise ValueError(f"Climatology.from_dataset: clim_quantile is {table.shape}, {len(qs)} quantiles of {S} "
+                                 f"slots asked for")
+            flat = ta.cut_rows(table.reshape(J * S, -1), rows, device, kern, "Climatology.from_dataset")
+            quant = [F.reshape(J, S, -1) for F in flat]
+        return cls(kind, ta.attr_int(ds.attrs["window_days"]), mean, sd, counts, ta.attr_int(ds.attrs["ddof"]), kern,
+                   qs, quant, method)

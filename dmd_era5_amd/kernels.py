@@ -18,6 +18,9 @@ the GPU is missing.
 
 from __future__ import annotations
 
+import ctypes
+
+import numpy as np
 import torch
 
 from . import _lib
@@ -802,6 +805,53 @@ class HipKernels:
         ))
         _lib.check(rc, "dmdx_clim_apply_f32")
         return Yt
+
+    # -- K25 ----------------------------------------------------------------
+    QUANTILE_METHODS = {"linear": 0, "lower": 1, "higher": 2}
+
+    @property
+    def clim_quantile_max_q(self) -> int:
+        return int(self._lib.dmdx_clim_quantile_max_q())
+
+    @property
+    def clim_quantile_max_staged(self) -> int:
+        """The longest slot list whose members are staged in LDS (one read of X); longer ones are re-read per step."""
+        return int(self._lib.dmdx_clim_quantile_max_staged())
+
+    def clim_quantile(self, Xt: torch.Tensor, order: torch.Tensor, start: torch.Tensor, q, method: str = "linear",
+                      out: torch.Tensor | None = None, streamed: bool = False) -> torch.Tensor:
+        """The empirical quantiles of the snapshots of a row block per slot.  Xt, ``order``, ``start`` as
+        :meth:`clim_mean`; ``q``: 1 .. ``clim_quantile_max_q`` values in [0, 1]; ``method``: ``"linear"`` (numpy's
+        default), ``"lower"`` or ``"higher"`` -> (J, S, m) fp32, the ``thr`` of :meth:`exceed_prob`: order statistics
+        with their bits, the linear interpolation in fp64 rounded once; NaN for a slot without a counted snapshot
+        and where a member is NaN.  ``out``: a (J, S, m) fp32 view to write into (inner stride 1, the planes one
+        uniform row stride apart).  ``streamed``: re-read the members in every step of the selection instead of
+        staging them in LDS (the route of lists beyond ``clim_quantile_max_staged``; the same bits)."""
+        m, T, ldx, n_order, S = self._clim_lists(Xt, order, start, "clim_quantile")
+        qs = [float(v) for v in np.atleast_1d(np.asarray(q, dtype=np.float64)).reshape(-1)]
+        J = len(qs)
+        if not 1 <= J <= self.clim_quantile_max_q or not all(0.0 <= v <= 1.0 for v in qs):
+            raise _lib.DmdxError(f"clim_quantile: q must hold 1 .. {self.clim_quantile_max_q} values in [0, 1], got {q!r}")
+        if method not in self.QUANTILE_METHODS:
+            raise _lib.DmdxError(f"clim_quantile: method = {method!r}, expected one of {sorted(self.QUANTILE_METHODS)}")
+        if out is None:
+            res = torch.empty((J, S, m), dtype=torch.float32, device=Xt.device)
+        else:
+            if (not isinstance(out, torch.Tensor) or out.dim() != 3 or tuple(out.shape) != (J, S, m)
+                    or (J > 1 and S > 1 and out.stride(0) != S * out.stride(1))):
+                raise _lib.DmdxError(f"clim_quantile: out must be a ({J}, {S}, {m}) fp32 view whose planes lie one uniform "
+                                     f"row stride apart")
+            res = out
+        row = res.stride(0) if S == 1 else res.stride(1)
+        flat, ldo = _out_view(res.as_strided((J * S, m), (row, res.stride(2))), m, J * S, torch.float32, Xt.device,
+                              "clim_quantile")
+        qa = (ctypes.c_double * J)(*qs)
+        rc = self._timed("clim_quantile", (m, T, S, J), lambda: self._lib.dmdx_clim_quantile_f32(
+            _ptr(Xt), m, T, ldx, _ptr(order), n_order, _ptr(start), S, qa, J, self.QUANTILE_METHODS[method],
+            int(bool(streamed)), _ptr(flat), ldo, self._stream()
+        ))
+        _lib.check(rc, "dmdx_clim_quantile_f32")
+        return res
 
     # -- K21 ----------------------------------------------------------------
     # the fit cuts time over workgroups (a workspace of segment sums, added in order by a second kernel) whenever

@@ -693,6 +693,40 @@ int dmdx_clim_apply_f32(const float* X, int64_t m, int64_t T, int64_t ldx, const
                         const float* mean, int64_t ldc, const float* sd /* nullable */, int64_t lds, int restore,
                         float* Y, int64_t ldy, void* stream);
 
+/* ---- K25: empirical quantiles of the snapshots per slot -- the percentile thresholds of K24 ------------------------------
+ * The thresholds published for fields that are not normal (precipitation, wind speed, daily maxima) are percentiles of
+ * a calendar slot: the 10th / 90th percentile of a +-2-day window (ETCCDI, TX90p), terciles.  X, order, n_order, start
+ * and S are those of dmdx_clim_mean_f32, read the same way: start clamped to [0, n_order], an entry of order outside
+ * [0, T) skipped, not counted and never used as an address; a snapshot may be listed in several slots and more than
+ * once in one.  n_s = the counted entries of slot s.  q: J doubles ON THE HOST, each in [0, 1], 1 <= J <=
+ * dmdx_clim_quantile_max_q() = DMDX_CLIM_QUANTILE_MAX_Q (4 = DMDX_EXCEED_MAX_THR).
+ *   out[(j S + s) ldo + i]   quantile q[j] of row i over the members of slot s, ldo >= m: K24's thr layout ("column
+ *                            j S + s"), so out is the thr operand of dmdx_exceed_* with ldthr = ldo.
+ * Order: by the key of the bit pattern u -- ~u if the sign bit is set, u | 0x80000000 otherwise --, a total order:
+ * -0.0 before +0.0, the infinities and the denormals ordinary values, nothing flushed; x_(0) <= ... <= x_(n_s - 1).
+ * Position, IEEE fp64, the product rounded once:  h = q[j] (n_s - 1),  lo = floor(h),  g = h - floor(h).
+ *   method 0 (linear, numpy's default, type 7) as above;  1 (lower) g := 0;  2 (higher) lo := ceil(h), g := 0.
+ * Result: with g == 0 the bits of x_(lo), unchanged; otherwise d = fp64(x_(lo + 1)) - fp64(x_(lo)), p = d g,
+ * r = fp64(x_(lo)) + p, each rounded, none fused, then one rounding to fp32 (Inf - Inf: a NaN of arithmetic, no
+ * contractual bits).  n_s == 0: the quiet NaN 0x7FC00000 for every j; a NaN among the counted members of (slot, row):
+ * 0x7FC00000 for every j of that (slot, row) and nothing else changes.  2^e X gives 2^e out bit for bit (no overflow,
+ * no underflow).  No atomics, no workspace, no allocation, no synchronisation; the bits depend on the operands only --
+ * not on the body that ran, the launch geometry, the alignment of X or ldx.
+ * Bodies, chosen per slot by the length L of its clamped list (skipped entries included): with C =
+ * dmdx_clim_quantile_max_staged() / 4, L <= C stages the keys of 64 rows in LDS, L <= 2 C those of 32 rows, L <= 4 C
+ * those of 16 rows (one read of X each); a longer list, or every list with streamed != 0, re-reads its members from
+ * global memory in every step of the selection (no limit on L, no speed).
+ * Memory: only logical elements of X are read, every logical element of out is written, nothing else; no alignment
+ * beyond that of the elements.  A refused call (DMDX_E_INVALID: a null X, order, start, q or out; S < 1; J outside
+ * 1 .. 4; a q[j] that is NaN or outside [0, 1]; method outside 0 .. 2; ldx < m or ldo < m; a negative size; a size or
+ * J S >= 2^31) has written nothing.  m == 0 returns 0 after the checks; T == 0 with m > 0 fills out with the NaN. */
+#define DMDX_CLIM_QUANTILE_MAX_Q 4
+int dmdx_clim_quantile_max_q(void);
+int dmdx_clim_quantile_max_staged(void);
+int dmdx_clim_quantile_f32(const float* X, int64_t m, int64_t T, int64_t ldx, const int32_t* order, int64_t n_order,
+                           const int32_t* start, int64_t S, const double* q /* HOST, J values */, int64_t J, int method,
+                           int streamed, float* out, int64_t ldo, void* stream);
+
 /* ---- K20: rows (grid points) with a missing value, and one value for all of them -------------------------------------
  * What lets a field with a static mask -- sea-surface temperature, missing over land in every file -- through the
  * decomposition: a grid point that is missing in any snapshot takes no part (its row of X becomes 0, which gives a zero
