@@ -109,6 +109,10 @@ SIGNATURES = {
     "dmdx_treg_fit_workspace_bytes": (_sz, [_i64, _i64, _i64, _i64]),
     "dmdx_treg_fit_f32": (C.c_int, [_p, _i64, _i64, _i64, _p, C.c_int, _i64, _i64, _p, _i64, _p, _sz, _p]),
     "dmdx_treg_apply_f32": (C.c_int, [_p, _i64, _i64, _i64, _p, C.c_int, _i64, _p, _i64, C.c_int, _p, _i64, _p]),
+    "dmdx_lag_moments_max_lags": (C.c_int, []),
+    "dmdx_lag_moments_ring": (C.c_int, []),
+    "dmdx_lag_moments_workspace_bytes": (_sz, [_i64, _i64, _i64, _i64]),
+    "dmdx_lag_moments_f32": (C.c_int, [_p, _i64, _i64, _i64, _p, _p, C.c_int, _i64, _p, _i64, C.c_int, _p, _sz, _p]),
     "dmdx_tfilt_max_taps": (C.c_int, []),
     "dmdx_tfilt_f32": (C.c_int, [_p, _i64, _i64, _i64, _p, _i64, _i64, _p, _i64, _i64, _p]),
     "dmdx_coarsen_max_factor": (C.c_int, []),

@@ -96,8 +96,10 @@ class HipKernels:
 
     name = "hip"
 
-    def __init__(self):
-        self._lib = _lib.load()
+    def __init__(self, lib=None):
+        # lib: another build of the library with its signatures set (the A/B builds of the measurement scripts);
+        # workspaces and events are per object, nothing is shared with the default provider
+        self._lib = _lib.load() if lib is None else lib
         if not torch.cuda.is_available():
             raise _lib.DmdxError("no HIP device visible: the dmdx kernels have no CPU fallback")
         self._ws: dict[int, torch.Tensor] = {}
@@ -909,6 +911,50 @@ class HipKernels:
         ))
         _lib.check(rc, "dmdx_treg_apply_f32")
         return Yt
+
+    # -- K26 ----------------------------------------------------------------
+    @property
+    def lag_max_lags(self) -> int:
+        return int(self._lib.dmdx_lag_moments_max_lags())
+
+    @property
+    def lag_ring(self) -> int:
+        """The largest lag whose earlier member a lane keeps in LDS; beyond it the member is loaded again."""
+        return int(self._lib.dmdx_lag_moments_ring())
+
+    def lag_moments(self, Xt: torch.Tensor, lags, mu: torch.Tensor | None = None, seg: int = 1024,
+                    out: torch.Tensor | None = None, ring: bool = True) -> torch.Tensor:
+        """The lagged second moments of every row of a block.  Xt: (T, m) fp32 (any row stride); ``lags``: 1 .. 8
+        strictly ascending integers, 0 <= tau < T; ``mu``: (m,) fp32 centres or None; ``seg``: the segment length of
+        the fp64 sums (part of the result: :data:`baseline.SEGMENT`) -> (1 + 3L, m) fp64: plane 0 the sum of squares
+        S of ``d = fp64(x) - fp64(mu)``, planes 1 + l the lagged products P_l, planes 1 + L + l and 1 + 2L + l the
+        squares of the first and of the last tau_l snapshots (H_l, E_l).  ``out``: a (1 + 3L, m) fp64 view to write
+        into (inner stride 1); ``ring`` False loads the earlier member of every pair again instead of keeping it
+        in LDS (the same bits).  One read of Xt, time split over workgroups whenever there is more than one
+        segment."""
+        lags = [int(v) for v in lags]
+        L = len(lags)
+        if not 1 <= L <= self.lag_max_lags or int(seg) < 1:
+            raise _lib.DmdxError(f"lag_moments: {L} lags outside 1..{self.lag_max_lags} or seg = {seg} < 1")
+        if Xt.dim() != 2:
+            raise _lib.DmdxError(f"lag_moments: X must be (T, m), got {tuple(Xt.shape)}")
+        T, m = int(Xt.shape[0]), int(Xt.shape[1])
+        # here and not only in C: the int32 array below would wrap a lag of 2^32 + 1 to 1, which passes there
+        if T > 0 and (lags[0] < 0 or lags[-1] >= T or any(b <= a for a, b in zip(lags, lags[1:]))):
+            raise _lib.DmdxError(f"lag_moments: lags must be strictly ascending with 0 <= tau < T = {T}, got {lags}")
+        ldx = _check_snapshots(Xt, m, T, Xt.device, "lag_moments")
+        _check_vec(mu, m, Xt.device, "lag_moments", "mu")
+        planes, ldo = _out_view(out, m, 1 + 3 * L, torch.float64, Xt.device, "lag_moments")
+        split = T > int(seg)
+        nbytes = int(self._lib.dmdx_lag_moments_workspace_bytes(m, T, L, int(seg))) if split else 0
+        ws = self._workspace(Xt.device, nbytes) if split else None
+        host = (ctypes.c_int32 * L)(*lags)
+        rc = self._timed("lag_moments", (m, T, L), lambda: self._lib.dmdx_lag_moments_f32(
+            _ptr(Xt), m, T, ldx, _ptr(mu), host, L, int(seg), _ptr(planes), ldo, 0 if ring else 1, _ptr(ws), nbytes,
+            self._stream()
+        ))
+        _lib.check(rc, "dmdx_lag_moments_f32")
+        return planes
 
     # -- K22 ----------------------------------------------------------------
     @property

@@ -788,6 +788,50 @@ int dmdx_treg_fit_f32(const float* X, int64_t m, int64_t T, int64_t ldx, const d
 int dmdx_treg_apply_f32(const float* X, int64_t m, int64_t T, int64_t ldx, const double* D, int p, int64_t ldd,
                         const float* coef, int64_t ldc, int restore, float* Y, int64_t ldy, void* stream);
 
+/* ---- K26: lagged second moments of every row of a row block: autocorrelation and the persistence baselines ------------
+ * The sums behind autocovariance / autocorrelation, the persistence, damped-persistence and climatology baselines of a
+ * forecast score and the effective sample size of a trend map, for L <= dmdx_lag_moments_max_lags() (8) lags in one read
+ * of X.  X is a row block as everywhere: T columns (snapshots) of m floats, ldx >= m.
+ *   mu     (device fp32, nullable) one centre per row.       lags   (HOST int32) L lags, strictly ascending, 0 <= tau < T.
+ *   out    (device fp64) 1 + 3L planes of m doubles, plane q at out + q ldo, ldo >= m.  Nothing is rounded to fp32.
+ * For row i:  d_t = fp64(x_t) - fp64(mu) (one rounded subtraction; with mu == NULL d_t = fp64(x_t), no operation),
+ * sq_t = d_t d_t (rounded), pr_u = d_{u - tau} d_u (rounded), indexed by the LATER snapshot u in [tau, T).
+ * segsum(v, I): time is cut into segments of `seg` >= 1 snapshots, [0, seg), [seg, 2 seg), ... as in K21;
+ *     tot = +0.0; for every segment in ascending order { acc = +0.0; for t ascending in I and the segment { acc = acc + v_t; }
+ *     tot = tot + acc; }            -- all in fp64, never an FMA; segments that hold no index of I are included.
+ *   plane 0           S   = segsum(sq, [0, T))
+ *   plane 1 + l       P_l = segsum(pr, [tau_l, T))
+ *   plane 1 + L + l   H_l = segsum(sq, [0, tau_l))        the head the later members of the pairs miss
+ *   plane 1 + 2L + l  E_l = segsum(sq, [T - tau_l, T))    the tail the earlier members miss
+ * so that S - E_l and S - H_l are the squares of the earlier and of the later members, and T - tau_l the pairs.
+ * The partition is part of the result and the launch is not: with `workspace` (dmdx_lag_moments_workspace_bytes(m, T, L,
+ * seg) bytes = ceil(T / seg) (1 + L) m doubles, no initialisation needed) every segment of S and P is summed by workgroups
+ * of its own and a second kernel adds the partials in ascending order; with workspace == NULL one lane walks the segments
+ * of its rows.  Both give the same bits.  The walk is meant for a T of a few segments or few rows: it has 1 / segments of
+ * the split's workgroups, re-reads the ring's snapshots at every segment start, and with more than 4 lags its 16-byte
+ * body runs one wave per SIMD where the split runs two: pass the workspace whenever T > seg on a full row block.
+ * H and E come from a small pass of their own over the first and the last tau_max
+ * snapshots.  The earlier member of a pair with tau <= dmdx_lag_moments_ring() (16) is kept by its lane in LDS; for a
+ * larger lag, or for every lag with flags bit 0 set, it is a second load from the caches: the same bits either way, and
+ * a mixed list uses each per lag in one launch.  No other bit of flags is defined.
+ * No allocation, no synchronisation, no atomics: results are bit-wise reproducible.
+ * Memory: only the logical elements of X and mu are read (X is never written), only the logical (1 + 3L) x m elements of
+ * out and the declared workspace bytes are written.  out and workspace are 8-byte aligned; X and mu need no alignment
+ * beyond their elements: a 16-byte aligned X with ldx % 4 == 0 is read with 16-byte loads (4 rows per lane, the ragged
+ * last quad element by element), anything else one dword per lane, with the same bits.
+ * Values: a non-finite X[i, t] reaches the planes of row i whose index sets hold t and nothing else; a row of zeros
+ * with mu == NULL gives +0.0 in every plane.
+ * A refused call (DMDX_E_INVALID: L outside 1 .. 8; null lags; lags not strictly ascending, negative or >= T; seg < 1; an
+ * undefined flag bit; a negative size; m, T, seg or a leading dimension >= 2^31; ldx or ldo < m; a pointer not aligned
+ * to its element; out overlapping X; a workspace smaller than asked for; a null X or out with m T > 0) has written
+ * nothing.  m == 0 or T == 0 returns 0 after the checks without a launch (no lag is compared with T == 0). */
+int dmdx_lag_moments_max_lags(void);
+int dmdx_lag_moments_ring(void);
+size_t dmdx_lag_moments_workspace_bytes(int64_t m, int64_t T, int64_t L, int64_t seg);
+int dmdx_lag_moments_f32(const float* X, int64_t m, int64_t T, int64_t ldx, const float* mu /* nullable */,
+                         const int32_t* lags /* host */, int L, int64_t seg, double* out, int64_t ldo, int flags,
+                         void* workspace /* nullable */, size_t workspace_bytes, void* stream);
+
 /* ---- K22: a FIR filter along time with an output stride: daily means, low-pass + decimation, band-pass ----------------
  * The fourth preparation step on the device, before K18 and K21: a weighted sum over a sliding window of snapshots.  X
  * and Y are row blocks as everywhere: snapshot t of X at X + t ldx, output snapshot u of Y at Y + u ldy, m floats each,
