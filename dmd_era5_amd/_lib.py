@@ -113,6 +113,11 @@ SIGNATURES = {
     "dmdx_lag_moments_ring": (C.c_int, []),
     "dmdx_lag_moments_workspace_bytes": (_sz, [_i64, _i64, _i64, _i64]),
     "dmdx_lag_moments_f32": (C.c_int, [_p, _i64, _i64, _i64, _p, _p, C.c_int, _i64, _p, _i64, C.c_int, _p, _sz, _p]),
+    "dmdx_spell_max_thresholds": (C.c_int, []),
+    "dmdx_spell_max_periods": (C.c_int, []),
+    "dmdx_spell_workspace_bytes": (_sz, [_i64, _p, C.c_int, C.c_int, _i64]),
+    "dmdx_spell_f32": (C.c_int, [_p, _i64, _i64, _i64, _p, _i64, C.c_int, _i64, _p, C.c_uint, _p, _p, C.c_int, _i64, _p,
+                                 _i64, C.c_int, _p, _sz, _p]),
     "dmdx_tfilt_max_taps": (C.c_int, []),
     "dmdx_tfilt_f32": (C.c_int, [_p, _i64, _i64, _i64, _p, _i64, _i64, _p, _i64, _i64, _p]),
     "dmdx_coarsen_max_factor": (C.c_int, []),

@@ -78,7 +78,8 @@ def _out_view(out: torch.Tensor | None, m: int, T: int, dtype, device, who: str,
     return out, _check_field(out, m, T, dtype, device, who, "out", kind)
 
 
-_DTYPE_NAME = {torch.float64: "fp64", torch.int64: "int64"}
+_DTYPE_NAME = {torch.float64: "fp64", torch.int64: "int64", torch.int32: "int32"}
+DMDX_SPELL_NQ = 7                        # the planes of K27 (include/dmdx.h)
 
 
 def _accumulator(out: torch.Tensor | None, shape: tuple, dtype, device, who: str, name: str = "out") -> torch.Tensor:
@@ -954,6 +955,82 @@ class HipKernels:
             self._stream()
         ))
         _lib.check(rc, "dmdx_lag_moments_f32")
+        return planes
+
+    # -- K27 ----------------------------------------------------------------
+    @property
+    def spell_max_thresholds(self) -> int:
+        return int(self._lib.dmdx_spell_max_thresholds())
+
+    @property
+    def spell_max_periods(self) -> int:
+        """The periods of one launch (their bounds travel by value); :meth:`spells` loops beyond."""
+        return int(self._lib.dmdx_spell_max_periods())
+
+    def spells(self, Xt: torch.Tensor, thr: torch.Tensor, bounds, min_len=1, above=True,
+               slot: torch.Tensor | None = None, seg: int = 512, out: torch.Tensor | None = None) -> torch.Tensor:
+        """Spell and exceedance-count indices of every row of a block, per threshold and period.  Xt: (T, m) fp32 (any
+        row stride); thr: (J, S, m) or (J, m) fp32, threshold j of every row for slot s (as :meth:`exceed_prob`), J <=
+        ``spell_max_thresholds``; ``bounds``: P + 1 strictly ascending integers in 0 .. T, period p is the snapshots
+        [b_p, b_{p+1}); ``min_len``: the shortest run that qualifies, one integer >= 1 or one per threshold;
+        ``above``: the event is x > thr, otherwise x < thr (strict), one bool or one per threshold; slot: (T,) device
+        int32 labels or None (S = 1); a label outside 0 .. S - 1 makes its snapshot invalid -> (J, 7, P, m) int32:
+        n_valid, n_event, n_spell, n_in_spell, longest, first, last (include/dmdx.h, K27).  A run never spans two
+        periods.
+
+        ``seg``: the snapshots of a piece of the time split; no value depends on it.  Time is split over workgroups
+        whenever there is more than one piece; any number of periods runs in launches of ``spell_max_periods``.
+        ``out``: a contiguous (J, 7, P, m) int32 tensor to write into."""
+        who = "spells"
+        if Xt.dim() != 2:
+            raise _lib.DmdxError(f"{who}: X must be (T, m), got {tuple(Xt.shape)}")
+        T, m = int(Xt.shape[0]), int(Xt.shape[1])
+        ldx = _check_snapshots(Xt, m, T, Xt.device, who)
+        if (not isinstance(thr, torch.Tensor) or thr.dtype != torch.float32 or thr.dim() not in (2, 3)
+                or thr.device != Xt.device or thr.shape[-1] != m or not thr.is_contiguous()):
+            raise _lib.DmdxError(f"{who}: thr must be a contiguous (J, S, {m}) or (J, {m}) fp32 tensor on {Xt.device}")
+        thr3 = thr if thr.dim() == 3 else thr.unsqueeze(1)
+        J, S = int(thr3.shape[0]), int(thr3.shape[1])
+        if not 1 <= J <= self.spell_max_thresholds or S < 1:
+            raise _lib.DmdxError(f"{who}: {J} thresholds in {S} slots; 1 .. {self.spell_max_thresholds} thresholds and at "
+                                 f"least one slot asked for")
+        if slot is None:
+            if S != 1:
+                raise _lib.DmdxError(f"{who}: thr has {S} slots, so slot must name one per snapshot")
+        else:
+            _check_ivec(slot, Xt.device, who, "slot", T)
+        b = [int(v) for v in np.asarray(bounds).reshape(-1)]
+        # here and not only in C: the int32 arrays below would wrap what does not fit them
+        if len(b) < 2 or b[0] < 0 or b[-1] > T or any(y <= x for x, y in zip(b, b[1:])):
+            raise _lib.DmdxError(f"{who}: bounds must be at least 2 strictly ascending integers in 0 .. T = {T}")
+        ml = [int(v) for v in np.atleast_1d(np.asarray(min_len)).reshape(-1)]
+        ab = [bool(v) for v in np.atleast_1d(np.asarray(above)).reshape(-1)]
+        ml, ab = (ml * J if len(ml) == 1 else ml), (ab * J if len(ab) == 1 else ab)
+        if len(ml) != J or len(ab) != J or min(ml) < 1 or max(ml) >= 2**31 or not 1 <= int(seg) < 2**31:
+            raise _lib.DmdxError(f"{who}: min_len and above hold one value or {J}, min_len >= 1 and seg >= 1 asked for "
+                                 f"(min_len = {min_len!r}, above = {above!r}, seg = {seg})")
+        P = len(b) - 1
+        planes = _accumulator(out, (J, DMDX_SPELL_NQ, P, m), torch.int32, Xt.device, who)
+        if m == 0:
+            return planes
+        mask = sum(1 << j for j in range(J) if ab[j])
+        host_ml = (ctypes.c_int32 * J)(*ml)
+        maxp = self.spell_max_periods
+        for p0 in range(0, P, maxp):
+            n = min(maxp, P - p0)
+            part = planes if n == P else torch.empty((J, DMDX_SPELL_NQ, n, m), dtype=torch.int32, device=Xt.device)
+            host_b = (ctypes.c_int32 * (n + 1))(*b[p0:p0 + n + 1])
+            pieces = sum(-(-(y - x) // int(seg)) for x, y in zip(b[p0:p0 + n], b[p0 + 1:p0 + n + 1]))
+            split = pieces > 1
+            nbytes = int(self._lib.dmdx_spell_workspace_bytes(m, host_b, n, J, int(seg))) if split else 0
+            ws = self._workspace(Xt.device, nbytes) if split else None
+            rc = self._timed("spells", (m, b[p0 + n] - b[p0], J, n), lambda: self._lib.dmdx_spell_f32(
+                _ptr(Xt), m, T, ldx, _ptr(thr3), m, J, S, _ptr(slot), mask, host_ml, host_b, n, int(seg), _ptr(part), m, 0,
+                _ptr(ws), nbytes, self._stream()
+            ))
+            _lib.check(rc, "dmdx_spell_f32")
+            if part is not planes:
+                planes[:, :, p0:p0 + n] = part
         return planes
 
     # -- K22 ----------------------------------------------------------------

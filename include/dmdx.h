@@ -832,6 +832,63 @@ int dmdx_lag_moments_f32(const float* X, int64_t m, int64_t T, int64_t ldx, cons
                          const int32_t* lags /* host */, int L, int64_t seg, double* out, int64_t ldo, int flags,
                          void* workspace /* nullable */, size_t workspace_bytes, void* stream);
 
+/* ---- K27: spell and exceedance-count indices of every row of a row block, per threshold and period ------------------
+ * What climate users compute first from percentile thresholds (K25) or fixed ones, on an analysis or a forecast field:
+ * the snapshots of a year beyond the threshold (TX90p / TN10p), those in runs of at least 6 (WSDI / CSDI), the longest
+ * run (CDD / CWD), and where the first and the last such run of a season lie (heat-wave onset, first and last frost).  X
+ * is a row block as everywhere: T columns (snapshots) of m floats, ldx >= m, only read.  thr (m x (J S), ldthr >= m) and
+ * slot (T device int32, nullable: every snapshot in slot 0) are K24's: column j S + s holds threshold j of every row for
+ * slot s; 1 <= J <= dmdx_spell_max_thresholds() = DMDX_SPELL_MAX_THR (4), S >= 1.
+ *   bounds     (HOST int32) P + 1 values, 0 <= b_0 < b_1 < ... < b_P <= T, 1 <= P <= dmdx_spell_max_periods() =
+ *              DMDX_SPELL_MAX_PERIODS (128; they travel by value, a caller with more periods makes several calls).
+ *              Period p is the snapshots [b_p, b_{p+1}); snapshots outside [b_0, b_P) are not read.
+ *   min_len    (HOST int32) J values >= 1: the shortest run of threshold j that qualifies.
+ *   above_mask bit j set: the event of threshold j is x > h;  clear: x < h.  Bits at or above J must be 0.
+ * For row i, threshold j and snapshot t of a period, with x = X[i, t] and h = thr[i, j S + slot[t]]:
+ *   valid  v_t = x is finite (K20's test of the bit pattern)  and  slot[t] lies in 0 .. S - 1  and  h is not NaN
+ *   event  e_t = v_t and (x > h or x < h, as above_mask says): a strict IEEE comparison, a tie is no event, an infinite
+ *          threshold is a threshold
+ *   run    a maximal set of consecutive t INSIDE ONE PERIOD with e_t true: a period boundary cuts a run (spells do not
+ *          span years, as in climdex), an invalid snapshot ends one.  A run QUALIFIES if its length is >= min_len[j].
+ * The DMDX_SPELL_NQ = 7 results, int32, at out[((j 7 + q) P + p) ldo + i], ldo >= m:
+ *   0 n_valid     the number of v_t               1 n_event      the number of e_t
+ *   2 n_spell     the qualifying runs             3 n_in_spell   the sum of their lengths
+ *   4 longest     the length of the longest run, qualifying or not; 0 if there is none
+ *   5 first       t - b_p of the first snapshot of the first qualifying run; -1 if there is none
+ *   6 last        t - b_p of the last snapshot of the last qualifying run; -1 if there is none
+ * Every period is cut from its own start into pieces of `seg` >= 1 snapshots, N = sum_p ceil((b_{p+1} - b_p) / seg)
+ * pieces in all.  With `workspace` (dmdx_spell_workspace_bytes(m, bounds, P, J, seg) bytes = N J m DMDX_SPELL_WS_WORDS
+ * int32, no initialisation needed) every piece is scanned by workgroups of its own into a record per (row, j) -- valid,
+ * events, the run at its head, the run at its tail, and what the runs strictly inside closed to -- and a second kernel
+ * merges the records of a period in ascending order: a piece of events only extends the carry; otherwise carry + head
+ * is a run, the interior is added and the carry becomes the tail; the carry is closed at the period's end.  With
+ * workspace == NULL one lane walks the periods of its rows.  The results are integers and the merge is exact: both forms
+ * and every seg give the same values -- here the partition is NOT part of the result.  The walk has one workgroup row:
+ * pass the workspace whenever there is more than one piece on a full row block.
+ * The thresholds of a row are loaded again only when slot[t] changes: X is read once, thr once per change of slot.
+ * No allocation, no synchronisation, no atomics, no copy.
+ * Memory: only the logical elements of X in [b_0, b_P), of slot in [b_0, b_P) and of the columns of thr they name are
+ * read; only the logical J x 7 x P x m elements of out, every one of them, and the declared workspace bytes are written.
+ * X, thr, slot, out and workspace need no alignment beyond 4 bytes: a 16-byte aligned X with ldx % 4 == 0 is read with
+ * 16-byte loads (4 rows per lane, the ragged last quad element by element), anything else one dword per lane.
+ * A refused call (DMDX_E_INVALID: J outside 1 .. 4; S < 1; P outside 1 .. 128; null bounds or min_len; bounds not
+ * strictly ascending or outside [0, T]; min_len[j] < 1; seg < 1; a bit of above_mask at or above J; any bit of flags
+ * (none is defined; reserved for spells that span periods); a negative size; m, T, S, J S, seg or a leading dimension
+ * >= 2^31; ldx, ldthr or ldo < m; a pointer not aligned to its element; out overlapping X or thr; a workspace smaller
+ * than asked for; a null X, thr or out with m > 0) has written nothing.  m == 0 returns 0 after the checks without a
+ * launch.  dmdx_spell_workspace_bytes returns 0 for arguments the call would refuse. */
+#define DMDX_SPELL_NQ 7
+#define DMDX_SPELL_MAX_THR 4
+#define DMDX_SPELL_MAX_PERIODS 128
+#define DMDX_SPELL_WS_WORDS 9
+int dmdx_spell_max_thresholds(void);
+int dmdx_spell_max_periods(void);
+size_t dmdx_spell_workspace_bytes(int64_t m, const int32_t* bounds /* host */, int P, int J, int64_t seg);
+int dmdx_spell_f32(const float* X, int64_t m, int64_t T, int64_t ldx, const float* thr, int64_t ldthr, int J, int64_t S,
+                   const int32_t* slot /* device, nullable */, unsigned above_mask, const int32_t* min_len /* host, J */,
+                   const int32_t* bounds /* host, P + 1 */, int P, int64_t seg, int32_t* out, int64_t ldo, int flags,
+                   void* workspace /* nullable */, size_t workspace_bytes, void* stream);
+
 /* ---- K22: a FIR filter along time with an output stride: daily means, low-pass + decimation, band-pass ----------------
  * The fourth preparation step on the device, before K18 and K21: a weighted sum over a sliding window of snapshots.  X
  * and Y are row blocks as everywhere: snapshot t of X at X + t ldx, output snapshot u of Y at Y + u ldy, m floats each,
