@@ -5,9 +5,16 @@
 // of values (truncation: m < 2^-7, l < 2^-15 of the binade) and come to about 2^-23 sum |a b| over a sum, one-signed
 // on all-positive data.
 //
-// Two forms that give the SAME planes for every finite value:
-//   split2_fast  and / subtract / pack, plus a detector (detect) that turns NaN on a non-finite input;
-//   split2_safe  the class rule of the value contract: a non-finite x keeps its class in h (Inf stays Inf,
+// Two forms that give the SAME planes for every finite value.  K1 runs the fast one everywhere and asks once per work
+// unit, on the unit's result, whether it was enough (alarm); only a unit that raised the alarm runs again, from its
+// first chunk, on the class-safe form.
+//   split2_fast  and / subtract / pack, nothing else in the loop.  A non-finite x leaves NaN in m and l (Inf - Inf,
+//                NaN - Inf): the packed l plane of EVERY Inf and NaN is a bf16 NaN (all 2^24 patterns:
+//                tests/host/bf16_fastnan_main.cpp).  The l plane is the carrier of the alarm: K1 contracts l h' and
+//                h' l for every pair, so every output that a non-finite input feeds is NaN at the end of the unit,
+//                whatever the partner holds (NaN * 0 is NaN), and an output that none feeds never sees such a plane.
+//                No NaN in the unit's result: the fast planes were the right ones.
+//   split2_safe  the rerun.  The class rule of the value contract: a non-finite x keeps its class in h (Inf stays Inf,
 //                every NaN becomes a quiet bf16 NaN -- truncation alone would turn a NaN whose payload sits in
 //                the low 16 bits into Inf), m = l = 0, and the copy h' for the four cross products holds 0 in
 //                its place: Inf then meets only the h of its partner, which is non-zero exactly when the
@@ -53,8 +60,12 @@ DMDX_SPLIT_HD uint32_t pack2(uint32_t a, uint32_t b) {
 }
 
 // running detector: stays a (signed) zero over finite values, NaN from the first Inf or NaN on
+// (the per-group detector of the first plane k-step; K1 no longer runs it -- the host checks still hold it to its word)
 DMDX_SPLIT_HD float detect(float x, float s) { return __builtin_fmaf(x, 0.0f, s); }
 DMDX_SPLIT_HD bool fired(float s) { return s != s; }
+
+// the verdict on one value of a unit's result: a NaN there <= a non-finite input (or Inf - Inf after overflow) fed it
+DMDX_SPLIT_HD bool alarm(float v) { return v != v; }
 
 DMDX_SPLIT_HD bool non_finite(uint32_t u) { return (u & 0x7F800000u) == 0x7F800000u; }
 
@@ -78,8 +89,8 @@ DMDX_SPLIT_HD void split2_fast(float x0, float x1, uint32_t& H, uint32_t& M, uin
 
 #if defined(__HIPCC__)
 // The fast form on a register pair, for the kernel: the same and / subtract / pack on both values at once (the two
-// subtractions are one packed fp32 instruction each, the detector one packed fma): the same planes as split2_fast,
-// operation for operation.  The detector pair stays (+-0, +-0) over finite values.
+// subtractions are one packed fp32 instruction each): the same planes as split2_fast, operation for operation.
+// (detect_pair: the retired per-group detector on a pair, one packed fma; it stays (+-0, +-0) over finite values.)
 typedef float f32x2_t __attribute__((ext_vector_type(2)));
 typedef uint32_t u32x2_t __attribute__((ext_vector_type(2)));
 DMDX_SPLIT_HD void split2_fast_pair(f32x2_t x, uint32_t& H, uint32_t& M, uint32_t& L) {

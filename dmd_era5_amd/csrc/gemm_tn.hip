@@ -30,9 +30,13 @@
 //   2^-21 |a b| per pair, about 2^-23 sum |a b| over a sum.  The bf16 MFMA truncates its sum a few bits below the
 //   fp32 ulp of its accumulator (one-signed: it shows on the diagonal of a Gram), so this body keeps its MFMA chains to
 //   ONE chunk of 32 rows and adds every chunk result into the second accumulator with rounded fp32 adds: at most
-//   2048 of them per unit, the same order as the 4096-row chain bound.  Inf / NaN keep numpy's classes (the class
-//   rule of bf16_split.h, on a wave-uniform slow path behind a detector; it assumes normal fp32 partners: Inf times
-//   a subnormal below 2^-133 gives NaN, not Inf).  Planes of values below ~2^-103 turn
+//   2048 of them per unit, the same order as the 4096-row chain bound.  Inf / NaN keep numpy's classes, and finite
+//   data pays nothing for it in the loop: every unit runs on the fast planes, whose l plane is NaN for every Inf and
+//   NaN, so that each output such a value feeds is NaN at the end of the unit; one NaN test on the unit's result, a
+//   workgroup-wide verdict, and a unit that raised the alarm runs once more from its first chunk on the class-safe
+//   planes (the class rule of bf16_split.h on every group) before anything is committed.  A unit with a non-finite
+//   value in its K-range of its 256 columns therefore costs twice; the rule assumes normal fp32 partners: Inf times
+//   a subnormal below 2^-133 gives NaN, not Inf.  Planes of values below ~2^-103 turn
 //   subnormal and lose bits; the host's magnitude guard rescales such data before it gets here.  K3, K3s, the 32- to
 //   112-row tiles and the small-n Gram stay on the fp32 MFMA; DMDX_K1_ARITH=f32 keeps K1 there too.
 //
@@ -60,6 +64,7 @@
 #include <stdlib.h>
 
 #include <algorithm>
+#include <type_traits>
 #include <vector>
 
 #include "bf16_split.h"
@@ -222,7 +227,7 @@ __device__ __forceinline__ int lane_now() {
 //   tile that would be padding for the rest.
 // One work unit: the K-range of `split` of the TM x 128 output tile at (row0, col0) (D rows <-
 // columns of A, D cols <- columns of B), written as fp64 into the partial tile Pt.
-// lds: 2 stages of (TM + 128) x 32 floats.
+// lds: 2 stages of (TM + 128) x 32 floats (PL: and what syrk_batch_kernel adds behind them).
 // H16 (round 3): one more 16-row block below the SK 32-row blocks, on v_mfma_f32_16x16x4_f32 (same flop
 //   rate, half the rows): tile heights 48 / 80 / 112, so that l = 70 columns of Y (BASELINE config 4:
 //   rank 50 + 20 oversamples) run 80 rows instead of 96.  Its fragments are 16-byte reads, one per operand
@@ -235,12 +240,15 @@ __device__ __forceinline__ int lane_now() {
 //   the k-steps 2g and 2g + 1 (k = 16g + 4h + e and 16g + 8 + 4h + e, the same on both operands); every
 //   value is split into three bf16 planes (bf16_split.h) and the six products h h, h' m, m h', h' l, m m,
 //   l h' of a 32 x 32 block go as v_mfma_f32_32x32x16_bf16 into the same `acc` (its 16-register layout is
-//   that of the fp32 instruction).  Non-finite input: a running fma(x, 0, s) per group, one unordered
-//   compare, and a wave-uniform branch to the class-safe split; both give the same planes on finite values.
+//   that of the fp32 instruction).  Non-finite input: nothing in the loop.  The chunk loop is instantiated twice, one
+//   pass behind the other (plane_pass): the fast pass, then -- if any lane of the workgroup finds a NaN in its 64
+//   values of acc + acc2 (a ballot per wave, one LDS word behind the stages, one barrier) -- the same unit again with
+//   make_safe2 on every pair and sanitise2 between h h and the cross products; both give the same planes on finite
+//   values, so outputs that no non-finite value feeds come out of the rerun as from a clean run.
 //   Everything outside the k-step (staging, barrier, refill order, fold, commit) is that of the fp32 body.
-//   ABL 16 (timing only): no detector and no slow path.
+//   (The former ablation ABL 16, the loop without its per-group detector, is what the product now runs.)
 template <bool DMA, int ABL, int SK, int H16 = 0, int PL = 0>
-__device__ __forceinline__ void tn_unit(const TnParams& p, const int split, const int row0, const int col0,
+__device__ __forceinline__ void tn_unit(const TnParams& p, const int split, const int row0_, const int col0_,
                                         double* Pt, float* lds) {
   static_assert(!H16 || SK >= 1, "a 16-row block only below at least one 32-row block");
   static_assert(!PL || (SK == 0 && H16 == 0), "the plane k-step is built for the 128 x 128 tile only");
@@ -248,6 +256,9 @@ __device__ __forceinline__ void tn_unit(const TnParams& p, const int split, cons
   unsigned long long pt0;
   asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(pt0)::"memory");
 #endif
+  // (plane k-step: the tile origin is wave-uniform, but the compiler carries it, and the panel bases made of it, in
+  // vector registers past the tile decode's loops; it has none to spare)
+  const int row0 = PL ? __builtin_amdgcn_readfirstlane(row0_) : row0_, col0 = PL ? __builtin_amdgcn_readfirstlane(col0_) : col0_;
   constexpr int TM = SK ? 32 * SK + 16 * H16 : BT;  // tile rows    (columns of OpA)
   constexpr int MI = SK ? SK : 2;        // 32-row MFMA blocks per wave
   constexpr int NI = SK ? 1 : 2;         // 32-column MFMA blocks per wave
@@ -560,6 +571,10 @@ __device__ __forceinline__ void tn_unit(const TnParams& p, const int split, cons
   // Measured on cfg2 blocks: barrier after k-step 3 + refill before it 85.6 %, this order
   // 87.4 %; pieces issued between the MFMAs of k-step 3 81 %; s_setprio 3 around the
   // refill 68 %.
+  // (plane k-step: the workgroup's alarm word, behind the stages and the parked DMA offsets; cleared ahead of the
+  // first barrier, raised and read once at the end of the unit)
+  int* const alarm_word = reinterpret_cast<int*>(lds + 2 * STG + (DMA ? 8 * NTH : 0));
+  if constexpr (PL != 0) *alarm_word = 0;
   stage(c_begin, 0);
   if (nchunks > 1 && !(ABL & 1)) stage(c_begin + 1, 1);
   if (DMA) __builtin_amdgcn_s_waitcnt(0x0f70);  // vmcnt(0), see the main loop
@@ -596,12 +611,14 @@ __device__ __forceinline__ void tn_unit(const TnParams& p, const int split, cons
   if constexpr (PL != 0) {
     // ---- plane k-step.  Blocks 0, 1: the A fragments (mi), 2, 3: the B fragments (ni).  One raw set: fa0 / fb0
     // hold the piece of k-step 2g, fa1 / fb1 that of k-step 2g + 1; the next group's pieces are read once the
-    // planes (and the detector's verdict) of this one are there, and land behind its 24 MFMAs.
+    // planes of this one are there, and land behind its 24 MFMAs.
+    // SAFE (the rerun of a unit whose fast pass ended with a NaN, see below): the class rule of bf16_split.h on every
+    // group -- make_safe2 on the fresh planes, sanitise2 on PH between h h and the cross products.  Both are the
+    // identity on finite values.
     unsigned PH[4][4], PM[4][4], PLo[4][4];
-#define DMDX_SPLIT_GROUP(g)                                                                      \
+#define DMDX_SPLIT_GROUP()                                                                       \
   do {                                                                                           \
     __builtin_amdgcn_sched_barrier(0);  /* not among the MFMAs before it: two plane sets do not fit */ \
-    bf16split::f32x2_t d_ = {0.f, 0.f};                                                          \
     _Pragma("unroll") for (int b_ = 0; b_ < 4; ++b_) {                                           \
       const f32x4 e_ = b_ < 2 ? fa0[b_ & 1] : fb0[b_ & 1], o_ = b_ < 2 ? fa1[b_ & 1] : fb1[b_ & 1]; \
       _Pragma("unroll") for (int q_ = 0; q_ < 4; ++q_) {                                         \
@@ -609,28 +626,8 @@ __device__ __forceinline__ void tn_unit(const TnParams& p, const int split, cons
                                              : bf16split::f32x2_t{o_[2 * (q_ & 1)], o_[2 * (q_ & 1) + 1]}; \
         unsigned h_, m_, l_;                                                                     \
         bf16split::split2_fast_pair(x_, h_, m_, l_);                                             \
+        if constexpr (SAFE) bf16split::make_safe2(x_[0], x_[1], h_, m_, l_);                     \
         PH[b_][q_] = h_; PM[b_][q_] = m_; PLo[b_][q_] = l_;                                      \
-        if (!(ABL & 16)) d_ = bf16split::detect_pair(x_, d_);                                    \
-      }                                                                                          \
-    }                                                                                            \
-    bad = !(ABL & 16) && __builtin_amdgcn_ballot_w64(__builtin_isunordered(d_[0], d_[1])) != 0ull;   \
-    if (bad) {  /* rare, wave-uniform: the pieces once more, block by block (the scheduling barriers keep its */ \
-      /* register need below that of the fast path), and the class rule applied to the planes in place        */ \
-      _Pragma("unroll") for (int b_ = 0; b_ < 4; ++b_) {                                         \
-        const float* s_ = lds + cur * STG + (b_ < 2 ? frag_a : OPA + frag_b) + (b_ & 1) * 32 * BK; \
-        __builtin_amdgcn_sched_barrier(0);                                                       \
-        int f0_ = foff[0];                                                                       \
-        asm volatile("" : "+v"(f0_));  /* (derived here, see DMDX_GROUP_MFMA) */                  \
-        const f32x4 e_ = *reinterpret_cast<const f32x4*>(s_ + (f0_ ^ (8 * (2 * (g)))));          \
-        const f32x4 o_ = *reinterpret_cast<const f32x4*>(s_ + (f0_ ^ (8 * (2 * (g) + 1))));      \
-        _Pragma("unroll") for (int q_ = 0; q_ < 4; ++q_) {                                       \
-          const float x0_ = q_ < 2 ? e_[2 * (q_ & 1)] : o_[2 * (q_ & 1)];                        \
-          const float x1_ = q_ < 2 ? e_[2 * (q_ & 1) + 1] : o_[2 * (q_ & 1) + 1];                \
-          unsigned h_ = PH[b_][q_], m_ = PM[b_][q_], l_ = PLo[b_][q_];                           \
-          bf16split::make_safe2(x0_, x1_, h_, m_, l_);                                           \
-          PH[b_][q_] = h_; PM[b_][q_] = m_; PLo[b_][q_] = l_;                                    \
-        }                                                                                        \
-        __builtin_amdgcn_sched_barrier(0);                                                       \
       }                                                                                          \
     }                                                                                            \
   } while (0)
@@ -641,7 +638,7 @@ __device__ __forceinline__ void tn_unit(const TnParams& p, const int split, cons
         _Pragma("unroll") for (int ni_ = 0; ni_ < 2; ++ni_) acc[mi_][ni_] =                      \
             __builtin_amdgcn_mfma_f32_32x32x16_bf16(DMDX_PLANE(PA, mi_), DMDX_PLANE(PB, 2 + ni_), acc[mi_][ni_], 0, 0, 0); \
   } while (0)
-    // The 24 MFMAs of a group.  h h sees the raw h, the cross products the copy with 0 in place of a non-finite
+    // The 24 MFMAs of a group.  SAFE: h h sees the raw h, the cross products the copy with 0 in place of a non-finite
     // value (PH in place).  The l products come first: their registers take the B pieces of the next group
     // (rd: read the pieces of k-steps t0, t0 + 1 of stage st for it -- the A pieces up front).
 #define DMDX_GROUP_MFMA(rd, st, t0, fresh)                                                            \
@@ -650,7 +647,7 @@ __device__ __forceinline__ void tn_unit(const TnParams& p, const int split, cons
     int f0_ = foff[0];                                                                           \
     asm volatile("" : "+v"(f0_));                                                                \
     const int fe_ = f0_ ^ (8 * (t0)), fo_ = f0_ ^ (8 * ((t0) + 1));                              \
-    if (rd) {                                                                                    \
+    if (rd && !SAFE) {                                                                           \
       const float* as_ = lds + (st) * STG + frag_a;                                              \
       fa0[0] = *reinterpret_cast<const f32x4*>(as_ + fe_);                                       \
       fa0[1] = *reinterpret_cast<const f32x4*>(as_ + fe_ + 32 * BK);                             \
@@ -664,9 +661,21 @@ __device__ __forceinline__ void tn_unit(const TnParams& p, const int split, cons
     } else {                                                                                     \
       DMDX_MFMA_PL(PH, PH);                                                                      \
     }                                                                                            \
-    if (bad) {                                                                                   \
+    if constexpr (SAFE) {  /* (between scheduling barriers: the rule's temporaries not next to anything in flight) */ \
+      __builtin_amdgcn_sched_barrier(0);                                                         \
       _Pragma("unroll") for (int b_ = 0; b_ < 4; ++b_)                                           \
-          _Pragma("unroll") for (int q_ = 0; q_ < 4; ++q_) PH[b_][q_] = bf16split::sanitise2(PH[b_][q_]); \
+          _Pragma("unroll") for (int q_ = 0; q_ < 4; ++q_) {                                     \
+            asm volatile("" : "+v"(PH[b_][q_]));  /* (the mask derived HERE: make_safe2's copy is not kept over the h h products) */ \
+            PH[b_][q_] = bf16split::sanitise2(PH[b_][q_]);                                       \
+          }                                                                                      \
+      __builtin_amdgcn_sched_barrier(0);                                                         \
+      if (rd) {  /* (the A pieces behind the rule, not next to its temporaries) */                \
+        const float* as_ = lds + (st) * STG + frag_a;                                            \
+        fa0[0] = *reinterpret_cast<const f32x4*>(as_ + fe_);                                     \
+        fa0[1] = *reinterpret_cast<const f32x4*>(as_ + fe_ + 32 * BK);                           \
+        fa1[0] = *reinterpret_cast<const f32x4*>(as_ + fo_);                                     \
+        fa1[1] = *reinterpret_cast<const f32x4*>(as_ + fo_ + 32 * BK);                           \
+      }                                                                                          \
     }                                                                                            \
     DMDX_MFMA_PL(PH, PLo);                                                                       \
     DMDX_MFMA_PL(PLo, PH);                                                                       \
@@ -682,7 +691,6 @@ __device__ __forceinline__ void tn_unit(const TnParams& p, const int split, cons
     DMDX_MFMA_PL(PM, PH);                                                                        \
     DMDX_MFMA_PL(PM, PM);                                                                        \
   } while (0)
-    bool bad = false;
     DMDX_READ_FRAGS(fa1, fb1, 0, 1);
     // The DMA byte offsets do not fit into the registers next to the planes: every thread parks its eight in LDS
     // behind the stages (its own 32 bytes: no synchronisation) and reads them back ahead of every refill.
@@ -691,40 +699,96 @@ __device__ __forceinline__ void tn_unit(const TnParams& p, const int split, cons
       park[0] = u32x4{aoffb[0], aoffb[1], aoffb[2], aoffb[3]};
       park[1] = u32x4{boffb[0], boffb[1], boffb[2], boffb[3]};
     }
-    for (int c = 0; c < nchunks; ++c) {
-      DMDX_STAMP(st0);
-      const bool has_next = (c + 1 < nchunks) && !(ABL & 1);
-      DMDX_STAMP(st1);
-      DMDX_SPLIT_GROUP(0);
-      DMDX_GROUP_MFMA(true, cur, 2, true);
-      DMDX_SPLIT_GROUP(1);
-      DMDX_STAMP(st2);
+    // One pass over the unit's chunks, from both stages filled and the first group's pieces in fa0 / fb0 / fa1 / fb1.
+    // Two instantiations, one behind the other: the fast pass holds no trace of the class rule.
+    auto plane_pass = [&](auto safe_) __attribute__((always_inline)) {
+      constexpr bool SAFE = decltype(safe_)::value;
+      for (int c = 0; c < nchunks; ++c) {
+        DMDX_STAMP(st0);
+        const bool has_next = (c + 1 < nchunks) && !(ABL & 1);
+        DMDX_STAMP(st1);
+        DMDX_SPLIT_GROUP();
+        DMDX_GROUP_MFMA(true, cur, 2, true);
+        DMDX_SPLIT_GROUP();
+        DMDX_STAMP(st2);
+        unsigned pa[NPA] = {0u, 0u, 0u, 0u}, pb[4] = {0u, 0u, 0u, 0u};
+        if (DMA && c + 2 < nchunks) {
+          const u32x4* park = reinterpret_cast<const u32x4*>(lds + 2 * STG) + 2 * (64 * wave + lane_now());
+          const u32x4 a_ = park[0], b_ = park[1];
+          pa[0] = a_[0]; pa[1] = a_[1]; pa[2] = a_[2]; pa[3] = a_[3];
+          pb[0] = b_[0]; pb[1] = b_[1]; pb[2] = b_[2]; pb[3] = b_[3];
+        }
+
+        if (DMA) __builtin_amdgcn_s_waitcnt(0x0f70);  // vmcnt(0): the asm LDS-DMA pieces are invisible to the compiler's counters
+        DMDX_STAMP(st2b);
+        if (!(ABL & 2)) __syncthreads();
+        if (c + 2 < nchunks && !(ABL & 1)) stage_with(c_begin + c + 2, cur, pa, pb);
+        cur ^= 1;
+        DMDX_STAMP(st3);
+        DMDX_GROUP_MFMA(has_next, cur, 0, false);
+        // The bf16 MFMA truncates its sum a few bits below the fp32 ulp of the accumulator (measured: a one-signed
+        // 6e-7 on the diagonal of a Gram with 1312-row chains, growing with the chain), so the plane body keeps its
+        // MFMA chains to ONE chunk: every chunk's 32-row result is added into acc2 by rounded fp32 adds (32 packed
+        // adds per chunk) and the next chunk starts from zero.  acc2 then sums at most 2048 chunk results.
+        if (!(ABL & 8)) {
+          DMDX_FOLD(0, 0); DMDX_FOLD(0, NI - 1); DMDX_FOLD(MI - 1, 0); DMDX_FOLD(MI - 1, NI - 1);
+        }
+#ifdef DMDX_STAMPS
+        DMDX_STAMP(st4);
+        sa0 += st1 - st0; sa1 += st2 - st1; sa2 += st3 - st2b; sa3 += st4 - st3; sa5 += st2b - st2;
+#endif
+      }
+    };
+    plane_pass(std::false_type{});
+    // ---- the verdict, once per unit.  The fast planes of an Inf or NaN carry a NaN in l (Inf - Inf), and l h' and
+    // h' l are contracted for every pair: every output that a non-finite input of this K-range feeds holds NaN by
+    // now, whatever its partners were (NaN * 0 included), and the fold kept it.  No NaN in acc + acc2: the fast
+    // result is the result.  A NaN: the whole workgroup (the four waves share stages and barriers; an A-panel value
+    // poisons two of them only) runs the unit again on class-safe planes and commits that.  Nothing has been written
+    // to Pt so far.  Finite input that overflows to Inf - Inf raises the alarm too and gets the same classes again.
+    bool nan_ = false;
+#pragma unroll
+    for (int mi = 0; mi < MI; ++mi)
+#pragma unroll
+      for (int ni = 0; ni < NI; ++ni)
+#pragma unroll
+        for (int r = 0; r < 16; ++r) nan_ |= bf16split::alarm(acc[mi][ni][r] + acc2[mi][ni][r]);
+    if (__builtin_amdgcn_ballot_w64(nan_) != 0ull) *alarm_word = 1;
+    __syncthreads();   // (also: every wave is done with the stages of the fast pass)
+    if (__builtin_amdgcn_readfirstlane(*alarm_word) != 0) {
+#pragma unroll
+      for (int mi = 0; mi < MI; ++mi)
+#pragma unroll
+        for (int ni = 0; ni < NI; ++ni)
+#pragma unroll
+          for (int r = 0; r < 16; ++r) acc[mi][ni][r] = acc2[mi][ni][r] = 0.f;
       unsigned pa[NPA] = {0u, 0u, 0u, 0u}, pb[4] = {0u, 0u, 0u, 0u};
-      if (DMA && c + 2 < nchunks) {
+      if (DMA) {
         const u32x4* park = reinterpret_cast<const u32x4*>(lds + 2 * STG) + 2 * (64 * wave + lane_now());
         const u32x4 a_ = park[0], b_ = park[1];
         pa[0] = a_[0]; pa[1] = a_[1]; pa[2] = a_[2]; pa[3] = a_[3];
         pb[0] = b_[0]; pb[1] = b_[1]; pb[2] = b_[2]; pb[3] = b_[3];
       }
-
-      if (DMA) __builtin_amdgcn_s_waitcnt(0x0f70);  // vmcnt(0): the asm LDS-DMA pieces are invisible to the compiler's counters
-      DMDX_STAMP(st2b);
-      if (!(ABL & 2)) __syncthreads();
-      if (c + 2 < nchunks && !(ABL & 1)) stage_with(c_begin + c + 2, cur, pa, pb);
-      cur ^= 1;
-      DMDX_STAMP(st3);
-      DMDX_GROUP_MFMA(has_next, cur, 0, false);
-      // The bf16 MFMA truncates its sum a few bits below the fp32 ulp of the accumulator (measured: a one-signed
-      // 6e-7 on the diagonal of a Gram with 1312-row chains, growing with the chain), so the plane body keeps its
-      // MFMA chains to ONE chunk: every chunk's 32-row result is added into acc2 by rounded fp32 adds (32 packed
-      // adds per chunk) and the next chunk starts from zero.  acc2 then sums at most 2048 chunk results.
-      if (!(ABL & 8)) {
-        DMDX_FOLD(0, 0); DMDX_FOLD(0, NI - 1); DMDX_FOLD(MI - 1, 0); DMDX_FOLD(MI - 1, NI - 1);
+      cur = 0;
+      stage_with(c_begin, 0, pa, pb);
+      if (nchunks > 1 && !(ABL & 1)) stage_with(c_begin + 1, 1, pa, pb);
+      if (DMA) __builtin_amdgcn_s_waitcnt(0x0f70);
+      __syncthreads();
+      {  // the first group's pieces, as DMDX_READ_FRAGS reads them for k-steps 0 and 1 (foff[1] = foff[0] ^ 8)
+        int f0_ = foff[0];
+        asm volatile("" : "+v"(f0_));
+        const float* as_ = lds + frag_a;
+        const float* bs_ = lds + OPA + frag_b;
+        fa0[0] = *reinterpret_cast<const f32x4*>(as_ + f0_);
+        fa0[1] = *reinterpret_cast<const f32x4*>(as_ + f0_ + 32 * BK);
+        fa1[0] = *reinterpret_cast<const f32x4*>(as_ + (f0_ ^ 8));
+        fa1[1] = *reinterpret_cast<const f32x4*>(as_ + (f0_ ^ 8) + 32 * BK);
+        fb0[0] = *reinterpret_cast<const f32x4*>(bs_ + f0_);
+        fb0[1] = *reinterpret_cast<const f32x4*>(bs_ + f0_ + 32 * BK);
+        fb1[0] = *reinterpret_cast<const f32x4*>(bs_ + (f0_ ^ 8));
+        fb1[1] = *reinterpret_cast<const f32x4*>(bs_ + (f0_ ^ 8) + 32 * BK);
       }
-#ifdef DMDX_STAMPS
-      DMDX_STAMP(st4);
-      sa0 += st1 - st0; sa1 += st2 - st1; sa2 += st3 - st2b; sa3 += st4 - st3; sa5 += st2b - st2;
-#endif
+      plane_pass(std::true_type{});
     }
     {  // (no register held across the loop for the commit)
       lane_off_c = lane_off_of(lane_now());
@@ -842,8 +906,9 @@ __device__ __forceinline__ int xcd_unit(int b, int total) {
 template <bool DMA, int SK = 0, int H16 = 0, int PL = 0>
 __global__ __launch_bounds__(NTH, 2) void syrk_batch_kernel(TnParams p, TnBatch bt) {
   constexpr int TM = SK ? 32 * SK + 16 * H16 : BT;
-  // (plane k-step on the LDS-DMA path: + 32 bytes per thread for its parked DMA offsets; 72 KiB, two workgroups per CU)
-  __shared__ __attribute__((aligned(16))) float lds[2 * (TM + BT) * BK + (PL && DMA ? 8 * NTH : 0)];
+  // (plane k-step: + 32 bytes per thread for the parked DMA offsets of the LDS-DMA path, + 16 bytes for the alarm word
+  // of the unit's verdict; 72 KiB + 16 bytes, two workgroups per CU)
+  __shared__ __attribute__((aligned(16))) float lds[2 * (TM + BT) * BK + (PL && DMA ? 8 * NTH : 0) + (PL ? 4 : 0)];
   const int b = blockIdx.x;
   int j = 0;
   while (j + 1 < bt.nblocks && b >= bt.unit_begin[j + 1]) ++j;
