@@ -1109,6 +1109,62 @@ class HipKernels:
         _lib.check(rc, "dmdx_coarsen_f32")
         return Yt
 
+    # -- K28 ----------------------------------------------------------------
+    @property
+    def remap_max_span(self) -> int:
+        return int(self._lib.dmdx_remap_max_span())
+
+    def remap(self, Xt: torch.Tensor, planes: int, nlat: int, nlon: int, iy0: torch.Tensor, ny: torch.Tensor,
+              wy: torch.Tensor, jx0: torch.Tensor, nx: torch.Tensor, wx: torch.Tensor, *, ldp: int | None = None,
+              skipna: bool = False, min_frac: float = 0.0, out: torch.Tensor | None = None,
+              ldq: int | None = None) -> torch.Tensor:
+        """First-order conservative remapping onto another regular latitude / longitude grid, separable in the two
+        axes.  Xt: (T, m) fp32 (any row stride), every snapshot ``planes`` planes of ``nlat x nlon`` points, plane p
+        at ``p * ldp`` (default ``nlat * nlon``; rows beyond the last plane are pad and are not read).  The six
+        tables are contiguous on the device: ``iy0``, ``ny`` (NLAT,) int32 and ``wy`` (NLAT, SY) fp64 -- target row
+        I overlaps the ``ny[I]`` source rows from ``iy0[I]`` on with the weights ``wy[I, :ny[I]]`` -- and ``jx0``,
+        ``nx`` (NLON,) int32 and ``wx`` (NLON, SX) fp64, the source columns ``(jx0[J] + b) mod nlon`` -> Yt (T,
+        rows_out) fp32, ``rows_out = (planes - 1) ldq + NLAT NLON``, plane p at ``p * ldq`` (default ``NLAT * NLON``),
+        cell (I, J) at ``I * NLON + J``: the weighted mean of what the cell overlaps, an fp64 chain in ascending order
+        with one rounding to fp32 (include/dmdx.h, K28).  ``skipna``: values that are not finite are left out of a
+        cell, and a cell whose kept weight is below ``min_frac`` of its full weight is NaN.  ``out``: a (T, rows_out)
+        fp32 view that does not overlap Xt (inner stride 1).  ``regrid.Remap`` forms the tables."""
+        planes, nlat, nlon = int(planes), int(nlat), int(nlon)
+        if min(planes, nlat, nlon) < 0:
+            raise _lib.DmdxError("remap: a negative size")
+        for name, t in (("iy0", iy0), ("ny", ny), ("wy", wy), ("jx0", jx0), ("nx", nx), ("wx", wx)):
+            if not isinstance(t, torch.Tensor):
+                raise _lib.DmdxError(f"remap: {name} must be a device tensor")
+        if wy.dim() != 2 or wx.dim() != 2:
+            raise _lib.DmdxError(f"remap: wy must be (NLAT, SY) and wx (NLON, SX), got {tuple(wy.shape)} and {tuple(wx.shape)}")
+        (NLAT, SY), (NLON, SX) = (int(v) for v in wy.shape), (int(v) for v in wx.shape)
+        smax = self.remap_max_span
+        if not (1 <= SY <= smax and 1 <= SX <= smax):
+            raise _lib.DmdxError(f"remap: SY = {SY} or SX = {SX} outside 1..{smax}")
+        ldp = nlat * nlon if ldp is None else int(ldp)
+        ldq = NLAT * NLON if ldq is None else int(ldq)
+        if ldp < nlat * nlon or ldq < NLAT * NLON:
+            raise _lib.DmdxError(f"remap: ldp = {ldp} < nlat nlon or ldq = {ldq} < NLAT NLON")
+        m, T = (int(Xt.shape[1]), int(Xt.shape[0])) if Xt.dim() == 2 else (-1, -1)
+        ldx = _check_snapshots(Xt, m, T, Xt.device, "remap")
+        need = (planes - 1) * ldp + nlat * nlon if planes else 0
+        if m < need:
+            raise _lib.DmdxError(f"remap: X holds {m} rows, {planes} planes of {nlat} x {nlon} (ldp = {ldp}) need {need}")
+        _check_ivec(iy0, Xt.device, "remap", "iy0", NLAT)
+        _check_ivec(ny, Xt.device, "remap", "ny", NLAT)
+        _check_ivec(jx0, Xt.device, "remap", "jx0", NLON)
+        _check_ivec(nx, Xt.device, "remap", "nx", NLON)
+        _accumulator(wy, (NLAT, SY), torch.float64, Xt.device, "remap", "wy")
+        _accumulator(wx, (NLON, SX), torch.float64, Xt.device, "remap", "wx")
+        rows_out = (planes - 1) * ldq + NLAT * NLON if planes else 0
+        Yt, ldy = _out_view(out, rows_out, T, torch.float32, Xt.device, "remap")
+        rc = self._timed("remap", (planes, nlat, nlon, T, NLAT, NLON), lambda: self._lib.dmdx_remap_f32(
+            _ptr(Xt), T, ldx, planes, ldp, nlat, nlon, _ptr(iy0), _ptr(ny), _ptr(wy), SY, _ptr(jx0), _ptr(nx), _ptr(wx), SX,
+            NLAT, NLON, int(bool(skipna)), float(min_frac), _ptr(Yt), ldy, ldq, self._stream()
+        ))
+        _lib.check(rc, "dmdx_remap_f32")
+        return Yt
+
     # -- K20 ----------------------------------------------------------------
     def row_missing_count(self, Xt: torch.Tensor, out: torch.Tensor | None = None) -> torch.Tensor:
         """How many snapshots of every row of a block are not finite (NaN of any payload, +-Inf; tested on the

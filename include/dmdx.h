@@ -959,6 +959,48 @@ int dmdx_coarsen_f32(const float* X, int64_t T, int64_t ldx, int64_t P, int64_t 
                      const double* w, int fy, int fx, int64_t lat0, int64_t lon0, int64_t NLAT, int64_t NLON, int skipna,
                      double min_frac, float* Y, int64_t ldy, int64_t ldq, void* stream);
 
+/* ---- K28: first-order conservative remapping onto another regular latitude / longitude grid ---------------------------
+ * K23 takes whole fy x fx blocks.  The grids other data sets live on (1 degree with the poles, 181 x 360; 1.5 degrees,
+ * 121 x 240; 5.625 degrees, offset by half a cell) cut source cells, wrap around in longitude and end in a clipped cap at
+ * the poles.  Both grids are regular, so the remapping is separable: six device tables say what a target cell is made of.
+ * X and Y are laid out exactly as in K23: snapshot t at X + t ldx, plane p at p ldp, ldp >= nlat nlon, the slack is pad
+ * and is never read; Y[t ldy + p ldq + I NLON + J], ldq >= NLAT NLON.  Target row I overlaps the ny[I] source rows from
+ * iy0[I] on, with the weights wy[I SY + a] (NLAT x SY doubles, row-major: the area of the overlap of the two latitude
+ * bands); target column J overlaps the nx[J] source columns (jx0[J] + b) mod nlon, with the weights wx[J SX + b]
+ * (NLON x SX doubles: the overlap in degrees).  Entries of wy and wx beyond the count are never read.  The host forms
+ * the tables in fp64 (regrid.Remap).  Per snapshot t, plane p, cell (I, J):
+ *     num = +0.0; den = +0.0; full = +0.0
+ *     for a = 0 .. ny[I] - 1 ascending, i = iy0[I] + a:
+ *         r = +0.0; c = +0.0; f = +0.0
+ *         for b = 0 .. nx[J] - 1 ascending, j = (jx0[J] + b) mod nlon, u = wx[J][b], x = X[t, p, i, j]:
+ *             if (!skipna || finite(x)) { r = r + u * fp64(x); c = c + u; }
+ *             f = f + u
+ *         num = num + wy[I][a] * r; den = den + wy[I][a] * c; full = full + wy[I][a] * f;   (products rounded, then the sums)
+ *     Y = (den == 0 || den < min_frac * full) ? quiet NaN (0x7fc00000) : fp32(num / den)
+ * all in fp64, every product rounded on its own, never an FMA, one rounding to fp32.  finite(x) is K20's test of the bit
+ * pattern.  With wx == 1.0 and wy[I][a] = w[lat0 + I fy + a] this is K23's contract term for term: block tables give the
+ * bits of dmdx_coarsen_f32.  A cell is formed by one lane; no atomics, no workspace, no allocation, no synchronisation:
+ * the launch geometry is not part of the result.  So a constant field comes out constant bit for bit, 2^e X gives 2^e Y,
+ * and a cell of zeros of either sign gives +0.0.
+ * Memory: the contents of the tables live on the device and cannot be checked here, so the kernel is safe for any
+ * contents: counts are clamped to 0 .. SY and 0 .. SX, row indices into [0, nlat), column indices are reduced modulo
+ * nlon.  A bad table gives a wrong number and never an access outside the planes of X; plane pads and the slack of ldx
+ * are never read, and only the logical P NLAT NLON x T elements of Y are written.  No alignment is asked for beyond that
+ * of the element types: with SX <= 8 a lane reads its run of a source row as the aligned quads of that row that cover it
+ * (16-byte loads; floats of the row beside the run are loaded and not used) where the run does not wrap and the address
+ * of the row allows it, and element by element otherwise and for every wider SX.  All give the same bits.
+ * A refused call (DMDX_E_INVALID: a null X, Y or table; a negative size; SY or SX outside 1 .. dmdx_remap_max_span() (64);
+ * cells of an empty plane (NLAT NLON > 0 with nlat nlon == 0); ldp < nlat nlon or ldq < NLAT NLON; ldx < (P - 1) ldp +
+ * nlat nlon or ldy < (P - 1) ldq + NLAT NLON; any size or leading dimension >= 2^31; an extent >= 2^60 elements; min_frac
+ * outside [0, 1] or NaN; a pointer not aligned to its element; any overlap of the address ranges of X and Y: there is no
+ * in-place form) has written nothing and made no HIP call.  T, P, NLAT or NLON == 0 returns 0 after the checks without
+ * a launch. */
+int dmdx_remap_max_span(void);
+int dmdx_remap_f32(const float* X, int64_t T, int64_t ldx, int64_t P, int64_t ldp, int64_t nlat, int64_t nlon,
+                   const int32_t* iy0, const int32_t* ny, const double* wy, int SY, const int32_t* jx0, const int32_t* nx,
+                   const double* wx, int SX, int64_t NLAT, int64_t NLON, int skipna, double min_frac, float* Y, int64_t ldy,
+                   int64_t ldq, void* stream);
+
 /* ---- upper triangle of a symmetric fp64 matrix <-> packed row by row ---------------------
  * packed[i (2n - i + 1) / 2 + (j - i)] = A[i][j], j >= i: what the Gram all-reduce of the
  * row-sharded path moves (n (n + 1) / 2 doubles instead of n^2).  unpack writes both triangles. */
