@@ -118,6 +118,11 @@ SIGNATURES = {
     "dmdx_spell_workspace_bytes": (_sz, [_i64, _p, C.c_int, C.c_int, _i64]),
     "dmdx_spell_f32": (C.c_int, [_p, _i64, _i64, _i64, _p, _i64, C.c_int, _i64, _p, C.c_uint, _p, _p, C.c_int, _i64, _p,
                                  _i64, C.c_int, _p, _sz, _p]),
+    "dmdx_period_stats_max_window": (C.c_int, []),
+    "dmdx_period_stats_max_periods": (C.c_int, []),
+    "dmdx_period_stats_workspace_bytes": (_sz, [_i64, _p, C.c_int, _i64, _i64]),
+    "dmdx_period_stats_f32": (C.c_int, [_p, _i64, _i64, _i64, _p, C.c_int, _i64, C.c_int, C.c_int, _i64, _p, _i64, _p, _i64,
+                                        C.c_uint, _p, _sz, _p]),
     "dmdx_tfilt_max_taps": (C.c_int, []),
     "dmdx_tfilt_f32": (C.c_int, [_p, _i64, _i64, _i64, _p, _i64, _i64, _p, _i64, _i64, _p]),
     "dmdx_coarsen_max_factor": (C.c_int, []),

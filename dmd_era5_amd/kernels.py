@@ -80,6 +80,8 @@ def _out_view(out: torch.Tensor | None, m: int, T: int, dtype, device, who: str,
 
 _DTYPE_NAME = {torch.float64: "fp64", torch.int64: "int64", torch.int32: "int32"}
 DMDX_SPELL_NQ = 7                        # the planes of K27 (include/dmdx.h)
+DMDX_PSTAT_NQ = 8                        # the planes of K29
+PSTAT_INNER = ("sum", "mean", "max", "min", "range")      # DMDX_PSTAT_SUM .. DMDX_PSTAT_RANGE
 
 
 def _accumulator(out: torch.Tensor | None, shape: tuple, dtype, device, who: str, name: str = "out") -> torch.Tensor:
@@ -1031,6 +1033,73 @@ class HipKernels:
             _lib.check(rc, "dmdx_spell_f32")
             if part is not planes:
                 planes[:, :, p0:p0 + n] = part
+        return planes
+
+    # -- K29 ----------------------------------------------------------------
+    @property
+    def period_stats_max_window(self) -> int:
+        return int(self._lib.dmdx_period_stats_max_window())
+
+    @property
+    def period_stats_max_periods(self) -> int:
+        """The periods of one launch (their bounds travel by value); :meth:`period_stats` loops beyond."""
+        return int(self._lib.dmdx_period_stats_max_periods())
+
+    def period_stats(self, Xt: torch.Tensor, bounds, group: int = 1, inner: str = "sum", window: int = 1,
+                     min_count: int | None = None, thr: torch.Tensor | None = None, below: bool = False,
+                     inclusive: bool = False, seg: int = 64, out: torch.Tensor | None = None) -> torch.Tensor:
+        """Extremes and totals of a daily statistic of every row of a block, per period.  Xt: (T, m) fp32 (any row
+        stride); ``bounds``: P + 1 strictly ascending integers in 0 .. T, period p is the snapshots [b_p, b_{p+1});
+        ``group``: the snapshots of a day, cut from the period's start; ``inner``: ``"sum"``, ``"mean"``, ``"max"``,
+        ``"min"`` or ``"range"`` of the finite snapshots of a day; ``min_count``: the finite snapshots a valid day
+        needs (None: all ``group``); ``window``: the days of the running sum, 1 .. ``period_stats_max_window``, never
+        across a period; ``thr``: (m,) fp32 thresholds or None; the event is r > thr, r < thr with ``below``, >= / <=
+        with ``inclusive`` -> (8, P, m) fp64: n, max, argmax, min, argmin, total, event total, event count
+        (include/dmdx.h, K29).
+
+        ``seg``: the days of a piece of the time split; part of the totals (planes 5 and 6) and of nothing else
+        (:data:`extremes.SEGMENT`).  Time is split over workgroups whenever there is more than one piece; any number
+        of periods runs in launches of ``period_stats_max_periods``.  ``out``: a contiguous (8, P, m) fp64 tensor to
+        write into."""
+        who = "period_stats"
+        if Xt.dim() != 2:
+            raise _lib.DmdxError(f"{who}: X must be (T, m), got {tuple(Xt.shape)}")
+        T, m = int(Xt.shape[0]), int(Xt.shape[1])
+        ldx = _check_snapshots(Xt, m, T, Xt.device, who)
+        _check_vec(thr, m, Xt.device, who, "thr")
+        b = [int(v) for v in np.asarray(bounds).reshape(-1)]
+        # here and not only in C: the int32 array below would wrap what does not fit it
+        if len(b) < 2 or b[0] < 0 or b[-1] > T or any(y <= x for x, y in zip(b, b[1:])):
+            raise _lib.DmdxError(f"{who}: bounds must be at least 2 strictly ascending integers in 0 .. T = {T}")
+        if inner not in PSTAT_INNER:
+            raise _lib.DmdxError(f"{who}: inner = {inner!r}, expected one of {PSTAT_INNER}")
+        g, w, seg = int(group), int(window), int(seg)
+        mc = g if min_count is None else int(min_count)
+        if not (1 <= g < 2**31 and 1 <= w <= self.period_stats_max_window and 1 <= mc <= g and 1 <= seg < 2**31):
+            raise _lib.DmdxError(f"{who}: group >= 1, window in 1 .. {self.period_stats_max_window}, min_count in 1 .. group "
+                                 f"and seg >= 1 asked for (group = {group}, window = {window}, min_count = {min_count}, "
+                                 f"seg = {seg})")
+        P = len(b) - 1
+        planes = _accumulator(out, (DMDX_PSTAT_NQ, P, m), torch.float64, Xt.device, who)
+        if m == 0:
+            return planes
+        flags = (1 if below else 0) | (2 if inclusive else 0)
+        maxp = self.period_stats_max_periods
+        for p0 in range(0, P, maxp):
+            n = min(maxp, P - p0)
+            part = planes if n == P else torch.empty((DMDX_PSTAT_NQ, n, m), dtype=torch.float64, device=Xt.device)
+            host_b = (ctypes.c_int32 * (n + 1))(*b[p0:p0 + n + 1])
+            pieces = sum(-(-(-(-(y - x) // g)) // seg) for x, y in zip(b[p0:p0 + n], b[p0 + 1:p0 + n + 1]))
+            split = pieces > 1
+            nbytes = int(self._lib.dmdx_period_stats_workspace_bytes(m, host_b, n, g, seg)) if split else 0
+            ws = self._workspace(Xt.device, nbytes) if split else None
+            rc = self._timed("period_stats", (m, b[p0 + n] - b[p0], g, w, n), lambda: self._lib.dmdx_period_stats_f32(
+                _ptr(Xt), m, T, ldx, host_b, n, g, PSTAT_INNER.index(inner), w, mc, _ptr(thr), seg, _ptr(part), m, flags,
+                _ptr(ws), nbytes, self._stream()
+            ))
+            _lib.check(rc, "dmdx_period_stats_f32")
+            if part is not planes:
+                planes[:, p0:p0 + n] = part
         return planes
 
     # -- K22 ----------------------------------------------------------------

@@ -889,6 +889,75 @@ int dmdx_spell_f32(const float* X, int64_t m, int64_t T, int64_t ldx, const floa
                    const int32_t* bounds /* host, P + 1 */, int P, int64_t seg, int32_t* out, int64_t ldo, int flags,
                    void* workspace /* nullable */, size_t workspace_bytes, void* stream);
 
+/* ---- K29: per-period extremes and totals of a daily statistic of every row of a row block ------------------------------
+ * The other half of the standard climate indices next to K27's counts: the hottest and the coldest day of a year and when
+ * they fell (TXx, TNn, TXn, TNx), the mean diurnal range (DTR), the wettest day and the wettest five days (Rx1day, Rx5day),
+ * totals and wet-day totals (PRCPTOT, SDII), the share of very wet days (R95pTOT), degree days.  X is a row block as
+ * everywhere: T columns (snapshots) of m floats, ldx >= m, only read.
+ *   bounds     (HOST int32) P + 1 values, 0 <= b_0 < b_1 < ... < b_P <= T, 1 <= P <= dmdx_period_stats_max_periods() =
+ *              DMDX_PSTAT_MAX_PERIODS (128; they travel by value, a caller with more periods makes several calls).
+ *              Period p is the snapshots [b_p, b_{p+1}); snapshots outside [b_0, b_P) are not read.
+ *   thr        (device fp32, nullable) one threshold per row.
+ * For row i and period p:
+ *   days   the period is cut from its own start into groups of `group` = g >= 1 snapshots: day k is [b_p + k g,
+ *          min(b_p + (k + 1) g, b_{p+1})), D_p = ceil((b_{p+1} - b_p) / g) days, the last one may be ragged.  A snapshot
+ *          counts if it is finite (K20's test of the bit pattern: NaN and +-Inf are missing); c_k is the number of finite
+ *          snapshots of day k, and the day is VALID iff c_k >= min_count, 1 <= min_count <= g (a ragged day shorter than
+ *          min_count is never valid).
+ *   d_k    the day value, fp64, from the finite snapshots of the day in ascending t:  s = +0.0; s = s + fp64(x)
+ *          (rounded, never an FMA);  hi = the first finite value, replaced when x > hi;  lo likewise when x < lo (strict:
+ *          a tie keeps the earlier value, -0.0 followed by +0.0 stays -0.0).  inner selects  SUM: s;  MEAN: s / fp64(c_k)
+ *          (one correctly rounded division);  MAX: fp64(hi);  MIN: fp64(lo);  RANGE: fp64(hi) - fp64(lo) (one rounded
+ *          subtraction).
+ *   r_k    the running sum over `window` = w days, 1 <= w <= dmdx_period_stats_max_window() = DMDX_PSTAT_MAX_WINDOW (8),
+ *          that never crosses a period: r_k exists for k >= w - 1 iff the days k - w + 1 .. k are all valid;
+ *          r = d_{k-w+1}, then r = r + d_u for u ascending -- recomputed for every k in that order, never a sliding
+ *          update, so it does not depend on where a piece starts.  w = 1: r_k = d_k, no operation.
+ *   e_k    the event: r_k exists, thr != NULL, h = thr[i] is not NaN, and r_k > fp64(h); r_k < fp64(h) with
+ *          DMDX_PSTAT_BELOW; >= / <= with DMDX_PSTAT_INCLUSIVE.  An infinite threshold is a threshold.
+ * The DMDX_PSTAT_NQ = 8 planes, fp64, at out[(q P + p) ldo + i], ldo >= m:
+ *   0 n            the number of existing r_k
+ *   1 max          the first r_k, replaced when r_k > max (strict); NaN when n = 0
+ *   2 argmax       the k of that value (the day of the period that is the window's last); -1 when n = 0
+ *   3 min          as plane 1, replaced when r_k < min           4 argmin   as plane 2
+ *   5 total        segsum(r_k over the existing k)
+ *   6 event total  segsum(r_k over e_k)                          7 event count   the number of e_k
+ * With thr == NULL planes 6 and 7 are +0.0.
+ * segsum is K26's, applied to days: the period is cut from its own start into pieces of `seg` >= 1 days; per piece in
+ * ascending order { acc = +0.0; acc = acc + v for its terms ascending; } tot = tot + acc, from tot = +0.0; pieces
+ * without a term are included.  The partition is part of planes 5 and 6 and of nothing else; the launch form is part of
+ * nothing: with `workspace` (dmdx_period_stats_workspace_bytes(m, bounds, P, group, seg) bytes = N 8 m doubles, N = sum_p
+ * ceil(D_p / seg), no initialisation needed) every piece is scanned by workgroups of its own -- it reads the up to
+ * (w - 1) g snapshots before its start inside its period again -- into a record per row, and a second kernel merges
+ * the records of a period in ascending order: a strict compare (the earlier piece wins a tie), counts added, tot + acc.
+ * With workspace == NULL one lane walks the periods of its rows.  Both give the same bits.  The walk has one workgroup
+ * row: pass the workspace whenever there is more than one piece on a full row block.
+ * No allocation, no synchronisation, no atomics.
+ * Memory: only the logical elements of X in [b_0, b_P) and of thr are read; only the logical 8 x P x m elements of out,
+ * every one of them, and the declared workspace bytes are written.  out and workspace are 8-byte aligned; X and thr need
+ * no alignment beyond their elements: a 16-byte aligned X with ldx % 4 == 0 is read with 16-byte loads (4 rows per lane,
+ * the ragged last quad element by element), anything else one dword per lane, with the same bits.
+ * A refused call (DMDX_E_INVALID: P outside 1 .. 128; null bounds; bounds not strictly ascending or outside [0, T];
+ * group < 1; inner outside 0 .. 4; window outside 1 .. 8; min_count outside 1 .. group; seg < 1; an undefined flag bit; a
+ * negative size; m, T, group, seg or a leading dimension >= 2^31; ldx or ldo < m; a pointer not aligned to its element;
+ * out overlapping X or thr; a workspace smaller than asked for; a null X or out with m > 0) has written nothing.  m == 0
+ * returns 0 after the checks without a launch.  dmdx_period_stats_workspace_bytes returns 0 for arguments the call
+ * would refuse. */
+#define DMDX_PSTAT_NQ 8
+#define DMDX_PSTAT_MAX_WINDOW 8
+#define DMDX_PSTAT_MAX_PERIODS 128
+enum { DMDX_PSTAT_SUM = 0, DMDX_PSTAT_MEAN = 1, DMDX_PSTAT_MAX = 2, DMDX_PSTAT_MIN = 3, DMDX_PSTAT_RANGE = 4 };
+#define DMDX_PSTAT_BELOW 1u       /* event: r < h instead of r > h */
+#define DMDX_PSTAT_INCLUSIVE 2u   /* >= / <= instead of the strict comparison */
+int dmdx_period_stats_max_window(void);
+int dmdx_period_stats_max_periods(void);
+size_t dmdx_period_stats_workspace_bytes(int64_t m, const int32_t* bounds /* host */, int P, int64_t group, int64_t seg);
+int dmdx_period_stats_f32(const float* X, int64_t m, int64_t T, int64_t ldx,
+                          const int32_t* bounds /* host, P + 1 */, int P, int64_t group, int inner, int window,
+                          int64_t min_count, const float* thr /* device, m, nullable */, int64_t seg,
+                          double* out, int64_t ldo, unsigned flags,
+                          void* workspace /* nullable */, size_t workspace_bytes, void* stream);
+
 /* ---- K22: a FIR filter along time with an output stride: daily means, low-pass + decimation, band-pass ----------------
  * The fourth preparation step on the device, before K18 and K21: a weighted sum over a sliding window of snapshots.  X
  * and Y are row blocks as everywhere: snapshot t of X at X + t ldx, output snapshot u of Y at Y + u ldy, m floats each,
