@@ -131,6 +131,10 @@ SIGNATURES = {
     "dmdx_remap_max_span": (C.c_int, []),
     "dmdx_remap_f32": (C.c_int, [_p, _i64, _i64, _i64, _i64, _i64, _i64, _p, _p, _p, C.c_int, _p, _p, _p, C.c_int, _i64, _i64,
                                  C.c_int, C.c_double, _p, _i64, _i64, _p]),
+    "dmdx_varimax_max_k": (C.c_int, []),
+    "dmdx_varimax_workspace_bytes": (_sz, [_i64, _i64]),
+    "dmdx_varimax_step_f32": (C.c_int, [_p, _i64, _i64, _i64, _p, _i64, _p, _p, _i64, _p, _p, C.c_int, _p, _sz, _p]),
+    "dmdx_row_norms_f32": (C.c_int, [_p, _i64, _i64, _i64, _p, _p, _p]),
     "dmdx_pack_triu_f64": (C.c_int, [_p, _i64, _i64, _p, _p]),
     "dmdx_unpack_triu_f64": (C.c_int, [_p, _i64, _p, _i64, _p]),
     "dmdx_exp_basis": (C.c_int, [_p, _p, _i64, _i64, _p, _p, C.c_int, _p]),

@@ -78,7 +78,7 @@ def _out_view(out: torch.Tensor | None, m: int, T: int, dtype, device, who: str,
     return out, _check_field(out, m, T, dtype, device, who, "out", kind)
 
 
-_DTYPE_NAME = {torch.float64: "fp64", torch.int64: "int64", torch.int32: "int32"}
+_DTYPE_NAME = {torch.float64: "fp64", torch.float32: "fp32", torch.int64: "int64", torch.int32: "int32"}
 DMDX_SPELL_NQ = 7                        # the planes of K27 (include/dmdx.h)
 DMDX_PSTAT_NQ = 8                        # the planes of K29
 PSTAT_INNER = ("sum", "mean", "max", "min", "range")      # DMDX_PSTAT_SUM .. DMDX_PSTAT_RANGE
@@ -618,6 +618,59 @@ class HipKernels:
         ))
         _lib.check(rc, "dmdx_project_f32")
         return Ct, energy
+
+    # -- K30 ----------------------------------------------------------------
+    @property
+    def varimax_max_k(self) -> int:
+        return int(self._lib.dmdx_varimax_max_k())
+
+    def varimax_step(self, Ut: torch.Tensor, Rt: torch.Tensor, w: torch.Tensor | None = None, out=None,
+                     want_f: bool = True):
+        """The sums of one orthomax step in one read of U: with ``a = U`` (or ``fl(U w)``, one weight per row) and
+        ``L = a R``, ``G = a^T L^3``, ``q = colsum(L^2)``, ``f = colsum(L^4)``; L is never stored.  Ut: (k, m) fp32,
+        Rt: (k, k) fp32 holding the column-major R (``Rt[c, j] = R[j, c]``, any row stride), w: (m,) fp32 or None
+        -> (Gt (k, k) fp64 with ``Gt[c, j] = G[j, c]``, q (k,) fp64, f (k,) fp64 or None).
+
+        ``out``: the triple (Gt, q, f) of an earlier call -- contiguous fp64 -- that this block's sums are ADDED to
+        (row blocks of U); its f is None iff ``want_f`` is false."""
+        m, k, ldu = _check_mat(Ut, torch.float32, "varimax_step U")
+        kr, kc, ldr = _check_mat(Rt, torch.float32, "varimax_step R")
+        if (kr, kc) != (k, k) or Rt.device != Ut.device:
+            raise _lib.DmdxError(f"varimax_step: R must be ({k}, {k}) on {Ut.device}, got {tuple(Rt.shape)} on {Rt.device}")
+        _check_vec(w, m, Ut.device, "varimax_step", "w")
+        if out is not None:
+            Gt, q, f = out
+            _accumulator(Gt, (k, k), torch.float64, Ut.device, "varimax_step", "out[0]")
+            _accumulator(q, (k,), torch.float64, Ut.device, "varimax_step", "out[1]")
+            if (f is not None) != bool(want_f):
+                raise _lib.DmdxError("varimax_step: out[2] must be given when f is wanted, and None otherwise")
+            if f is not None:
+                _accumulator(f, (k,), torch.float64, Ut.device, "varimax_step", "out[2]")
+        else:
+            Gt = torch.empty((k, k), dtype=torch.float64, device=Ut.device)
+            q = torch.empty(k, dtype=torch.float64, device=Ut.device)
+            f = torch.empty(k, dtype=torch.float64, device=Ut.device) if want_f else None
+        ws = self._workspace(Ut.device, self._lib.dmdx_varimax_workspace_bytes(m, k))
+        rc = self._timed("varimax_step", (m, k), lambda: self._lib.dmdx_varimax_step_f32(
+            _ptr(Ut), m, k, ldu, _ptr(Rt), ldr, _ptr(w), _ptr(Gt), k, _ptr(q), _ptr(f), int(out is not None),
+            _ptr(ws), ws.numel(), self._stream()
+        ))
+        _lib.check(rc, "dmdx_varimax_step_f32")
+        return Gt, q, f
+
+    def row_norms(self, Ut: torch.Tensor, cscale: torch.Tensor | None = None, out: torch.Tensor | None = None):
+        """``h[i] = fp32(sqrt(sum_j fp64(fl(U[i, j] cscale[j]))^2))``: the communalities of Kaiser's normalisation, how
+        much of a grid point the k modes explain.  Ut: (k, m) fp32 (any row stride), cscale: (k,) fp32 or None
+        -> h (m,) fp32 (``out`` if given).  One read of Ut."""
+        m, k, ldu = _check_mat(Ut, torch.float32, "row_norms U")
+        _check_vec(cscale, k, Ut.device, "row_norms", "cscale")
+        h = _accumulator(out, (m,), torch.float32, Ut.device, "row_norms") if out is not None else \
+            torch.empty(m, dtype=torch.float32, device=Ut.device)
+        rc = self._timed("row_norms", (m, k), lambda: self._lib.dmdx_row_norms_f32(
+            _ptr(Ut), m, k, ldu, _ptr(cscale), _ptr(h), self._stream()
+        ))
+        _lib.check(rc, "dmdx_row_norms_f32")
+        return h
 
     # -- K5 -----------------------------------------------------------------
     def row_center_scale_(self, Xt: torch.Tensor, scale: bool):

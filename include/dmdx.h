@@ -1070,6 +1070,47 @@ int dmdx_remap_f32(const float* X, int64_t T, int64_t ldx, int64_t P, int64_t ld
                    const double* wx, int SX, int64_t NLAT, int64_t NLON, int skipna, double min_frac, float* Y, int64_t ldy,
                    int64_t ldq, void* stream);
 
+/* ---- K30: one step of the orthomax (varimax) rotation of the leading k modes, and Kaiser's row norms --------------
+ * U: m x k (ldu), the left singular vectors; R: k x k column-major (ldr), any values -- the host hands over
+ * diag(s) R rounded to fp32; w: m floats, nullable (= 1), Kaiser's 1 / h.  1 <= k <= dmdx_varimax_max_k() (64).
+ *     a[i, j]  = w ? fl(U[i, j] w[i]) : U[i, j]
+ *     L[i, c]  = sum_j a[i, j] R[j, c]            fp32 MFMA chain, j ascending, k padded with zeros in a AND in R
+ *     G[j, c] (+)= sum_i a[i, j] fl(fl(L L) L)    G: k x k column-major (ldg), fp64
+ *     q[c]    (+)= sum_i fl(L L)                  k doubles
+ *     f[c]    (+)= sum_i fl(fl(L L) fl(L L))      k doubles, nullable
+ * U is read exactly once per call and L is never stored.  The sums over i are fp32 over one row range of at most
+ * DMDX_VARIMAX_FP32_ROWS rows (shortened, as K13's, while the launch would leave CUs idle) and fp64 across the row
+ * ranges, through per-unit slots in the workspace and a reduce kernel that adds the ranges in order.  No floating-point
+ * atomics: the order of every sum is a function of (m, k) only, two calls give the same bits.  accumulate != 0 adds to
+ * G, q and f, so that U can be passed as row blocks.
+ * Error against the exact sums of the fp32 inputs, with Labs = |a| |R| and u = 2^-24:
+ *     |dG| <= (4096 + 3 k + 8) u |a|^T Labs^3,  |dq| <= (4096 + 2 k + 6) u colsum(Labs^2),
+ *     |df| <= (4096 + 4 k + 8) u colsum(Labs^4).
+ * Memory: the operands are only read, and only inside their logical elements; with accumulate == 0 every logical
+ * element of G, q and f is written and nothing else, with accumulate != 0 they are read and written.  The pads
+ * ldu - m, ldr - k and ldg - k are never read for a result and never written.  No alignment is required beyond that of
+ * the elements; a 16-byte aligned U with ldu % 4 == 0 selects 16-byte loads with the same values.  The workspace needs
+ * no initialisation; dmdx_varimax_workspace_bytes is non-decreasing in m.
+ * Values: a non-finite U[i, j] or w[i] makes every element of G, q and f non-finite, of the class numpy's fp64
+ * evaluation of the formulas has.  A non-finite R[j, c] makes column c of G, q[c] and f[c] non-finite; every other
+ * element keeps the bits of the run without it.  Rows past m and columns past k are exact zeros on both sides, and L
+ * is zero for the rows past a row range before it is cubed: an Inf meets no pad.
+ * A refused call (DMDX_E_INVALID: a null U, R, G or q; k outside 1 .. 64; m < 1; ldu < m, ldr < k or ldg < k; any size
+ * >= 2^31; DMDX_E_WORKSPACE: a null or short workspace) has written nothing and made no HIP call; dmdx_last_error()
+ * names the entry point.
+ *
+ * dmdx_row_norms_f32: h[i] = fp32(sqrt(sum_j fp64(fl(U[i, j] cscale[j]))^2)), j ascending, every square rounded before
+ * it is added, cscale k floats, nullable (= 1): the communalities of Kaiser's normalisation, one streaming read of U,
+ * bit for bit the numpy expression.  Any k >= 1.  Refused (DMDX_E_INVALID): a null U or h, m < 1, k < 1, ldu < m, a size
+ * >= 2^31. */
+#define DMDX_VARIMAX_FP32_ROWS 4096
+int dmdx_varimax_max_k(void);
+size_t dmdx_varimax_workspace_bytes(int64_t m, int64_t k);
+int dmdx_varimax_step_f32(const float* U, int64_t m, int64_t k, int64_t ldu, const float* R, int64_t ldr, const float* w,
+                          double* G, int64_t ldg, double* q, double* f, int accumulate, void* workspace,
+                          size_t workspace_bytes, void* stream);
+int dmdx_row_norms_f32(const float* U, int64_t m, int64_t k, int64_t ldu, const float* cscale, float* h, void* stream);
+
 /* ---- upper triangle of a symmetric fp64 matrix <-> packed row by row ---------------------
  * packed[i (2n - i + 1) / 2 + (j - i)] = A[i][j], j >= i: what the Gram all-reduce of the
  * row-sharded path moves (n (n + 1) / 2 doubles instead of n^2).  unpack writes both triangles. */
