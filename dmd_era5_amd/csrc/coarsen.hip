@@ -41,8 +41,6 @@ namespace {
 
 constexpr int kBlock = DMDX_COARSEN_BLOCK;
 
-__device__ __forceinline__ bool finite_bits(float x) { return (__float_as_uint(x) & 0x7F800000u) != 0x7F800000u; }
-
 // N values in ascending longitude -> r (their fp64 sum from +0.0) and c (how many were added)
 template <int N, bool SKIPNA>
 __device__ __forceinline__ void chain(const float* v, double& r, int& c) {

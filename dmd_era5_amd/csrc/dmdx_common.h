@@ -42,6 +42,9 @@ static inline bool dmdx_aligned16(const void* p) { return ((uintptr_t)p & 15u) =
 // Jacobi step = 16 round trips of ~1 us).  Ordering against the producer is the caller's barrier.
 // `rs` = dmdx_sc1_rsrc(base), offsets in bytes (< 2^31).
 #ifdef __HIPCC__
+// neither Inf nor NaN, by the exponent bits
+__device__ __forceinline__ bool finite_bits(float x) { return (__float_as_uint(x) & 0x7F800000u) != 0x7F800000u; }
+
 __device__ __forceinline__ __amdgpu_buffer_rsrc_t dmdx_sc1_rsrc(const void* base) {
   return __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(base), 0, -1, 0x00020000);
 }

@@ -47,8 +47,6 @@ struct Lags {
   int32_t pre;                     // the largest lag the ring serves (<= kRing): what a segment re-reads before its start
 };
 
-template <int R> struct VecOf { typedef float type __attribute__((ext_vector_type(R))); };
-
 // One lane: R consecutive rows from row r0 of xb.  Segments s = blockIdx.y, blockIdx.y + gridDim.y, ...: SPLIT stores every
 // segment sum to ws[(s np + plane) m + row], np = 1 + L; otherwise gridDim.y is 1 and the lane adds them up itself.
 template <int LT, int R, bool FULL, bool SPLIT, bool MU>
@@ -58,13 +56,7 @@ __device__ __forceinline__ void lag_rows(const float* __restrict__ xb, int64_t r
                                          typename VecOf<R>::type* ring) {
   typedef typename VecOf<R>::type vec;
   const float* xp = xb + r0;
-  auto ld = [&](const float* p) -> vec {
-    if (FULL) return *reinterpret_cast<const vec*>(p);
-    vec v;
-#pragma unroll
-    for (int e = 0; e < R; ++e) v[e] = e < nr ? p[e] : 0.f;
-    return v;
-  };
+  auto ld = [&](const float* p) { return ld_rows<R, FULL>(p, nr); };
   double mud[R];
 #pragma unroll
   for (int e = 0; e < R; ++e) mud[e] = (MU && e < nr) ? (double)mup[e] : 0.0;
@@ -244,11 +236,9 @@ __global__ __launch_bounds__(256) void lag_edge_kernel(const float* __restrict__
     if (l < L) o[l * ldo] = tot[l] + acc[l];
 }
 
-// nseg (1 + L) m doubles (the factors are below 2^31, 2^4 and 2^31: the product is formed in 128 bits and saturates)
+// nseg (1 + L) m doubles
 size_t lag_workspace_bytes(int64_t m, int64_t T, int64_t L, int64_t seg) {
-  const int64_t nseg = (T + seg - 1) / seg;
-  const unsigned __int128 n = (unsigned __int128)nseg * (unsigned)(1 + L) * (uint64_t)m * sizeof(double);
-  return n > (unsigned __int128)SIZE_MAX ? SIZE_MAX : (size_t)n;
+  return saturating_bytes((T + seg - 1) / seg, 1 + L, m, sizeof(double));
 }
 
 template <int LT, int R, bool MU>
@@ -270,11 +260,10 @@ void launch_main_form(dim3 grid, size_t lds, hipStream_t st, const float* X, int
 template <int LT>
 int launch_main(const float* X, int64_t m, int64_t T, int64_t ldx, const float* mu, const Lags& lg, int L, int64_t seg,
                 int64_t nseg, double* ws, double* out, int64_t ldo, hipStream_t st) {
-  const bool quad = dmdx_aligned16(X) && ldx % 4 == 0;
-  const int64_t rows_per_wg = quad ? 1024 : 256;
-  const dim3 grid((unsigned)((m + rows_per_wg - 1) / rows_per_wg), ws ? grid_rows(nseg) : 1u);
-  const size_t lds = lg.n_near ? (size_t)kRing * 256 * (quad ? 16 : 4) : 0;
-  if (quad) {
+  const RowLanes ln = row_lanes(X, ldx, m, nseg, ws != nullptr);
+  const dim3 grid(ln.gx, ln.gy);
+  const size_t lds = lg.n_near ? (size_t)kRing * 256 * (ln.quad ? 16 : 4) : 0;
+  if (ln.quad) {
     if (mu) launch_main_form<LT, 4, true>(grid, lds, st, X, m, T, ldx, mu, lg, seg, nseg, ws, out, ldo);
     else launch_main_form<LT, 4, false>(grid, lds, st, X, m, T, ldx, mu, lg, seg, nseg, ws, out, ldo);
   } else {
@@ -318,9 +307,7 @@ extern "C" int dmdx_lag_moments_f32(const float* X, int64_t m, int64_t T, int64_
   // X against the (1 + 3L) planes of out, stated as a two-column fp32 matrix of the same extent: 2 ((1 + 3L - 1) ldo + m)
   // floats = (2 - 1) ldy + m with ldy = 6 L ldo + m
   if (int rc = check_ranges("lag_moments", X, T, ldx, (const float*)out, 2, 6 * (int64_t)L * ldo + m, m, false)) return rc;
-  const size_t need = lag_workspace_bytes(m, T, L, seg);
-  DMDX_CHECK_ARG(!workspace || (need != SIZE_MAX && workspace_bytes >= need), "lag_moments: workspace of %zu bytes, %zu needed",
-                 workspace_bytes, need);
+  if (int rc = check_workspace("lag_moments", workspace, workspace_bytes, lag_workspace_bytes(m, T, L, seg))) return rc;
   if (m == 0 || T == 0) return 0;
 
   Lags all, lg;                                                 // every lag (the edge pass); the product chains

@@ -4,16 +4,15 @@
 // smallest running value with their day, the total, and the total and count beyond a per-row threshold come out (TXx,
 // TNn, DTR, Rx1day, Rx5day, PRCPTOT, SDII, R95pTOT, degree days; dmd_era5_amd/extremes.py).
 //
-// The contract is tests/pstat_ref.py, a plain loop over time, held bit for bit.  Every period is cut from its own
-// start into pieces of `seg` DAYS.  With a workspace (split) the lanes of a workgroup row scan one piece -- after the up
-// to window - 1 days before it inside its period, which only fill the ring -- and leave a record per row: the eight
-// planes of the piece alone, its partial sums from +0.0.  A combine kernel merges the records of a period in ascending
-// order: counts added, a strict compare for the extremes (the earlier piece wins a tie), tot = tot + acc.  Without a
-// workspace (walk) one lane walks the periods of its rows and closes a piece every seg days.  Every running value is
-// recomputed from the ring in one fixed order, so it does not depend on where a piece starts: both forms give the
-// same bits.
+// The contract is tests/pstat_ref.py, a plain loop over time, held bit for bit.  The frame is time_rows.h's (DESIGN.md,
+// "The period frame of K27 and K29"): pieces of `seg` DAYS, a record per piece, a combine kernel, a walk form.  A piece is
+// scanned after the up to window - 1 days before it inside its period, which only fill the ring; its record, per row, is
+// the eight planes of the piece alone, its partial sums from +0.0.  The merge, in ascending order: counts added, a strict
+// compare for the extremes (the earlier piece wins a tie), tot = tot + acc.  The walk form closes a piece every seg days.
+// Every running value is recomputed from the ring in one fixed order, so it does not depend on where a piece starts:
+// both forms give the same bits.
 //
-// A lane owns R consecutive rows (4 with 16-byte loads, 1 with dword loads).  Per row: the day accumulators (s, hi, lo,
+// Per row: the day accumulators (s, hi, lo,
 // c), a ring of the last W day values (W = window is a template parameter: the ring is rotated by moving registers once
 // per day and never indexed at run time) with a bit mask of their validity, and the outer words.  kAhead snapshot loads
 // are in flight ahead of their steps in a queue that is rotated the same way.  inner, the comparison and thr == NULL (a
@@ -24,7 +23,6 @@
 namespace {
 
 constexpr int kMaxWindow = DMDX_PSTAT_MAX_WINDOW;
-constexpr int kMaxPeriods = DMDX_PSTAT_MAX_PERIODS;
 constexpr int kNQ = DMDX_PSTAT_NQ;
 constexpr int kAhead = 4;                   // snapshot loads in flight per lane
 
@@ -32,17 +30,11 @@ constexpr int kAhead = 4;                   // snapshot loads in flight per lane
 enum { Q_N, Q_MAX, Q_ARGMAX, Q_MIN, Q_ARGMIN, Q_TOTAL, Q_ETOTAL, Q_ECOUNT };
 static_assert(Q_ECOUNT + 1 == kNQ, "a record is DMDX_PSTAT_NQ doubles");
 
-// What travels by value: the periods, the first piece of every period (piece0[P] = N) and the scalars of the call.
-struct Periods {
-  int32_t bound[kMaxPeriods + 1];
-  int32_t piece0[kMaxPeriods + 1];
-  int32_t P, group, inner, min_count;
+// What travels by value: the periods and their pieces (time_rows.h) and the scalars of the call.
+struct Periods : PeriodCuts {
+  int32_t group, inner, min_count;
   uint32_t flags;
 };
-
-template <int R> struct VecOf { typedef float type __attribute__((ext_vector_type(R))); };
-
-__device__ __forceinline__ bool finite_bits(float x) { return (__float_as_uint(x) & 0x7F800000u) != 0x7F800000u; }
 
 __device__ __forceinline__ double quiet_nan() { return __longlong_as_double(0x7FF8000000000000ll); }
 
@@ -72,13 +64,7 @@ __device__ __forceinline__ void pstat_rows(const float* __restrict__ X, int64_t 
                                            double* __restrict__ ws, double* __restrict__ out, int64_t ldo) {
   typedef typename VecOf<R>::type vec;
   const float* xp = X + r0;
-  auto ld = [&](const float* p) -> vec {
-    if (FULL) return *reinterpret_cast<const vec*>(p);
-    vec v;
-#pragma unroll
-    for (int e = 0; e < R; ++e) v[e] = e < nr ? p[e] : 0.f;
-    return v;
-  };
+  auto ld = [&](const float* p) { return ld_rows<R, FULL>(p, nr); };
 
   const int32_t g = pd.group, inner = pd.inner, min_count = pd.min_count;
   const bool below = pd.flags & DMDX_PSTAT_BELOW, incl = pd.flags & DMDX_PSTAT_INCLUSIVE;
@@ -197,7 +183,7 @@ __device__ __forceinline__ void pstat_rows(const float* __restrict__ X, int64_t 
     const int64_t N = pd.piece0[pd.P];
     int p = 0;
     for (int64_t sx = blockIdx.y; sx < N; sx += gridDim.y) {
-      while (pd.piece0[p + 1] <= sx) ++p;                       // (sx ascends: p only moves forward)
+      p = pd.period_of(sx, p);
       const int64_t b0 = pd.bound[p], b1 = pd.bound[p + 1];
       const int64_t days = (b1 - b0 + g - 1) / g;
       const int64_t k0 = (sx - pd.piece0[p]) * seg;             // < days: the piece exists
@@ -274,47 +260,12 @@ __global__ __launch_bounds__(256) void pstat_combine_kernel(const double* __rest
   o[Q_ECOUNT * pl] = ec;
 }
 
-// 0 <= b_0 < b_1 < ... < b_P (<= T when T >= 0 is given)
-bool bounds_ok(const int32_t* bounds, int P, int64_t T) {
-  if (!bounds || P < 1 || P > kMaxPeriods || bounds[0] < 0) return false;
-  for (int p = 0; p < P; ++p)
-    if (bounds[p + 1] <= bounds[p]) return false;
-  return T < 0 || bounds[P] <= T;
-}
+// N kNQ m doubles
+size_t pstat_workspace_bytes(int64_t m, int64_t N) { return saturating_bytes(N, kNQ, m, sizeof(double)); }
 
-// N = sum over the periods of ceil(days / seg), days = ceil(length / group): at most b_P - b_0 < 2^31
-int64_t count_pieces(const int32_t* bounds, int P, int64_t group, int64_t seg, int32_t* piece0) {
-  int64_t n = 0;
-  for (int p = 0; p < P; ++p) {
-    if (piece0) piece0[p] = (int32_t)n;
-    const int64_t days = ((int64_t)bounds[p + 1] - bounds[p] + group - 1) / group;
-    n += (days + seg - 1) / seg;
-  }
-  if (piece0) piece0[P] = (int32_t)n;
-  return n;
-}
-
-// N kNQ m doubles (the factors are below 2^31, 2^3, 2^31 and 2^3: the product is formed in 128 bits and saturates)
-size_t pstat_workspace_bytes(int64_t m, int64_t N) {
-  const unsigned __int128 n = (unsigned __int128)(uint64_t)N * (uint64_t)m * (kNQ * sizeof(double));
-  return n > (unsigned __int128)SIZE_MAX ? SIZE_MAX : (size_t)n;
-}
-
-template <int W, int R>
-void launch_scan(dim3 grid, hipStream_t st, const float* X, int64_t m, int64_t ldx, const float* thr, const Periods& pd,
-                 int64_t seg, double* ws, double* out, int64_t ldo) {
-  if (ws)
-    hipLaunchKernelGGL((pstat_scan_kernel<W, R, true>), grid, dim3(256), 0, st, X, m, ldx, thr, pd, seg, ws, out, ldo);
-  else
-    hipLaunchKernelGGL((pstat_scan_kernel<W, R, false>), grid, dim3(256), 0, st, X, m, ldx, thr, pd, seg, ws, out, ldo);
-}
-
-template <int W>
-void launch_window(bool quad, dim3 grid, hipStream_t st, const float* X, int64_t m, int64_t ldx, const float* thr,
-                   const Periods& pd, int64_t seg, double* ws, double* out, int64_t ldo) {
-  if (quad) launch_scan<W, 4>(grid, st, X, m, ldx, thr, pd, seg, ws, out, ldo);
-  else launch_scan<W, 1>(grid, st, X, m, ldx, thr, pd, seg, ws, out, ldo);
-}
+template <int W> struct Scan {
+  template <int R, bool SPLIT> static constexpr auto kernel() { return pstat_scan_kernel<W, R, SPLIT>; }
+};
 
 }  // namespace
 
@@ -353,32 +304,23 @@ extern "C" int dmdx_period_stats_f32(const float* X, int64_t m, int64_t T, int64
     if (int rc = check_ranges("period_stats", thr, 1, m, (const float*)out, 2, ldy, m, false)) return rc;
 
   Periods pd;
-  const int64_t N = count_pieces(bounds, P, group, seg, pd.piece0);
-  const size_t need = pstat_workspace_bytes(m, N);
-  DMDX_CHECK_ARG(!workspace || (need != SIZE_MAX && workspace_bytes >= need), "period_stats: workspace of %zu bytes, %zu needed",
-                 workspace_bytes, need);
+  const int64_t N = fill_periods(pd, bounds, P, group, seg);
+  if (int rc = check_workspace("period_stats", workspace, workspace_bytes, pstat_workspace_bytes(m, N))) return rc;
   if (m == 0) return 0;
-
-  for (int p = 0; p <= kMaxPeriods; ++p) {
-    pd.bound[p] = bounds[p < P ? p : P];
-    if (p > P) pd.piece0[p] = pd.piece0[P];
-  }
-  pd.P = P, pd.group = (int32_t)group, pd.inner = inner, pd.min_count = (int32_t)min_count, pd.flags = flags;
+  pd.group = (int32_t)group, pd.inner = inner, pd.min_count = (int32_t)min_count, pd.flags = flags;
 
   double* ws = (double*)workspace;
   hipStream_t st = (hipStream_t)stream;
-  const bool quad = dmdx_aligned16(X) && ldx % 4 == 0;
-  const int64_t rows_per_wg = quad ? 1024 : 256;
-  const dim3 grid((unsigned)((m + rows_per_wg - 1) / rows_per_wg), ws ? grid_rows(N) : 1u);
+  const RowLanes ln = row_lanes(X, ldx, m, N, ws != nullptr);
   switch (window) {
-    case 1: launch_window<1>(quad, grid, st, X, m, ldx, thr, pd, seg, ws, out, ldo); break;
-    case 2: launch_window<2>(quad, grid, st, X, m, ldx, thr, pd, seg, ws, out, ldo); break;
-    case 3: launch_window<3>(quad, grid, st, X, m, ldx, thr, pd, seg, ws, out, ldo); break;
-    case 4: launch_window<4>(quad, grid, st, X, m, ldx, thr, pd, seg, ws, out, ldo); break;
-    case 5: launch_window<5>(quad, grid, st, X, m, ldx, thr, pd, seg, ws, out, ldo); break;
-    case 6: launch_window<6>(quad, grid, st, X, m, ldx, thr, pd, seg, ws, out, ldo); break;
-    case 7: launch_window<7>(quad, grid, st, X, m, ldx, thr, pd, seg, ws, out, ldo); break;
-    default: launch_window<8>(quad, grid, st, X, m, ldx, thr, pd, seg, ws, out, ldo); break;
+    case 1: launch_lanes<Scan<1>>(ln, ws, st, X, m, ldx, thr, pd, seg, ws, out, ldo); break;
+    case 2: launch_lanes<Scan<2>>(ln, ws, st, X, m, ldx, thr, pd, seg, ws, out, ldo); break;
+    case 3: launch_lanes<Scan<3>>(ln, ws, st, X, m, ldx, thr, pd, seg, ws, out, ldo); break;
+    case 4: launch_lanes<Scan<4>>(ln, ws, st, X, m, ldx, thr, pd, seg, ws, out, ldo); break;
+    case 5: launch_lanes<Scan<5>>(ln, ws, st, X, m, ldx, thr, pd, seg, ws, out, ldo); break;
+    case 6: launch_lanes<Scan<6>>(ln, ws, st, X, m, ldx, thr, pd, seg, ws, out, ldo); break;
+    case 7: launch_lanes<Scan<7>>(ln, ws, st, X, m, ldx, thr, pd, seg, ws, out, ldo); break;
+    default: launch_lanes<Scan<8>>(ln, ws, st, X, m, ldx, thr, pd, seg, ws, out, ldo); break;
   }
   DMDX_LAUNCH_CHECK();
   if (ws) {

@@ -45,8 +45,6 @@ namespace {
 constexpr int kBlock = DMDX_REMAP_BLOCK;
 constexpr int kRegSpan = 8;                                      // wx rows up to this wide live in registers
 
-__device__ __forceinline__ bool finite_bits(float x) { return (__float_as_uint(x) & 0x7F800000u) != 0x7F800000u; }
-
 template <bool REG, bool SKIPNA>
 __global__ __launch_bounds__(kBlock) void remap_kernel(const float* __restrict__ X, int64_t T, int64_t ldx, int64_t ldp,
                                                        int64_t nlat, int64_t nlon, const int32_t* __restrict__ iy0,

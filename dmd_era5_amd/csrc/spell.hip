@@ -5,23 +5,21 @@
 //
 // The contract is tests/spell_ref.py, a plain loop over time, held element for element.  The state of the scan along
 // time -- the open run -- is not a sum: K21 / K26 add the partials of their time split, here they are MERGED in order.
-// Every period is cut from its own start into pieces of `seg` snapshots.  With a workspace (split) the lanes of a
-// workgroup row scan one piece and leave a record per (row, j): valid, events, the head run (from the piece's start to
-// its first non-event), the tail run (from its last non-event to its end) and what the runs strictly inside closed to
-// (count, snapshots, longest, first start, last end).  A combine kernel walks the records of a period in ascending
-// order:   all events: the piece extends the carry;   otherwise: carry + head is a run and is closed, the interior is
-// added, the carry becomes the tail;   the carry is closed at the period's end.  Without a workspace (walk) one lane
-// scans the periods of its rows end to end.  All results are integers: both forms and every seg give the same ones.
+// The frame is time_rows.h's ("The period frame of K27 and K29"): pieces of `seg` snapshots, a record per
+// piece, a combine kernel, a walk form.  The record of a piece, per (row, j): valid, events, the head run (from the
+// piece's start to its first non-event), the tail run (from its last non-event to its end) and what the runs strictly
+// inside closed to (count, snapshots, longest, first start, last end).  The merge, in ascending order:   all events: the
+// piece extends the carry;   otherwise: carry + head is a run and is closed, the interior is added, the carry becomes
+// the tail;   the carry is closed at the period's end.  All results are integers: both forms and every seg give the
+// same ones.
 //
-// A lane owns R consecutive rows (4 with 16-byte loads, 1 with dword loads) and J R state machines in registers (J is a
-// template tier).  The thresholds of a lane, h[j][e] = thr[(j S + slot[t]) ldthr + row], are loaded again only when
+// A lane keeps J R state machines in registers (J is a template tier).  The thresholds of a lane, h[j][e] = thr[(j S + slot[t]) ldthr + row], are loaded again only when
 // slot[t] changes -- the same snapshot for every lane, so the test is wave-uniform.  No atomics, no LDS, no barrier.
 #include "time_rows.h"
 
 namespace {
 
 constexpr int kMaxThr = DMDX_SPELL_MAX_THR;
-constexpr int kMaxPeriods = DMDX_SPELL_MAX_PERIODS;
 constexpr int kNQ = DMDX_SPELL_NQ;
 constexpr int kWords = DMDX_SPELL_WS_WORDS;
 
@@ -29,12 +27,9 @@ constexpr int kWords = DMDX_SPELL_WS_WORDS;
 enum { W_VALID, W_EVENT, W_HEAD, W_TAIL, W_NSPELL, W_INSPELL, W_LONGEST, W_FIRST, W_LAST };
 static_assert(W_LAST + 1 == kWords, "a record is DMDX_SPELL_WS_WORDS words");
 
-// What travels by value: the periods, the first piece of every period (piece0[P] = N) and the shortest qualifying run.
-struct Periods {
-  int32_t bound[kMaxPeriods + 1];
-  int32_t piece0[kMaxPeriods + 1];
+// What travels by value: the periods and their pieces (time_rows.h), the shortest qualifying run and the direction.
+struct Periods : PeriodCuts {
   int32_t min_len[kMaxThr];
-  int32_t P;
   uint32_t above;
 };
 
@@ -55,10 +50,6 @@ struct Tally {
   }
 };
 
-template <int R> struct VecOf { typedef float type __attribute__((ext_vector_type(R))); };
-
-__device__ __forceinline__ bool finite_bits(float x) { return (__float_as_uint(x) & 0x7F800000u) != 0x7F800000u; }
-
 // One lane: rows r0 .. r0 + nr - 1.  SPLIT: the pieces s = blockIdx.y, blockIdx.y + gridDim.y, ... of the call, a record
 // each; otherwise the periods one after another, their planes stored as they end.
 template <int J, int R, bool FULL, bool SPLIT>
@@ -68,13 +59,7 @@ __device__ __forceinline__ void spell_rows(const float* __restrict__ X, int64_t 
                                            int32_t* __restrict__ ws, int32_t* __restrict__ out, int64_t ldo) {
   typedef typename VecOf<R>::type vec;
   const float* xp = X + r0;
-  auto ld = [&](const float* p) -> vec {
-    if (FULL) return *reinterpret_cast<const vec*>(p);
-    vec v;
-#pragma unroll
-    for (int e = 0; e < R; ++e) v[e] = e < nr ? p[e] : 0.f;
-    return v;
-  };
+  auto ld = [&](const float* p) { return ld_rows<R, FULL>(p, nr); };
 
   Tally ty[J][R];
   int32_t head[J][R];                       // SPLIT: the head run, -1 until the piece's first non-event
@@ -150,7 +135,7 @@ __device__ __forceinline__ void spell_rows(const float* __restrict__ X, int64_t 
     const int64_t N = pd.piece0[pd.P];
     int p = 0;
     for (int64_t s = blockIdx.y; s < N; s += gridDim.y) {
-      while (pd.piece0[p + 1] <= s) ++p;                        // (s ascends: p only moves forward)
+      p = pd.period_of(s, p);
       const int64_t off = (s - pd.piece0[p]) * seg;             // the piece's first snapshot, after the period's start
       const int64_t a = pd.bound[p] + off;
       const int64_t b = pd.bound[p + 1] - a < seg ? pd.bound[p + 1] : a + seg;
@@ -253,49 +238,12 @@ __global__ __launch_bounds__(256) void spell_combine_kernel(const int32_t* __res
   o[0] = t.nv, o[pl] = t.ne, o[2 * pl] = t.ns, o[3 * pl] = t.nin, o[4 * pl] = t.longest, o[5 * pl] = (int32_t)t.first, o[6 * pl] = t.last;
 }
 
-// 0 <= b_0 < b_1 < ... < b_P (<= T when T >= 0 is given)
-bool bounds_ok(const int32_t* bounds, int P, int64_t T) {
-  if (!bounds || P < 1 || P > kMaxPeriods || bounds[0] < 0) return false;
-  for (int p = 0; p < P; ++p)
-    if (bounds[p + 1] <= bounds[p]) return false;
-  return T < 0 || bounds[P] <= T;
-}
+// N J m kWords int32
+size_t spell_workspace_bytes(int64_t m, int64_t N, int J) { return saturating_bytes(N, J, m, kWords * sizeof(int32_t)); }
 
-// N = sum over the periods of ceil(length / seg): at most b_P - b_0 < 2^31
-int64_t count_pieces(const int32_t* bounds, int P, int64_t seg, int32_t* piece0) {
-  int64_t n = 0;
-  for (int p = 0; p < P; ++p) {
-    if (piece0) piece0[p] = (int32_t)n;
-    n += ((int64_t)bounds[p + 1] - bounds[p] + seg - 1) / seg;
-  }
-  if (piece0) piece0[P] = (int32_t)n;
-  return n;
-}
-
-// N J m kWords int32 (the factors are below 2^31, 2^3, 2^31 and 2^6: the product is formed in 128 bits and saturates)
-size_t spell_workspace_bytes(int64_t m, int64_t N, int J) {
-  const unsigned __int128 n = (unsigned __int128)(uint64_t)N * (unsigned)J * (uint64_t)m * (kWords * sizeof(int32_t));
-  return n > (unsigned __int128)SIZE_MAX ? SIZE_MAX : (size_t)n;
-}
-
-template <int J, int R>
-void launch_scan(dim3 grid, hipStream_t st, const float* X, int64_t m, int64_t ldx, const float* thr, int64_t ldthr,
-                 int64_t S, const int32_t* slot, const Periods& pd, int64_t seg, int32_t* ws, int32_t* out, int64_t ldo) {
-  if (ws)
-    hipLaunchKernelGGL((spell_scan_kernel<J, R, true>), grid, dim3(256), 0, st, X, m, ldx, thr, ldthr, S, slot, pd, seg, ws,
-                       out, ldo);
-  else
-    hipLaunchKernelGGL((spell_scan_kernel<J, R, false>), grid, dim3(256), 0, st, X, m, ldx, thr, ldthr, S, slot, pd, seg, ws,
-                       out, ldo);
-}
-
-template <int J>
-void launch_tier(bool quad, dim3 grid, hipStream_t st, const float* X, int64_t m, int64_t ldx, const float* thr,
-                 int64_t ldthr, int64_t S, const int32_t* slot, const Periods& pd, int64_t seg, int32_t* ws, int32_t* out,
-                 int64_t ldo) {
-  if (quad) launch_scan<J, 4>(grid, st, X, m, ldx, thr, ldthr, S, slot, pd, seg, ws, out, ldo);
-  else launch_scan<J, 1>(grid, st, X, m, ldx, thr, ldthr, S, slot, pd, seg, ws, out, ldo);
-}
+template <int J> struct Scan {
+  template <int R, bool SPLIT> static constexpr auto kernel() { return spell_scan_kernel<J, R, SPLIT>; }
+};
 
 }  // namespace
 
@@ -305,7 +253,7 @@ extern "C" int dmdx_spell_max_periods(void) { return kMaxPeriods; }
 
 extern "C" size_t dmdx_spell_workspace_bytes(int64_t m, const int32_t* bounds, int P, int J, int64_t seg) {
   if (m < 0 || m >= kMaxSize || J < 1 || J > kMaxThr || seg < 1 || seg >= kMaxSize || !bounds_ok(bounds, P, -1)) return 0;
-  return spell_workspace_bytes(m, count_pieces(bounds, P, seg, nullptr), J);
+  return spell_workspace_bytes(m, count_pieces(bounds, P, 1, seg, nullptr), J);
 }
 
 extern "C" int dmdx_spell_f32(const float* X, int64_t m, int64_t T, int64_t ldx, const float* thr, int64_t ldthr, int J,
@@ -330,29 +278,20 @@ extern "C" int dmdx_spell_f32(const float* X, int64_t m, int64_t T, int64_t ldx,
   if (int rc = check_ranges("spell", thr, Tt, ldthr, (const float*)out, To, ldo, m, false)) return rc;
 
   Periods pd;
-  const int64_t N = count_pieces(bounds, P, seg, pd.piece0);
-  const size_t need = spell_workspace_bytes(m, N, J);
-  DMDX_CHECK_ARG(!workspace || (need != SIZE_MAX && workspace_bytes >= need), "spell: workspace of %zu bytes, %zu needed",
-                 workspace_bytes, need);
+  const int64_t N = fill_periods(pd, bounds, P, 1, seg);
+  if (int rc = check_workspace("spell", workspace, workspace_bytes, spell_workspace_bytes(m, N, J))) return rc;
   if (m == 0) return 0;
-
-  for (int p = 0; p <= kMaxPeriods; ++p) {
-    pd.bound[p] = bounds[p < P ? p : P];
-    if (p > P) pd.piece0[p] = pd.piece0[P];
-  }
   for (int j = 0; j < kMaxThr; ++j) pd.min_len[j] = min_len[j < J ? j : J - 1];
-  pd.P = P, pd.above = above_mask;
+  pd.above = above_mask;
 
   int32_t* ws = (int32_t*)workspace;
   hipStream_t st = (hipStream_t)stream;
-  const bool quad = dmdx_aligned16(X) && ldx % 4 == 0;
-  const int64_t rows_per_wg = quad ? 1024 : 256;
-  const dim3 grid((unsigned)((m + rows_per_wg - 1) / rows_per_wg), ws ? grid_rows(N) : 1u);
+  const RowLanes ln = row_lanes(X, ldx, m, N, ws != nullptr);
   switch (J) {
-    case 1: launch_tier<1>(quad, grid, st, X, m, ldx, thr, ldthr, S, slot, pd, seg, ws, out, ldo); break;
-    case 2: launch_tier<2>(quad, grid, st, X, m, ldx, thr, ldthr, S, slot, pd, seg, ws, out, ldo); break;
-    case 3: launch_tier<3>(quad, grid, st, X, m, ldx, thr, ldthr, S, slot, pd, seg, ws, out, ldo); break;
-    default: launch_tier<4>(quad, grid, st, X, m, ldx, thr, ldthr, S, slot, pd, seg, ws, out, ldo); break;
+    case 1: launch_lanes<Scan<1>>(ln, ws, st, X, m, ldx, thr, ldthr, S, slot, pd, seg, ws, out, ldo); break;
+    case 2: launch_lanes<Scan<2>>(ln, ws, st, X, m, ldx, thr, ldthr, S, slot, pd, seg, ws, out, ldo); break;
+    case 3: launch_lanes<Scan<3>>(ln, ws, st, X, m, ldx, thr, ldthr, S, slot, pd, seg, ws, out, ldo); break;
+    default: launch_lanes<Scan<4>>(ln, ws, st, X, m, ldx, thr, ldthr, S, slot, pd, seg, ws, out, ldo); break;
   }
   DMDX_LAUNCH_CHECK();
   if (ws) {

@@ -44,10 +44,9 @@ from dataclasses import dataclass
 import numpy as np
 import torch
 
+from . import _periods as pp
 from . import _timeaxis as ta
-from .forecast import _check_weights, _group_pieces
-from .labeled import Coord, DataArray, Dataset
-from .spells import _bounds_list, periods_of
+from .labeled import Dataset
 from .svd import Comm, _kern
 
 __all__ = ["SEGMENT", "PLANES", "INNER", "snapshots_per_day", "period_stat_blocks", "PeriodStats"]
@@ -106,7 +105,7 @@ def period_stat_blocks(Xblocks, bounds, group=1, inner="sum", window=1, min_coun
     a (rows,) fp32 table; the event is value > threshold, < with ``below``, >= / <= with ``inclusive``."""
     who = "period_stat_blocks"
     kern = _kern(kern)
-    b = _bounds_list(bounds, who)
+    b = pp.bounds_list(bounds, who)
     g, w, mc = _settings(group, inner, window, min_count, who)
     tabs = None
     if threshold is not None and not _is_number(threshold):
@@ -133,13 +132,8 @@ def period_stat_blocks(Xblocks, bounds, group=1, inner="sum", window=1, min_coun
     return out
 
 
-def _ratio(num, den):
-    """num / den where den > 0, NaN elsewhere."""
-    return torch.where(den > 0, num / torch.where(den > 0, den, torch.ones_like(den)), torch.full_like(den, float("nan")))
-
-
 @dataclass
-class PeriodStats:
+class PeriodStats(pp.Periods):
     """The period statistics of a list of row blocks: ``planes`` holds one (8, P, rows) fp64 tensor per block
     (:func:`period_stat_blocks`), ``bounds`` the P + 1 positions of the periods, ``labels`` their names, ``times`` the
     T stamps (or None), the rest the settings of the fit."""
@@ -164,36 +158,16 @@ class PeriodStats:
         ``period``: a kind of :func:`spells.periods_of`, or the bounds themselves (then ``times`` may be None).  The
         rest as :func:`period_stat_blocks`."""
         who = "PeriodStats.fit"
-        t = None if times is None else ta.stamps(times, who).astype("datetime64[ns]")
-        if isinstance(period, str):
-            if t is None:
-                raise ValueError(f"{who}: period = {period!r} needs times")
-            bounds, labels = periods_of(t, period)
-        else:
-            bounds = np.asarray(_bounds_list(period, who), dtype=np.int32)
-            labels = np.array([str(p) for p in range(bounds.shape[0] - 1)])
-            if t is not None and bounds[-1] > t.shape[0]:
-                raise ValueError(f"{who}: the bounds end at {int(bounds[-1])}, times has {t.shape[0]}")
+        t, bounds, labels = pp.resolve_periods(times, period, who)
         g, w, mc = _settings(group, inner, window, min_count, who)
         kern = _kern(kern)
-
-        def checked():
-            for b, X in enumerate(Xblocks):
-                T = int(X.shape[0])
-                if t is not None and T != t.shape[0]:
-                    raise ValueError(f"{who}: block {b} holds {T} snapshots, times has {t.shape[0]}")
-                yield X
-
-        planes = period_stat_blocks(checked(), bounds, g, inner, w, mc, threshold, below, inclusive, kern)
+        planes = period_stat_blocks(pp.checked_blocks(Xblocks, t, who), bounds, g, inner, w, mc, threshold, below, inclusive,
+                                    kern)
         if not planes:
             raise ValueError(f"{who}: no blocks")
         return cls(planes, bounds, labels, g, inner, w, mc, bool(below), bool(inclusive), threshold is not None, t, kern)
 
     # -- the indices ------------------------------------------------------------------------------------------------
-    @property
-    def n_periods(self) -> int:
-        return int(self.bounds.shape[0]) - 1
-
     def period_days(self) -> np.ndarray:
         """The days of every period, the ragged last one included, (P,) int64."""
         return -(-np.diff(self.bounds.astype(np.int64)) // self.group)
@@ -227,40 +201,29 @@ class PeriodStats:
 
     def mean(self) -> list:
         """total / n (DTR), NaN where the period has no value."""
-        return [_ratio(Q[5], Q[0]) for Q in self.planes]
+        return [pp.ratio(Q[5], Q[0]) for Q in self.planes]
 
     def intensity(self) -> list:
         """total_beyond / count_beyond (SDII), NaN where nothing lies beyond the threshold."""
-        return [_ratio(Q[6], Q[7]) for Q in self.planes]
+        return [pp.ratio(Q[6], Q[7]) for Q in self.planes]
 
     def fraction_beyond(self) -> list:
         """total_beyond / total (R95pTOT), NaN where the total is not positive."""
-        return [_ratio(Q[6], Q[5]) for Q in self.planes]
+        return [pp.ratio(Q[6], Q[5]) for Q in self.planes]
 
-    def _when(self, name: str, as_time: bool, who: str) -> list:
+    def _day(self, name: str, as_time: bool, who: str) -> list:
         off = [Q.to(torch.int64) for Q in self._plane(name)]
-        if not as_time:
-            return off
-        if self.times is None:
-            raise ValueError(f"PeriodStats.{who}: fitted without times: only the offsets are known")
-        start = self.bounds[:-1].astype(np.int64)[:, None]
-        out = []
-        for o in off:
-            o = o.cpu().numpy()
-            when = self.times[np.where(o >= 0, start + o * self.group, 0)]
-            when[o < 0] = np.datetime64("NaT")
-            out.append(when)
-        return out
+        return self._when(off, self.group, who) if as_time else off
 
     def when_max(self, as_time: bool = False) -> list:
         """The day of the period on which the maximum fell (the last day of its window; the first one among equal
         maxima): the offset in days from the period's start, (P, rows) int64, -1 where there is none; ``as_time``: the
         stamp of the first snapshot of that day instead (numpy datetime64, NaT where none)."""
-        return self._when("argmax", as_time, "when_max")
+        return self._day("argmax", as_time, "when_max")
 
     def when_min(self, as_time: bool = False) -> list:
         """The day of the minimum, as :meth:`when_max`."""
-        return self._when("argmin", as_time, "when_min")
+        return self._day("argmin", as_time, "when_min")
 
     def _index(self, name: str, who: str) -> list:
         if name not in _INDICES:
@@ -288,32 +251,8 @@ class PeriodStats:
         stacked sums per call."""
         who = "PeriodStats.area_mean"
         values = self._index(index, who)
-        comm = comm or Comm()
-        weights = _check_weights(weights, who)
-        rows_of = [int(Q.shape[2]) for Q in self.planes]
-        if weights is not None and len(weights) != len(rows_of):
-            raise ValueError(f"{who}: {len(weights)} weight vectors for {len(rows_of)} blocks")
-        pieces, G = _group_pieces(groups, rows_of, [1] * len(rows_of), n_groups, who)
-        P = self.n_periods
-        device = self.planes[0].device if self.planes else torch.device("cpu")
-        # P numbers per row: reduced on the host, in one order whatever the device
-        sums = torch.zeros((3, G, P), dtype=torch.float64)
-        for b, (Q, val) in enumerate(zip(self.planes, values)):
-            w = torch.ones(rows_of[b], dtype=torch.float64) if weights is None else \
-                torch.as_tensor(weights[b]).to(device="cpu", dtype=torch.float64).reshape(-1)
-            if w.numel() != rows_of[b]:
-                raise ValueError(f"{who}: weights[{b}] has {w.numel()} entries, the block {rows_of[b]} rows")
-            val = val.cpu().to(torch.float64)
-            keep = (w != 0)[None] & (Q[0].cpu() > 0) & ~torch.isnan(val)
-            ww = torch.where(keep, w[None].expand_as(val), torch.zeros_like(val))
-            wv = torch.where(keep, ww * val, torch.zeros_like(val))
-            for s, e, g in pieces[b]:
-                sums[0, g] += wv[:, s:e].sum(dim=1)
-                sums[1, g] += ww[:, s:e].sum(dim=1)
-                sums[2, g] += keep[:, s:e].sum(dim=1)
-        sums = comm.allreduce_sum_(sums.reshape(-1).to(device), tag="pstat_allreduce").cpu().reshape(3, G, P)
-        W = sums[1]
-        return {"mean": _ratio(sums[0], W), "weight": W, "rows": sums[2].to(torch.int64)}
+        return pp.area_mean_sums(self._plane("n"), values, lambda v: ~torch.isnan(v), weights, groups, n_groups, comm,
+                                 "pstat_allreduce", who)
 
     # -- persistence ----------------------------------------------------------------------------------------------
     def to_dataset(self, coords=None) -> Dataset:
@@ -322,25 +261,10 @@ class PeriodStats:
         the stamps as ``time_s`` / ``time_ns(time_index)`` (whole seconds since 1970 and the nanoseconds beyond;
         absent without times) and the attribute ``period_labels`` (the labels joined by commas); ``coords``: the
         per-row coordinates of the decomposed array, taken over as they are.  ``io_netcdf.to_netcdf`` writes it."""
-        P = self.n_periods
         sets = [self.group, INNER.index(self.inner), self.window, self.min_count, int(self.below), int(self.inclusive),
                 int(self.has_threshold)]
-        cds = {"plane": Coord("plane", np.arange(len(PLANES) * P, dtype=np.int64)),
-               "bound": Coord("bound", np.arange(P + 1, dtype=np.int64)),
-               "setting": Coord("setting", np.arange(len(sets), dtype=np.int64)), **ta.row_coords(coords)}
-        ds = Dataset(coords=cds, attrs={"period_labels": ",".join(str(v) for v in self.labels)})
-        row = {k: v for k, v in cds.items() if k not in ("plane", "bound", "setting")}
-        field = np.concatenate([Q.detach().cpu().numpy().reshape(len(PLANES) * P, -1) for Q in self.planes], axis=1)
-        ds["period_planes"] = DataArray(field.astype(np.float64), ("plane", "space"), {"plane": cds["plane"], **row})
-        ds["period_bound"] = DataArray(self.bounds.astype(np.int64), ("bound",), {"bound": cds["bound"]})
-        ds["settings"] = DataArray(np.asarray(sets, dtype=np.int64), ("setting",), {"setting": cds["setting"]})
-        if self.times is not None:
-            ns = self.times.astype("datetime64[ns]").astype(np.int64)
-            tc = Coord("time_index", np.arange(ns.shape[0], dtype=np.int64))
-            ds.coords["time_index"] = tc
-            ds["time_s"] = DataArray(ns // 10**9, ("time_index",), {"time_index": tc})
-            ds["time_ns"] = DataArray(ns % 10**9, ("time_index",), {"time_index": tc})
-        return ds
+        return pp.to_dataset("period_planes", self.planes, np.float64, self.bounds, self.labels, self.times, coords, "setting",
+                             {"settings": sets})
 
     @classmethod
     def from_dataset(cls, ds: Dataset, rows=None, device=None, kern=None) -> "PeriodStats":
@@ -349,19 +273,12 @@ class PeriodStats:
         the HIP provider)."""
         who = "PeriodStats.from_dataset"
         kern = _kern(kern)
-        field = np.ascontiguousarray(np.asarray(ds["period_planes"].values), dtype=np.float64)
-        bounds = np.asarray(ds["period_bound"].values).astype(np.int32).reshape(-1)
+        field, bounds, labels, times = pp.from_dataset(ds, "period_planes", np.float64)
         sets = [int(v) for v in np.asarray(ds["settings"].values).reshape(-1)]
         P = int(bounds.shape[0]) - 1
         if field.shape[0] != len(PLANES) * P or len(sets) != 7 or not 0 <= sets[1] < len(INNER):
             raise ValueError(f"{who}: period_planes holds {field.shape[0]} planes, {P} periods ask for {len(PLANES) * P}; "
                              f"settings holds {len(sets)} values")
-        text = ta.attr_str(ds.attrs["period_labels"]) if "period_labels" in ds.attrs else ""
-        labels = np.array(text.split(",")) if text else np.array([str(p) for p in range(P)])
-        times = None
-        if "time_s" in ds:
-            s = np.asarray(ds["time_s"].values).astype(np.int64).reshape(-1)
-            times = (s * 10**9 + np.asarray(ds["time_ns"].values).astype(np.int64).reshape(-1)).astype("datetime64[ns]")
         flat = ta.cut_rows(field, rows, device, kern, who)
         return cls([F.reshape(len(PLANES), P, -1) for F in flat], bounds, labels, sets[0], INNER[sets[1]], sets[2], sets[3],
                    bool(sets[4]), bool(sets[5]), bool(sets[6]), times, kern)

@@ -94,6 +94,39 @@ def _accumulator(out: torch.Tensor | None, shape: tuple, dtype, device, who: str
     return out
 
 
+def _check_bounds(bounds, T: int, who: str) -> list[int]:
+    """The P + 1 positions of the periods of a (T, m) block, as integers."""
+    b = [int(v) for v in np.asarray(bounds).reshape(-1)]
+    # here and not only in C: the int32 array of a launch would wrap what does not fit it
+    if len(b) < 2 or b[0] < 0 or b[-1] > T or any(y <= x for x, y in zip(b, b[1:])):
+        raise _lib.DmdxError(f"{who}: bounds must be at least 2 strictly ascending integers in 0 .. T = {T}")
+    return b
+
+
+def _check_threshold_table(thr, slot, m: int, T: int, device, max_thr: int, who: str, check_labels: bool):
+    """-> (thr3, J, S): ``thr`` as the contiguous (J, S, m) fp32 table of K24 and K27, J <= ``max_thr``; ``slot`` the
+    (T,) int32 labels on ``device``, or None for S = 1.  ``check_labels``: a device read, the labels must lie in
+    0 .. S - 1."""
+    if (not isinstance(thr, torch.Tensor) or thr.dtype != torch.float32 or thr.dim() not in (2, 3)
+            or thr.device != device or thr.shape[-1] != m or not thr.is_contiguous()):
+        raise _lib.DmdxError(f"{who}: thr must be a contiguous (J, S, {m}) or (J, {m}) fp32 tensor on {device}")
+    thr3 = thr if thr.dim() == 3 else thr.unsqueeze(1)
+    J, S = int(thr3.shape[0]), int(thr3.shape[1])
+    if not 1 <= J <= max_thr or S < 1:
+        raise _lib.DmdxError(f"{who}: {J} thresholds in {S} slots; 1 .. {max_thr} thresholds and at least one slot "
+                             f"asked for")
+    if slot is None:
+        if S != 1:
+            raise _lib.DmdxError(f"{who}: thr has {S} slots, so slot must name one per snapshot")
+    else:
+        _check_ivec(slot, device, who, "slot", T)
+        if check_labels:
+            lo, hi = int(slot.min()), int(slot.max())
+            if lo < 0 or hi >= S:
+                raise _lib.DmdxError(f"{who}: slot labels {lo} .. {hi} outside 0 .. {S - 1}")
+    return thr3, J, S
+
+
 class HipKernels:
     """The product kernel provider (libdmdx.so on the current CUDA/HIP device)."""
 
@@ -133,6 +166,28 @@ class HipKernels:
         if ws is None or ws.numel() < nbytes:
             self._ws[key] = ws = torch.empty(max(nbytes, 1), dtype=torch.uint8, device=device)
         return ws
+
+    def _per_period(self, name: str, entry: str, planes: torch.Tensor, paxis: int, b: list, maxp: int, mid: tuple,
+                    pieces_of, workspace_bytes, call) -> torch.Tensor:
+        """A per-period kernel (K27, K29) over the periods ``b`` in launches of at most ``maxp``, their bounds by value:
+        fills ``planes`` (periods along ``paxis``, rows last) and returns it.  ``pieces_of(length)``: the pieces of one
+        period; time is split, and ``workspace_bytes(host_b, n)`` asked for, only where a launch has more than one.
+        ``call(host_b, n, part, ws, nbytes)``: the C call ``entry`` for n periods into ``part``."""
+        P, m = len(b) - 1, int(planes.shape[-1])
+        for p0 in range(0, P, maxp):
+            n = min(maxp, P - p0)
+            cut = b[p0:p0 + n + 1]
+            part = planes if n == P else torch.empty(planes.shape[:paxis] + (n,) + planes.shape[paxis + 1:],
+                                                     dtype=planes.dtype, device=planes.device)
+            host_b = (ctypes.c_int32 * (n + 1))(*cut)
+            split = sum(pieces_of(y - x) for x, y in zip(cut, cut[1:])) > 1
+            nbytes = int(workspace_bytes(host_b, n)) if split else 0
+            ws = self._workspace(planes.device, nbytes) if split else None
+            rc = self._timed(name, (m, cut[-1] - cut[0], *mid, n), lambda: call(host_b, n, part, ws, nbytes))
+            _lib.check(rc, entry)
+            if part is not planes:
+                planes.narrow(paxis, p0, n).copy_(part)
+        return planes
 
     def release_workspace(self) -> int:
         """Drop the cached partial-tile workspaces (K1 / K3: 128 KB per (row block, K-split, tile)
@@ -508,22 +563,7 @@ class HipKernels:
         if B > self.exceed_max_members:
             raise _lib.DmdxError(f"{who}: {B} members, at most {self.exceed_max_members}")
         _check_vec(mean, m, Ut.device, who, "mean")
-        if (not isinstance(thr, torch.Tensor) or thr.dtype != torch.float32 or thr.dim() not in (2, 3)
-                or thr.device != Ut.device or thr.shape[-1] != m or not thr.is_contiguous()):
-            raise _lib.DmdxError(f"{who}: thr must be a contiguous (J, S, {m}) or (J, {m}) fp32 tensor on {Ut.device}")
-        thr3 = thr if thr.dim() == 3 else thr.unsqueeze(1)
-        J, S = int(thr3.shape[0]), int(thr3.shape[1])
-        if not 1 <= J <= self.exceed_max_thresholds or S < 1:
-            raise _lib.DmdxError(f"{who}: {J} thresholds in {S} slots; 1 .. {self.exceed_max_thresholds} thresholds and "
-                                 f"at least one slot asked for")
-        if slot is None:
-            if S != 1:
-                raise _lib.DmdxError(f"{who}: thr has {S} slots, so slot must name one per snapshot")
-        else:
-            _check_ivec(slot, Ut.device, who, "slot", T)
-            lo, hi = int(slot.min()), int(slot.max())
-            if lo < 0 or hi >= S:
-                raise _lib.DmdxError(f"{who}: slot labels {lo} .. {hi} outside 0 .. {S - 1}")
+        thr3, J, S = _check_threshold_table(thr, slot, m, T, Ut.device, self.exceed_max_thresholds, who, True)
         return m, k, ldu, T, B, Dt, ldc, thr3, J, S
 
     def exceed_prob(self, Ut: torch.Tensor, Cm: torch.Tensor, thr: torch.Tensor, slot: torch.Tensor | None = None,
@@ -1041,23 +1081,9 @@ class HipKernels:
             raise _lib.DmdxError(f"{who}: X must be (T, m), got {tuple(Xt.shape)}")
         T, m = int(Xt.shape[0]), int(Xt.shape[1])
         ldx = _check_snapshots(Xt, m, T, Xt.device, who)
-        if (not isinstance(thr, torch.Tensor) or thr.dtype != torch.float32 or thr.dim() not in (2, 3)
-                or thr.device != Xt.device or thr.shape[-1] != m or not thr.is_contiguous()):
-            raise _lib.DmdxError(f"{who}: thr must be a contiguous (J, S, {m}) or (J, {m}) fp32 tensor on {Xt.device}")
-        thr3 = thr if thr.dim() == 3 else thr.unsqueeze(1)
-        J, S = int(thr3.shape[0]), int(thr3.shape[1])
-        if not 1 <= J <= self.spell_max_thresholds or S < 1:
-            raise _lib.DmdxError(f"{who}: {J} thresholds in {S} slots; 1 .. {self.spell_max_thresholds} thresholds and at "
-                                 f"least one slot asked for")
-        if slot is None:
-            if S != 1:
-                raise _lib.DmdxError(f"{who}: thr has {S} slots, so slot must name one per snapshot")
-        else:
-            _check_ivec(slot, Xt.device, who, "slot", T)
-        b = [int(v) for v in np.asarray(bounds).reshape(-1)]
-        # here and not only in C: the int32 arrays below would wrap what does not fit them
-        if len(b) < 2 or b[0] < 0 or b[-1] > T or any(y <= x for x, y in zip(b, b[1:])):
-            raise _lib.DmdxError(f"{who}: bounds must be at least 2 strictly ascending integers in 0 .. T = {T}")
+        # (a label outside 0 .. S - 1 is no error here: its snapshot is invalid)
+        thr3, J, S = _check_threshold_table(thr, slot, m, T, Xt.device, self.spell_max_thresholds, who, False)
+        b = _check_bounds(bounds, T, who)
         ml = [int(v) for v in np.atleast_1d(np.asarray(min_len)).reshape(-1)]
         ab = [bool(v) for v in np.atleast_1d(np.asarray(above)).reshape(-1)]
         ml, ab = (ml * J if len(ml) == 1 else ml), (ab * J if len(ab) == 1 else ab)
@@ -1070,23 +1096,13 @@ class HipKernels:
             return planes
         mask = sum(1 << j for j in range(J) if ab[j])
         host_ml = (ctypes.c_int32 * J)(*ml)
-        maxp = self.spell_max_periods
-        for p0 in range(0, P, maxp):
-            n = min(maxp, P - p0)
-            part = planes if n == P else torch.empty((J, DMDX_SPELL_NQ, n, m), dtype=torch.int32, device=Xt.device)
-            host_b = (ctypes.c_int32 * (n + 1))(*b[p0:p0 + n + 1])
-            pieces = sum(-(-(y - x) // int(seg)) for x, y in zip(b[p0:p0 + n], b[p0 + 1:p0 + n + 1]))
-            split = pieces > 1
-            nbytes = int(self._lib.dmdx_spell_workspace_bytes(m, host_b, n, J, int(seg))) if split else 0
-            ws = self._workspace(Xt.device, nbytes) if split else None
-            rc = self._timed("spells", (m, b[p0 + n] - b[p0], J, n), lambda: self._lib.dmdx_spell_f32(
-                _ptr(Xt), m, T, ldx, _ptr(thr3), m, J, S, _ptr(slot), mask, host_ml, host_b, n, int(seg), _ptr(part), m, 0,
-                _ptr(ws), nbytes, self._stream()
-            ))
-            _lib.check(rc, "dmdx_spell_f32")
-            if part is not planes:
-                planes[:, :, p0:p0 + n] = part
-        return planes
+        seg = int(seg)
+        return self._per_period(
+            "spells", "dmdx_spell_f32", planes, 2, b, self.spell_max_periods, (J,), lambda n: -(-n // seg),
+            lambda hb, n: self._lib.dmdx_spell_workspace_bytes(m, hb, n, J, seg),
+            lambda hb, n, part, ws, nbytes: self._lib.dmdx_spell_f32(
+                _ptr(Xt), m, T, ldx, _ptr(thr3), m, J, S, _ptr(slot), mask, host_ml, hb, n, seg, _ptr(part), m, 0, _ptr(ws),
+                nbytes, self._stream()))
 
     # -- K29 ----------------------------------------------------------------
     @property
@@ -1120,10 +1136,7 @@ class HipKernels:
         T, m = int(Xt.shape[0]), int(Xt.shape[1])
         ldx = _check_snapshots(Xt, m, T, Xt.device, who)
         _check_vec(thr, m, Xt.device, who, "thr")
-        b = [int(v) for v in np.asarray(bounds).reshape(-1)]
-        # here and not only in C: the int32 array below would wrap what does not fit it
-        if len(b) < 2 or b[0] < 0 or b[-1] > T or any(y <= x for x, y in zip(b, b[1:])):
-            raise _lib.DmdxError(f"{who}: bounds must be at least 2 strictly ascending integers in 0 .. T = {T}")
+        b = _check_bounds(bounds, T, who)
         if inner not in PSTAT_INNER:
             raise _lib.DmdxError(f"{who}: inner = {inner!r}, expected one of {PSTAT_INNER}")
         g, w, seg = int(group), int(window), int(seg)
@@ -1137,23 +1150,12 @@ class HipKernels:
         if m == 0:
             return planes
         flags = (1 if below else 0) | (2 if inclusive else 0)
-        maxp = self.period_stats_max_periods
-        for p0 in range(0, P, maxp):
-            n = min(maxp, P - p0)
-            part = planes if n == P else torch.empty((DMDX_PSTAT_NQ, n, m), dtype=torch.float64, device=Xt.device)
-            host_b = (ctypes.c_int32 * (n + 1))(*b[p0:p0 + n + 1])
-            pieces = sum(-(-(-(-(y - x) // g)) // seg) for x, y in zip(b[p0:p0 + n], b[p0 + 1:p0 + n + 1]))
-            split = pieces > 1
-            nbytes = int(self._lib.dmdx_period_stats_workspace_bytes(m, host_b, n, g, seg)) if split else 0
-            ws = self._workspace(Xt.device, nbytes) if split else None
-            rc = self._timed("period_stats", (m, b[p0 + n] - b[p0], g, w, n), lambda: self._lib.dmdx_period_stats_f32(
-                _ptr(Xt), m, T, ldx, host_b, n, g, PSTAT_INNER.index(inner), w, mc, _ptr(thr), seg, _ptr(part), m, flags,
-                _ptr(ws), nbytes, self._stream()
-            ))
-            _lib.check(rc, "dmdx_period_stats_f32")
-            if part is not planes:
-                planes[:, p0:p0 + n] = part
-        return planes
+        return self._per_period(
+            "period_stats", "dmdx_period_stats_f32", planes, 1, b, self.period_stats_max_periods, (g, w),
+            lambda n: -(-(-(-n // g)) // seg), lambda hb, n: self._lib.dmdx_period_stats_workspace_bytes(m, hb, n, g, seg),
+            lambda hb, n, part, ws, nbytes: self._lib.dmdx_period_stats_f32(
+                _ptr(Xt), m, T, ldx, hb, n, g, PSTAT_INNER.index(inner), w, mc, _ptr(thr), seg, _ptr(part), m, flags,
+                _ptr(ws), nbytes, self._stream()))
 
     # -- K22 ----------------------------------------------------------------
     @property

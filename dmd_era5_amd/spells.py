@@ -31,9 +31,11 @@ from dataclasses import dataclass
 import numpy as np
 import torch
 
+from . import _periods as pp
 from . import _timeaxis as ta
-from .forecast import _check_weights, _group_pieces, _slot_labels, _threshold_tables
-from .labeled import Coord, DataArray, Dataset
+from ._periods import KINDS, periods_of
+from .forecast import _slot_labels, _threshold_tables
+from .labeled import Dataset
 from .svd import Comm, _kern
 
 __all__ = ["SEGMENT", "PLANES", "KINDS", "periods_of", "spell_blocks", "SpellStats"]
@@ -41,39 +43,7 @@ __all__ = ["SEGMENT", "PLANES", "KINDS", "periods_of", "spell_blocks", "SpellSta
 # the snapshots of a piece of the time split (HipKernels.spells); no result depends on it
 SEGMENT = 512
 PLANES = ("n_valid", "n_event", "n_spell", "n_in_spell", "longest", "first", "last")
-KINDS = ("year", "month", "season", "all")
-_SEASONS = ("DJF", "MAM", "JJA", "SON")
 _INDICES = ("frequency", "spell_count", "spell_days", "longest", "onset", "end")
-
-
-def periods_of(times, kind: str = "year"):
-    """Time stamps -> ``(bounds, labels)``: the P + 1 int32 positions that cut the snapshots into periods -- period p is
-    ``times[bounds[p]:bounds[p + 1]]`` -- and a label per period (a numpy array of strings).
-
-    ``kind``: ``"year"`` ("2001"), ``"month"`` ("2001-03"), ``"season"`` ("2001-DJF": December to February is labelled
-    by the year of its January; a season cut off at either end of the series is kept as it is) or ``"all"`` (one
-    period, "all").  The times must be strictly ascending, else a ValueError."""
-    if kind not in KINDS:
-        raise ValueError(f"periods_of: kind = {kind!r}, expected one of {KINDS}")
-    t = ta.stamps(times, "periods_of")
-    T = int(t.shape[0])
-    if T == 0:
-        raise ValueError("periods_of: no times")
-    if T > 1 and not (np.diff(t.astype("datetime64[ns]").astype(np.int64)) > 0).all():
-        raise ValueError("periods_of: times must be strictly ascending: a period is a run of consecutive snapshots")
-    months = t.astype("datetime64[M]").astype(np.int64)             # months since 1970-01
-    if kind == "all":
-        key, names = np.zeros(T, dtype=np.int64), lambda k: "all"
-    elif kind == "year":
-        key, names = months // 12, lambda k: f"{1970 + k:04d}"
-    elif kind == "month":
-        key, names = months, lambda k: f"{1970 + k // 12:04d}-{k % 12 + 1:02d}"
-    else:
-        key = (months + 1) // 3                                      # Dec, Jan, Feb share a value; 3 key is the January
-        names = lambda k: f"{1970 + (3 * k) // 12:04d}-{_SEASONS[k % 4]}"
-    cuts = np.flatnonzero(np.diff(key)) + 1
-    bounds = np.concatenate([[0], cuts, [T]]).astype(np.int32)
-    return bounds, np.array([names(int(key[b])) for b in bounds[:-1]])
 
 
 def _per_threshold(v, J, cast, who, name):
@@ -93,16 +63,6 @@ def _scalar_thresholds(thresholds):
     return None
 
 
-def _bounds_list(bounds, who):
-    raw = np.asarray(bounds)
-    if raw.ndim != 1 or raw.size < 2 or raw.dtype.kind not in "iu":
-        raise ValueError(f"{who}: bounds must be at least two integers, got {bounds!r}")
-    b = [int(v) for v in raw]
-    if b[0] < 0 or any(y <= x for x, y in zip(b, b[1:])):
-        raise ValueError(f"{who}: bounds must be >= 0 and strictly ascending, got {b[:8]}{' ...' if len(b) > 8 else ''}")
-    return b
-
-
 def spell_blocks(Xblocks, thresholds, bounds, min_length=1, above=True, slot=None, kern=None) -> list:
     """The planes of ``HipKernels.spells`` for every block of ``Xblocks`` ((T, rows) fp32 per block, any iterable
     consumed once): per block a (J, 7, P, rows) int32 tensor, the planes in the order of :data:`PLANES`.
@@ -114,7 +74,7 @@ def spell_blocks(Xblocks, thresholds, bounds, min_length=1, above=True, slot=Non
     ``slot``: the T slot labels in 0 .. S - 1 (``Climatology.slots(times)``), None for S = 1."""
     who = "spell_blocks"
     kern = _kern(kern)
-    b = _bounds_list(bounds, who)
+    b = pp.bounds_list(bounds, who)
     scal = _scalar_thresholds(thresholds)
     Xblocks = list(Xblocks) if scal is None else Xblocks
     if scal is None:
@@ -145,7 +105,7 @@ def spell_blocks(Xblocks, thresholds, bounds, min_length=1, above=True, slot=Non
 
 
 @dataclass
-class SpellStats:
+class SpellStats(pp.Periods):
     """The spell indices of a list of row blocks: ``planes`` holds one (J, 7, P, rows) int32 tensor per block
     (:func:`spell_blocks`), ``bounds`` the P + 1 positions of the periods, ``labels`` their names, ``times`` the T
     stamps (or None), ``min_length`` and ``above`` one value per threshold."""
@@ -167,16 +127,7 @@ class SpellStats:
         means ``climatology.quantile_thresholds()``, and whenever a climatology is given the slots are
         ``climatology.slots(times)``; without one ``slot`` names them."""
         who = "SpellStats.fit"
-        t = None if times is None else ta.stamps(times, who).astype("datetime64[ns]")
-        if isinstance(period, str):
-            if t is None:
-                raise ValueError(f"{who}: period = {period!r} needs times")
-            bounds, labels = periods_of(t, period)
-        else:
-            bounds = np.asarray(_bounds_list(period, who), dtype=np.int32)
-            labels = np.array([str(p) for p in range(bounds.shape[0] - 1)])
-            if t is not None and bounds[-1] > t.shape[0]:
-                raise ValueError(f"{who}: the bounds end at {int(bounds[-1])}, times has {t.shape[0]}")
+        t, bounds, labels = pp.resolve_periods(times, period, who)
         if climatology is not None:
             if t is None or slot is not None:
                 raise ValueError(f"{who}: a climatology takes its slots from times: pass times and no slot")
@@ -186,17 +137,7 @@ class SpellStats:
         if thresholds is None:
             raise ValueError(f"{who}: no thresholds (and no climatology with quantiles to take them from)")
         kern = _kern(kern)
-        seen = []
-
-        def checked():
-            for b, X in enumerate(Xblocks):
-                T = int(X.shape[0])
-                if t is not None and T != t.shape[0]:
-                    raise ValueError(f"{who}: block {b} holds {T} snapshots, times has {t.shape[0]}")
-                seen.append(T)
-                yield X
-
-        planes = spell_blocks(checked(), thresholds, bounds, min_length, above, slot, kern)
+        planes = spell_blocks(pp.checked_blocks(Xblocks, t, who), thresholds, bounds, min_length, above, slot, kern)
         if not planes:
             raise ValueError(f"{who}: no blocks")
         J = int(planes[0].shape[0])
@@ -207,10 +148,6 @@ class SpellStats:
     @property
     def n_thresholds(self) -> int:
         return len(self.min_length)
-
-    @property
-    def n_periods(self) -> int:
-        return int(self.bounds.shape[0]) - 1
 
     def period_lengths(self) -> np.ndarray:
         """The snapshots of every period, (P,) int64."""
@@ -227,11 +164,7 @@ class SpellStats:
 
     def frequency(self) -> list:
         """n_event / n_valid per block, (J, P, rows) fp64; NaN where no snapshot of the period is valid."""
-        out = []
-        for Q in self.planes:
-            nv, ne = Q[:, 0].to(torch.float64), Q[:, 1].to(torch.float64)
-            out.append(torch.where(nv > 0, ne / nv.clamp(min=1.0), torch.full_like(nv, float("nan"))))
-        return out
+        return [pp.ratio(Q[:, 1].to(torch.float64), Q[:, 0].to(torch.float64)) for Q in self.planes]
 
     def spell_count(self) -> list:
         """The runs of at least ``min_length`` events, (J, P, rows) int32."""
@@ -245,29 +178,17 @@ class SpellStats:
         """The longest run of events, qualifying or not (CDD / CWD in snapshots); 0 where there is none."""
         return self._plane("longest")
 
-    def _when(self, name: str, as_time: bool, who: str) -> list:
-        off = self._plane(name)
-        if not as_time:
-            return off
-        if self.times is None:
-            raise ValueError(f"SpellStats.{who}: fitted without times: only the offsets are known")
-        start = self.bounds[:-1].astype(np.int64)[None, :, None]
-        out = []
-        for o in off:
-            o = o.cpu().numpy().astype(np.int64)
-            when = self.times[np.where(o >= 0, start + o, 0)]
-            when[o < 0] = np.datetime64("NaT")
-            out.append(when)
-        return out
+    def _offsets(self, name: str, as_time: bool, who: str) -> list:
+        return self._when(self._plane(name), 1, who) if as_time else self._plane(name)
 
     def onset(self, as_time: bool = False) -> list:
         """Where the first qualifying run of the period starts: the offset from the period's first snapshot, (J, P,
         rows) int32, -1 where there is none; ``as_time``: the stamps instead (numpy datetime64, NaT where none)."""
-        return self._when("first", as_time, "onset")
+        return self._offsets("first", as_time, "onset")
 
     def end(self, as_time: bool = False) -> list:
         """Where the last qualifying run of the period ends (its last snapshot), as :meth:`onset`."""
-        return self._when("last", as_time, "end")
+        return self._offsets("last", as_time, "end")
 
     # -- over the grid --------------------------------------------------------------------------------------------
     def area_mean(self, index: str, weights=None, groups=None, comm: Comm | None = None,
@@ -285,37 +206,9 @@ class SpellStats:
         who = "SpellStats.area_mean"
         if index not in _INDICES:
             raise ValueError(f"{who}: index = {index!r}, expected one of {_INDICES}")
-        comm = comm or Comm()
-        weights = _check_weights(weights, who)
-        rows_of = [int(Q.shape[3]) for Q in self.planes]
-        if weights is not None and len(weights) != len(rows_of):
-            raise ValueError(f"{who}: {len(weights)} weight vectors for {len(rows_of)} blocks")
-        pieces, G = _group_pieces(groups, rows_of, [1] * len(rows_of), n_groups, who)
-        J, P = self.n_thresholds, self.n_periods
-        values = {"frequency": self.frequency, "spell_count": self.spell_count, "spell_days": self.spell_days,
-                  "longest": self.longest, "onset": self.onset, "end": self.end}[index]()
-        device = self.planes[0].device if self.planes else torch.device("cpu")
-        # (J, P) numbers per row: reduced on the host, in one order whatever the device
-        sums = torch.zeros((3, G, J, P), dtype=torch.float64)
-        for b, (Q, val) in enumerate(zip(self.planes, values)):
-            w = torch.ones(rows_of[b], dtype=torch.float64) if weights is None else \
-                torch.as_tensor(weights[b]).to(device="cpu", dtype=torch.float64).reshape(-1)
-            if w.numel() != rows_of[b]:
-                raise ValueError(f"{who}: weights[{b}] has {w.numel()} entries, the block {rows_of[b]} rows")
-            val = val.cpu().to(torch.float64)
-            keep = (w != 0)[None, None] & (Q[:, 0].cpu() > 0)
-            if index in ("onset", "end"):
-                keep = keep & (val >= 0)
-            ww = torch.where(keep, w[None, None].expand_as(val), torch.zeros_like(val))
-            wv = torch.where(keep, ww * val, torch.zeros_like(val))
-            for s, e, g in pieces[b]:
-                sums[0, g] += wv[:, :, s:e].sum(dim=2)
-                sums[1, g] += ww[:, :, s:e].sum(dim=2)
-                sums[2, g] += keep[:, :, s:e].sum(dim=2)
-        sums = comm.allreduce_sum_(sums.reshape(-1).to(device), tag="spell_allreduce").cpu().reshape(3, G, J, P)
-        W = sums[1]
-        mean = torch.where(W > 0, sums[0] / torch.where(W > 0, W, torch.ones_like(W)), torch.full_like(W, float("nan")))
-        return {"mean": mean, "weight": W, "rows": sums[2].to(torch.int64)}
+        values = getattr(self, index)()
+        extra = (lambda v: v >= 0) if index in ("onset", "end") else None
+        return pp.area_mean_sums(self.n_valid(), values, extra, weights, groups, n_groups, comm, "spell_allreduce", who)
 
     # -- persistence ----------------------------------------------------------------------------------------------
     def to_dataset(self, coords=None) -> Dataset:
@@ -324,24 +217,8 @@ class SpellStats:
         seconds since 1970 and the nanoseconds beyond; absent without times) and the attribute ``period_labels``
         (the labels joined by commas); ``coords``: the per-row coordinates of the decomposed array, taken over as they
         are.  ``io_netcdf.to_netcdf`` writes it."""
-        J, P = self.n_thresholds, self.n_periods
-        cds = {"plane": Coord("plane", np.arange(J * len(PLANES) * P, dtype=np.int64)),
-               "bound": Coord("bound", np.arange(P + 1, dtype=np.int64)),
-               "threshold": Coord("threshold", np.arange(J, dtype=np.int64)), **ta.row_coords(coords)}
-        ds = Dataset(coords=cds, attrs={"period_labels": ",".join(str(v) for v in self.labels)})
-        row = {k: v for k, v in cds.items() if k not in ("plane", "bound", "threshold")}
-        field = np.concatenate([Q.detach().cpu().numpy().reshape(J * len(PLANES) * P, -1) for Q in self.planes], axis=1)
-        ds["spell_planes"] = DataArray(field.astype(np.int32), ("plane", "space"), {"plane": cds["plane"], **row})
-        ds["period_bound"] = DataArray(self.bounds.astype(np.int64), ("bound",), {"bound": cds["bound"]})
-        ds["min_length"] = DataArray(np.asarray(self.min_length, dtype=np.int64), ("threshold",), {"threshold": cds["threshold"]})
-        ds["above"] = DataArray(np.asarray(self.above, dtype=np.int64), ("threshold",), {"threshold": cds["threshold"]})
-        if self.times is not None:
-            ns = self.times.astype("datetime64[ns]").astype(np.int64)
-            tc = Coord("time_index", np.arange(ns.shape[0], dtype=np.int64))
-            ds.coords["time_index"] = tc
-            ds["time_s"] = DataArray(ns // 10**9, ("time_index",), {"time_index": tc})
-            ds["time_ns"] = DataArray(ns % 10**9, ("time_index",), {"time_index": tc})
-        return ds
+        return pp.to_dataset("spell_planes", self.planes, np.int32, self.bounds, self.labels, self.times, coords, "threshold",
+                             {"min_length": self.min_length, "above": self.above})
 
     @classmethod
     def from_dataset(cls, ds: Dataset, rows=None, device=None, kern=None) -> "SpellStats":
@@ -350,19 +227,12 @@ class SpellStats:
         the HIP provider)."""
         who = "SpellStats.from_dataset"
         kern = _kern(kern)
-        field = np.ascontiguousarray(np.asarray(ds["spell_planes"].values), dtype=np.int32)
-        bounds = np.asarray(ds["period_bound"].values).astype(np.int32).reshape(-1)
+        field, bounds, labels, times = pp.from_dataset(ds, "spell_planes", np.int32)
         ml = tuple(int(v) for v in np.asarray(ds["min_length"].values).reshape(-1))
         ab = tuple(bool(v) for v in np.asarray(ds["above"].values).reshape(-1))
         J, P = len(ml), int(bounds.shape[0]) - 1
         if field.shape[0] != J * len(PLANES) * P or len(ab) != J:
             raise ValueError(f"{who}: spell_planes holds {field.shape[0]} planes, {J} thresholds and {P} periods ask for "
                              f"{J * len(PLANES) * P}")
-        text = ta.attr_str(ds.attrs["period_labels"]) if "period_labels" in ds.attrs else ""
-        labels = np.array(text.split(",")) if text else np.array([str(p) for p in range(P)])
-        times = None
-        if "time_s" in ds:
-            s = np.asarray(ds["time_s"].values).astype(np.int64).reshape(-1)
-            times = (s * 10**9 + np.asarray(ds["time_ns"].values).astype(np.int64).reshape(-1)).astype("datetime64[ns]")
         flat = ta.cut_rows(field, rows, device, kern, who)
         return cls([F.reshape(J, len(PLANES), P, -1) for F in flat], bounds, labels, ml, ab, times, kern)
