@@ -135,6 +135,13 @@ SIGNATURES = {
     "dmdx_varimax_workspace_bytes": (_sz, [_i64, _i64]),
     "dmdx_varimax_step_f32": (C.c_int, [_p, _i64, _i64, _i64, _p, _i64, _p, _p, _i64, _p, _p, C.c_int, _p, _sz, _p]),
     "dmdx_row_norms_f32": (C.c_int, [_p, _i64, _i64, _i64, _p, _p, _p]),
+    "dmdx_gap_mask_segment": (C.c_int, []),
+    "dmdx_gap_mask_workspace_bytes": (_sz, [_i64, _i64]),
+    "dmdx_gap_mask_f32": (C.c_int, [_p, _i64, _i64, _i64, _p, _i64, _p, _p, _i64, _p, _sz, _p]),
+    "dmdx_gap_standardize_f32": (C.c_int, [_p, _i64, _i64, _i64, _p, _i64, _p, _p, C.c_int, _p]),
+    "dmdx_gap_fill_max_k": (C.c_int, []),
+    "dmdx_gap_fill_workspace_bytes": (_sz, [_i64, _i64, _i64]),
+    "dmdx_gap_fill_f32": (C.c_int, [_p, _i64, _i64, _i64, _p, _i64, _i64, _p, _p, _p, _i64, _p, _i64, _p, _p, _sz, _p]),
     "dmdx_pack_triu_f64": (C.c_int, [_p, _i64, _i64, _p, _p]),
     "dmdx_unpack_triu_f64": (C.c_int, [_p, _i64, _p, _i64, _p]),
     "dmdx_exp_basis": (C.c_int, [_p, _p, _i64, _i64, _p, _p, C.c_int, _p]),

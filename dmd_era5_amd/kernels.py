@@ -1315,6 +1315,78 @@ class HipKernels:
         _lib.check(rc, "dmdx_row_mask_apply_f32")
         return Xt
 
+    # -- K31 ----------------------------------------------------------------
+    @property
+    def gap_fill_max_k(self) -> int:
+        return int(self._lib.dmdx_gap_fill_max_k())
+
+    @property
+    def gap_mask_segment(self) -> int:
+        """Snapshots of one fp64 chain of ``gap_mask``'s sums (part of their bits)."""
+        return int(self._lib.dmdx_gap_mask_segment())
+
+    @staticmethod
+    def _gap_words(W, m: int, T: int, device, who: str) -> int:
+        """The packed mask of a (T, m) block: (ceil(T / 32), m) int32 on `device` (inner stride 1) -> ldw."""
+        return _check_field(W, m, -(-T // 32), torch.int32, device, who, "W", " int32")
+
+    def gap_mask(self, Xt: torch.Tensor, want_sums: bool = True, split: bool = True):
+        """The gaps of a block.  Xt: (T, m) fp32 (any row stride >= m) -> (W, nmiss, sums): ``W`` the
+        (ceil(T / 32), m) int32 words, bit b of W[tw, i] set where Xt[32 tw + b, i] is not finite (NaN of any payload,
+        +-Inf; tested on the bits); ``nmiss`` (m,) int32 the gaps per row; ``sums`` (2, m) fp64 the sum and the sum of
+        squares of the finite values of every row (None without ``want_sums``), summed in segments of
+        :attr:`gap_mask_segment` snapshots.  ``split`` False lets one lane walk all segments of its row instead of
+        spreading them over the launch: the same bits.  One read of Xt."""
+        m, T, ldx = _check_mat(Xt, torch.float32, "gap_mask X")
+        dev = Xt.device
+        W = torch.empty((-(-T // 32), m), dtype=torch.int32, device=dev)
+        nmiss = torch.empty(m, dtype=torch.int32, device=dev)
+        sums = torch.empty((2, m), dtype=torch.float64, device=dev) if want_sums else None
+        use_ws = bool(split) and T > self.gap_mask_segment
+        nbytes = int(self._lib.dmdx_gap_mask_workspace_bytes(m, T)) if use_ws else 0
+        ws = self._workspace(dev, nbytes) if use_ws else None
+        rc = self._timed("gap_mask", (m, T), lambda: self._lib.dmdx_gap_mask_f32(
+            _ptr(Xt), m, T, ldx, _ptr(W), m, _ptr(nmiss), _ptr(sums), m, _ptr(ws), nbytes, self._stream()
+        ))
+        _lib.check(rc, "dmdx_gap_mask_f32")
+        return W, nmiss, sums
+
+    def gap_standardize_(self, Xt: torch.Tensor, W: torch.Tensor | None, mean: torch.Tensor | None,
+                         std: torch.Tensor | None, back: bool = False) -> torch.Tensor:
+        """In place.  Forward: an element whose bit of ``W`` is set becomes +0.0, every other
+        ``fl(fl(x - mean) / std)`` (what ``row_center_scale_`` leaves for the same moments).  ``back``: every element
+        becomes ``fl(fl(x std) + mean)`` and ``W`` is not looked at.  mean / std: (m,) fp32 or None (0 and 1). -> Xt."""
+        m, T, ldx = _check_mat(Xt, torch.float32, "gap_standardize X")
+        ldw = m if W is None else self._gap_words(W, m, T, Xt.device, "gap_standardize")
+        for v, name in ((mean, "mean"), (std, "std")):
+            _check_vec(v, m, Xt.device, "gap_standardize", name)
+        rc = self._timed("gap_standardize", (m, T), lambda: self._lib.dmdx_gap_standardize_f32(
+            _ptr(Xt), m, T, ldx, _ptr(W), ldw, _ptr(mean), _ptr(std), int(bool(back)), self._stream()
+        ))
+        _lib.check(rc, "dmdx_gap_standardize_f32")
+        return Xt
+
+    def gap_fill_(self, Ut: torch.Tensor, Ct: torch.Tensor, W: torch.Tensor, Xt: torch.Tensor,
+                  mean: torch.Tensor | None = None, std: torch.Tensor | None = None, want_change: bool = True):
+        """In place: Xt = mean + std * (U C) where the bit of ``W`` is set -- bit for bit what :meth:`expand` stores
+        there -- and Xt neither read nor written where it is clear.  Ut: (k, m), Ct: (T, k), Xt: (T, m) fp32, W the
+        words of :meth:`gap_mask` -> ``change_row`` (m,) fp64, sum_t bit (new - old)^2, or None without
+        ``want_change``."""
+        m, k, ldu, T, Ct, ldc = self._expand_args(Ut, Ct, mean, std, "gap_fill")
+        ldx = _check_snapshots(Xt, m, T, Ut.device, "gap_fill")
+        if ldx < m:
+            raise _lib.DmdxError("gap_fill: X must not be a delay view")
+        ldw = self._gap_words(W, m, T, Ut.device, "gap_fill")
+        change = torch.empty(m, dtype=torch.float64, device=Ut.device) if want_change else None
+        nbytes = int(self._lib.dmdx_gap_fill_workspace_bytes(m, k, T)) if want_change else 0
+        ws = self._workspace(Ut.device, nbytes) if want_change else None
+        rc = self._timed("gap_fill", (m, k, T), lambda: self._lib.dmdx_gap_fill_f32(
+            _ptr(Ut), m, k, ldu, _ptr(Ct), ldc, T, _ptr(mean), _ptr(std), _ptr(W), ldw, _ptr(Xt), ldx, _ptr(change),
+            _ptr(ws), nbytes, self._stream()
+        ))
+        _lib.check(rc, "dmdx_gap_fill_f32")
+        return change
+
     # -- K6 -----------------------------------------------------------------
     def delay_shift_sum(self, G64: torch.Tensor, d: int, want32: bool = False):
         """Gd[i, j] = sum_{k<d} G[i+k, j+k]."""

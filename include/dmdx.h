@@ -73,6 +73,15 @@
  *   - K24 (dmdx_exceed_prob_f32, dmdx_exceed_score_f32): as K19, with thr (m x (J S)) and slot (T) only read, inside
  *     their logical elements and, for thr, only in the columns slot names; every logical element of the J planes of
  *     P, of row and -- with accumulate == 0 -- of col and cnt is written, nothing else.
+ *   - K31 (dmdx_gap_mask_f32, dmdx_gap_standardize_f32, dmdx_gap_fill_f32): the mask W is ceil(T / 32) columns of m
+ *     uint32 words (ldw); the delay view (rows > ldx) is refused by all three.  mask: X is only read, every logical
+ *     word of W and -- when given -- every element of nmiss and sums is written, nothing else.  standardize: every
+ *     logical element of X is read and written, W, mu and sigma are only read.  fill: U, C, mu, sigma and W are only
+ *     read, inside their logical elements; X is read (only when change_row is given) and written EXACTLY at the
+ *     elements whose bit is set, with row < m and snapshot < T: an element with a clear bit is neither read nor
+ *     written, the bits of the last word from snapshot T on are ignored; every element of change_row is written.  No
+ *     alignment is asked for: a 16-byte aligned X with ldx % 4 == 0 selects 16-byte accesses in mask and standardize, a
+ *     16-byte aligned C with ldc % 4 == 0 16-byte staging in fill, with the same bits.
  *
  * Value contract (tests/test_gpu_value_domain.py holds every fp32 entry point to it)
  *   - NaN / Inf propagate like IEEE arithmetic on the logical operands, nothing more and nothing less:
@@ -141,6 +150,16 @@
  *     for bit |Xhat| of dmdx_expand_f32(U, D, mu = NULL, sigma).  Integer U and D with every P_b^2 summed below 2^24
  *     and sigma a power of two give the integer V, var_col and var_row bit for bit (S = |sigma| sqrt(V) correctly
  *     rounded); (2^e U, 2^-e D) leaves every output bit unchanged (magnitudes as above).
+ *     K31: a gap is an element whose exponent bits are all ones (every NaN payload, +-Inf); denormals, +-0 and
+ *     +-FLT_MAX are finite.  mask: nmiss and sums of row i depend on row i alone, and sums are always finite for fp32
+ *     input (fp64 sums of at most 2^31 finite fp32 values and squares).  standardize forward: a set bit gives +0.0
+ *     whatever X holds; a clear bit gives fl(fl(x - mu) / sigma), K13's xt (sigma[i] = 0: +-Inf or NaN in row i alone).
+ *     fill is K12 restricted to the set bits: the stored value is bit for bit what dmdx_expand_f32 stores there, so a
+ *     non-finite U[i, j], mu[i] or sigma[i] reaches exactly the set-bit elements of row i and change_row[i], a
+ *     non-finite C[j, t] the set-bit elements of column t and the change_row of their rows; a non-finite old value at a
+ *     set bit makes change_row[i] non-finite and nothing else.  A tile or workgroup without a set bit is skipped and
+ *     contributes exact +0.0.  Integer U, C, mu, sigma and X with every intermediate below 2^24 give the integer
+ *     change_row bit for bit.
  */
 #ifndef DMDX_H
 #define DMDX_H
@@ -1110,6 +1129,49 @@ int dmdx_varimax_step_f32(const float* U, int64_t m, int64_t k, int64_t ldu, con
                           double* G, int64_t ldg, double* q, double* f, int accumulate, void* workspace,
                           size_t workspace_bytes, void* stream);
 int dmdx_row_norms_f32(const float* U, int64_t m, int64_t k, int64_t ldu, const float* cscale, float* h, void* stream);
+
+/* ---- K31: DINEOF gap filling -- the packed mask of the gaps, the standardised block, the rank-k field at the gaps ----
+ * The mask is one bit per element, packed along time in words of K12's tile width: W[tw ldw + i] bit b <=> element
+ * (i, 32 tw + b) is a gap, tw < ceil(T / 32), i < m, ldw >= m.  X: m x T fp32 (ldx >= m: no delay view).
+ *
+ * dmdx_gap_mask_f32: one read of X.  W: every logical word is written; the bit is K20's test of the bit pattern
+ * (exponent all ones); bits at snapshots >= T are 0.  nmiss (int32, m entries, nullable): the gaps of every row,
+ * overwritten.  sums (fp64, 2 x m, ldsum >= m, nullable): per row the sum (plane 0) and the sum of squares (plane 1) of
+ * the FINITE values.  Per segment of dmdx_gap_mask_segment() (1024) snapshots one fp64 chain in ascending t from +0.0;
+ * the segment results are added in ascending order; a square is the (exact) fp64 product of the converted value.  The
+ * bits depend on (X, T) only: with a workspace of dmdx_gap_mask_workspace_bytes(m, T) the segments are spread over the
+ * launch and a combine kernel adds their partials in order, with workspace == NULL one lane walks all segments of its
+ * row.  m == 0 or T == 0 returns 0 and touches nothing.
+ *
+ * dmdx_gap_standardize_f32: in place, one read and one write.  mu, sigma: m floats each, nullable (0 and 1).
+ *   back == 0: an element with its bit set becomes +0.0, every other fl(fl(x - mu[i]) / sigma[i]) (K13's xt, what K5
+ *              leaves for the same moments); W nullable = no gaps.
+ *   back != 0: every element becomes fl(fl(x sigma[i]) + mu[i]) (K12's two roundings); W is ignored.
+ *
+ * dmdx_gap_fill_f32: K12's field mu + sigma (U C) (U: m x k, C: k x T, 1 <= k <= dmdx_gap_fill_max_k() = 256) stored
+ * into X where the bit is set, bit for bit what dmdx_expand_f32 stores at (i, t) for the same operands; where the bit is
+ * clear X is neither read nor written.  change_row (m doubles, nullable, always overwritten) = sum_t bit (new - old)^2,
+ * old loaded only at set bits: one rounded subtraction, one rounded square, fp32 over the 16 values of a lane in a
+ * tile, fp64 over tiles and T splits in an order that is a function of (m, T); no atomics.  The workspace
+ * (dmdx_gap_fill_workspace_bytes) is needed only with change_row.  A wave whose 32 words of a tile are zero skips the
+ * MFMA chain and the epilogue of the tile, a workgroup whose words are all zero returns before it loads its panel of U:
+ * neither changes a result.
+ *
+ * A refused call (DMDX_E_INVALID: a null X, W, U or C; a negative size; k outside 1 .. 256; ldx, ldw, ldu or ldsum < m,
+ * ldc < k; any size or leading dimension >= 2^31; a pointer not aligned to its element; DMDX_E_WORKSPACE: a short
+ * workspace, or a null one where change_row is given) has written nothing and made no HIP call; dmdx_last_error() names
+ * the entry point.  m == 0 or T == 0 returns 0 after the checks without a launch. */
+int dmdx_gap_mask_segment(void);
+size_t dmdx_gap_mask_workspace_bytes(int64_t m, int64_t T);
+int dmdx_gap_mask_f32(const float* X, int64_t m, int64_t T, int64_t ldx, uint32_t* W, int64_t ldw, int32_t* nmiss,
+                      double* sums, int64_t ldsum, void* workspace, size_t workspace_bytes, void* stream);
+int dmdx_gap_standardize_f32(float* X, int64_t m, int64_t T, int64_t ldx, const uint32_t* W, int64_t ldw, const float* mu,
+                             const float* sigma, int back, void* stream);
+int dmdx_gap_fill_max_k(void);
+size_t dmdx_gap_fill_workspace_bytes(int64_t m, int64_t k, int64_t T);
+int dmdx_gap_fill_f32(const float* U, int64_t m, int64_t k, int64_t ldu, const float* C, int64_t ldc, int64_t T,
+                      const float* mu, const float* sigma, const uint32_t* W, int64_t ldw, float* X, int64_t ldx,
+                      double* change_row, void* workspace, size_t workspace_bytes, void* stream);
 
 /* ---- upper triangle of a symmetric fp64 matrix <-> packed row by row ---------------------
  * packed[i (2n - i + 1) / 2 + (j - i)] = A[i][j], j >= i: what the Gram all-reduce of the
