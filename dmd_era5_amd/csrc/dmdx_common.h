@@ -57,6 +57,11 @@ __device__ __forceinline__ float dmdx_ld_sc1_f32(__amdgpu_buffer_rsrc_t rs, int 
 }
 #endif
 
+// K1p (plane_split.hip): the bf16 plane images of one aligned K x n block (plane_image.h); `fits`: its
+// flat grid, ceil(chunks / 4) runs x panels workgroups, stays below 2^31
+bool dmdx_plane_split_fits(int64_t K, int64_t n);
+int dmdx_plane_split_launch(const float* X, int64_t K, int64_t n, int64_t ldx, void* out, hipStream_t st);
+
 // K2, 16x16x4 body (skinny16.hip): l <= 256 columns in one pass, 16-column granular, optional fused Gram
 bool dmdx_skinny16_shape_ok(int64_t m, int64_t ldx);
 int dmdx_skinny16_launch(const float* X, int64_t m, int64_t n, int64_t ldx, const float* W, int64_t ldw, int l, float* Y,

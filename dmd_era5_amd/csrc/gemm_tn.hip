@@ -54,6 +54,8 @@
 // launch) and dmdx_syrk_f32 / dmdx_gemm_tn_f32 (one pair of operands: a batch of one block).  One
 // path for all four: tn_refusal, run_batch, syrk_batch_kernel (body tn_unit), and the reduce kernel
 // that sums the K-splits; dmdx_gemm_tn_blocks_f32 alone also takes the small-l kernel (K3s).
+// dmdx_syrk_blocks_planes_f32 is dmdx_syrk_blocks_f32 with the bf16 planes of K1's full tiles made once per call
+// (plane_split.hip) and streamed by the fast pass (tn_unit_planes, PL = 2; the units it marks run again as PL = 3).
 // Environment knobs (tuning / A-B only, no result changes beyond rounding): DMDX_TN_MAX_CPS (chunks
 // per unit, default 2048), DMDX_TN_ROUNDS (rounds of 512 workgroups the K-splits aim at),
 // DMDX_TN_FORCE_TM, DMDX_TN_NO_TAILFIT, DMDX_NO_K3S, DMDX_K3S_32, DMDX_K1_ARITH (f32: K1 on the fp32 MFMA).  The timing-only ablations of
@@ -69,6 +71,7 @@
 
 #include "bf16_split.h"
 #include "dmdx_common.h"
+#include "plane_image.h"
 
 thread_local unsigned long long* dmdx_clock_probe_ptr = nullptr;  // dmdx_set_clock_probe (measurement aid)
 
@@ -126,6 +129,7 @@ struct TnBatch {
   int unit_begin[MAXB + 1];
   int slab_begin[MAXB + 1];
   int nblocks;
+  const unsigned char* planes[MAXB];   // PL = 2 only: the first plane image of block j (plane_image.h)
   // measurement aid (dmdx_set_clock_probe; null on the product path): every workgroup adds the
   // core-clock cycles and the 100 MHz reference ticks of its lifetime and 1 to clk[0..2]
   unsigned long long* clk;
@@ -739,7 +743,9 @@ __device__ __forceinline__ void tn_unit(const TnParams& p, const int split, cons
 #endif
       }
     };
-    plane_pass(std::false_type{});
+    // (PL = 3, the rerun launch behind the plane-fed fast pass: tn_unit_planes has run the unit on the fast planes and
+    // raised the alarm; the class-safe pass alone, from the same prologue)
+    if constexpr (PL != 3) plane_pass(std::false_type{});
     // ---- the verdict, once per unit.  The fast planes of an Inf or NaN carry a NaN in l (Inf - Inf), and l h' and
     // h' l are contracted for every pair: every output that a non-finite input of this K-range feeds holds NaN by
     // now, whatever its partners were (NaN * 0 included), and the fold kept it.  No NaN in acc + acc2: the fast
@@ -753,7 +759,7 @@ __device__ __forceinline__ void tn_unit(const TnParams& p, const int split, cons
       for (int ni = 0; ni < NI; ++ni)
 #pragma unroll
         for (int r = 0; r < 16; ++r) nan_ |= bf16split::alarm(acc[mi][ni][r] + acc2[mi][ni][r]);
-    if (__builtin_amdgcn_ballot_w64(nan_) != 0ull) *alarm_word = 1;
+    if (PL == 3 || __builtin_amdgcn_ballot_w64(nan_) != 0ull) *alarm_word = 1;   // (PL = 3: the verdict has been given)
     __syncthreads();   // (also: every wave is done with the stages of the fast pass)
     if (__builtin_amdgcn_readfirstlane(*alarm_word) != 0) {
 #pragma unroll
@@ -887,6 +893,196 @@ __device__ __forceinline__ void tn_unit(const TnParams& p, const int split, cons
 #undef DMDX_BLOCK_OFF
 }
 
+// The plane-fed fast pass of K1 (syrk_batch_kernel with PL = 2; aligned blocks whose planes dmdx_syrk_blocks_planes_f32
+// has made, plane_image.h): the fast pass of tn_unit's plane k-step with the split taken out of the loop.  The unit's
+// two panels are two contiguous streams of 16-k groups (12 288 bytes each: 128 columns x 3 planes x 2 lane halves x 16
+// bytes); LDS holds a ring of three stages of one A and one B group (24 KB each, 72 KB: what the fp32 stages and the
+// parked offsets take).  Every wave copies a quarter of both groups of a stage with six LDS-DMA instructions whose lane
+// offset is the constant 16 lane, and reads its 12 MFMA operands of a group (2 + 2 blocks of 32 columns x 3 planes)
+// straight from LDS, one ds_read_b128 each: a wave-instruction reads 1 KiB in lane order, no swizzle anywhere.
+// Group q: [operands in registers] 12 MFMAs (h h, h l, l h) -- wait for this wave's pieces of group q + 1, barrier
+// (every wave's pieces of q + 1 have landed, every wave holds its operands of q: the stage of q is free) -- LDS-DMA of
+// group q + 3 into the stage of q -- operand reads of q + 1 into the other register set -- 12 MFMAs (h m, m h, m m).
+// A group is loaded three groups ahead and waited for two groups after its issue: 48 MFMAs of 32 cycles of this wave,
+// about 3000 cycles with the SIMD's second wave issuing as many, against 1000 - 2000 of an HBM miss.
+// The arithmetic is tn_unit's to the bit: the same planes (the pre-split kernel runs split2_fast; the padding of the
+// images holds the zero planes the tail chunk's zero rows give -- and zero planes where tn_unit repeats the last
+// column, which only feeds outputs the reduce kernel never stores and, being a copy, never changes the verdict), the
+// same 24 MFMAs per group in the same order into the same accumulators, every chunk from the constant 0, the fold after
+// every chunk, the same verdict.  A unit whose verdict is the alarm commits nothing but a NaN in the first element of its
+// partial tile (a committed tile of a unit without alarm holds none): the rerun launch behind this one (PL = 3) runs
+// exactly the marked units again from raw X on the class-safe planes (tn_unit with PL = 3: its prologue and its
+// plane_pass(std::true_type{}), the fast pass and the verdict compiled out) and commits that.
+// (Two launches and not one kernel: with tn_unit inlined behind this pass the register allocator spilled the class-safe
+// loop, 216 bytes per lane; a launch whose workgroups read one word and leave costs some tens of microseconds.)
+__device__ __forceinline__ void tn_unit_planes(const TnParams& p, const unsigned char* planes, const int split, const int row0_,
+                                               const int col0_, double* Pt, float* lds_f) {
+  constexpr unsigned HALF = 12288u, STAGE = 2u * HALF;   // bytes: one group of a panel; one ring stage (A group, B group)
+  const int row0 = __builtin_amdgcn_readfirstlane(row0_), col0 = __builtin_amdgcn_readfirstlane(col0_);
+  const int c_begin = split * p.chunks_per_split;
+  int c_end = c_begin + p.chunks_per_split;
+  if (c_end > p.chunks_total) c_end = p.chunks_total;
+  const int nchunks = c_end - c_begin;
+  const int tid = threadIdx.x;
+  const int lane = tid & 63;
+  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+  const int wr = wave >> 1, wc = wave & 1;
+
+  f32x16 acc[2][2], acc2[2][2];
+#pragma unroll
+  for (int mi = 0; mi < 2; ++mi)
+#pragma unroll
+    for (int ni = 0; ni < 2; ++ni)
+#pragma unroll
+      for (int r = 0; r < 16; ++r) acc[mi][ni][r] = acc2[mi][ni][r] = 0.f;
+  auto commit = [&]() {
+    const int ln = lane_now();
+    double* q_ = Pt + (64 * wr + 4 * (ln >> 5)) * BT + 64 * wc + (ln & 31);
+#pragma unroll
+    for (int mi = 0; mi < 2; ++mi)
+#pragma unroll
+      for (int ni = 0; ni < 2; ++ni)
+#pragma unroll
+        for (int r = 0; r < 16; ++r)
+          __builtin_nontemporal_store((double)(acc[mi][ni][r] + acc2[mi][ni][r]),
+                                      q_ + (32 * mi + (r & 3) + 8 * (r >> 2)) * BT + 32 * ni);
+  };
+  if (nchunks <= 0) {  // empty split: the partial tile must still be defined
+    commit();
+    return;
+  }
+
+  unsigned char* const lds = reinterpret_cast<unsigned char*>(lds_f);
+  int* const alarm_word = reinterpret_cast<int*>(lds + 3 * STAGE);
+  *alarm_word = 0;
+  // ---- the two streams of this wave's quarter: group q of the unit at + q * HALF
+  const int64_t ct = p.chunks_total;
+  const unsigned char* Ag = planes + ((int64_t)(row0 / BT) * ct + c_begin) * (2 * (int64_t)HALF) + 3072 * wave;
+  const unsigned char* Bg = planes + ((int64_t)(col0 / BT) * ct + c_begin) * (2 * (int64_t)HALF) + 3072 * wave;
+  const unsigned lds0 = (unsigned)(uintptr_t)DMDX_LDS_PTR(lds);
+  const unsigned voff = 16u * (unsigned)lane;   // the one per-lane offset: of every LDS-DMA piece (the hardware adds it on the LDS side itself)
+  // (M0, the LDS-DMA's destination base, is written and read inside ONE statement, as in DMDX_DMA_OP4 and xty_dma.  It is
+  // not in the clobber list: the register is reserved, the compiler answers an "m0" clobber with -Winline-asm and
+  // ignores it.  It keeps no value in M0 across statements: on gfx950 neither its LDS instructions nor anything else it
+  // emits for this kernel reads M0 -- the only M0 in the kernel's assembly are these writes.)
+#define DMDX_PDMA3(ptr, la)                                                                        \
+  asm volatile("s_mov_b32 m0, %[la_]\n\ts_nop 0\n\t"                                               \
+               "global_load_lds_dwordx4 %[vo_], %[ap_]\n\t"                                        \
+               "global_load_lds_dwordx4 %[vo_], %[ap_] offset:1024\n\t"                            \
+               "global_load_lds_dwordx4 %[vo_], %[ap_] offset:2048"                                \
+               :: [la_] "s"(la), [ap_] "s"(ptr), [vo_] "v"(voff) : "memory")
+  auto issue = [&](int q, unsigned soff) {   // six pieces: this wave's quarter of group q into the stage at soff
+    const unsigned la = lds0 + soff + 3072u * (unsigned)wave;
+    DMDX_PDMA3(Ag + (int64_t)q * HALF, __builtin_amdgcn_readfirstlane(la));
+    DMDX_PDMA3(Bg + (int64_t)q * HALF, __builtin_amdgcn_readfirstlane(la + HALF));
+  };
+  // ---- operands: [plane h, m, l][block]; A blocks 2 wr + mi, B blocks 2 wc + ni of the group's four 32-column blocks
+  const unsigned char* const fa_base = lds + 2048 * wr + 16 * lane;
+  const unsigned char* const fb_base = lds + HALF + 2048 * wc + 16 * lane;
+  bf16x8 FA0[3][2], FB0[3][2], FA1[3][2], FB1[3][2];
+#define DMDX_PREAD(FA, FB, soff)                                                                   \
+  do {                                                                                             \
+    const unsigned char* a_ = fa_base + (soff);                                                    \
+    const unsigned char* b_ = fb_base + (soff);                                                    \
+    _Pragma("unroll") for (int pl_ = 0; pl_ < 3; ++pl_)                                            \
+        _Pragma("unroll") for (int b2_ = 0; b2_ < 2; ++b2_) {                                      \
+          FA[pl_][b2_] = *reinterpret_cast<const bf16x8*>(a_ + 4096 * pl_ + 1024 * b2_);           \
+          FB[pl_][b2_] = *reinterpret_cast<const bf16x8*>(b_ + 4096 * pl_ + 1024 * b2_);           \
+        }                                                                                          \
+  } while (0)
+#define DMDX_PMFMA(FA, pa, FB, pb)                                                                 \
+  do {                                                                                             \
+    _Pragma("unroll") for (int mi_ = 0; mi_ < 2; ++mi_)                                            \
+        _Pragma("unroll") for (int ni_ = 0; ni_ < 2; ++ni_) acc[mi_][ni_] =                        \
+            __builtin_amdgcn_mfma_f32_32x32x16_bf16(FA[pa][mi_], FB[pb][ni_], acc[mi_][ni_], 0, 0, 0); \
+  } while (0)
+  // the first 12 MFMAs of a group: h h (fresh: from the constant 0, the chunk's first products), h l, l h
+#define DMDX_PHEAD(FA, FB, fresh)                                                                  \
+  do {                                                                                             \
+    if (fresh) {                                                                                   \
+      _Pragma("unroll") for (int mi_ = 0; mi_ < 2; ++mi_)                                          \
+          _Pragma("unroll") for (int ni_ = 0; ni_ < 2; ++ni_) acc[mi_][ni_] =                      \
+              __builtin_amdgcn_mfma_f32_32x32x16_bf16(FA[0][mi_], FB[0][ni_], f32x16(0.f), 0, 0, 0); \
+    } else {                                                                                       \
+      DMDX_PMFMA(FA, 0, FB, 0);                                                                    \
+    }                                                                                              \
+    DMDX_PMFMA(FA, 0, FB, 2);                                                                      \
+    DMDX_PMFMA(FA, 2, FB, 0);                                                                      \
+  } while (0)
+  // the last 12: h m, m h, m m
+#define DMDX_PTAIL(FA, FB)                                                                         \
+  do {                                                                                             \
+    DMDX_PMFMA(FA, 0, FB, 1);                                                                      \
+    DMDX_PMFMA(FA, 1, FB, 0);                                                                      \
+    DMDX_PMFMA(FA, 1, FB, 1);                                                                      \
+  } while (0)
+  // The hand-over in the middle of group q (q + 1 exists): this wave's pieces of q + 1 have landed (those of q + 2, six,
+  // may still be in flight), its operand reads of q are done; behind the barrier that holds for every wave.  A raw
+  // barrier: the pieces in flight stay in flight across it.  Then the refill of q's stage and the operands of q + 1.
+#define DMDX_PHANDOVER(FA, FB, q)                                                                  \
+  do {                                                                                             \
+    if ((q) + 2 < ngroups) asm volatile("s_waitcnt vmcnt(6) lgkmcnt(0)\n\ts_barrier" ::: "memory"); \
+    else asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)\n\ts_barrier" ::: "memory");                  \
+    if ((q) + 3 < ngroups) issue((q) + 3, soff);                                                   \
+    soff = soff == 2u * STAGE ? 0u : soff + STAGE;                                                 \
+    DMDX_PREAD(FA, FB, soff);                                                                      \
+  } while (0)
+
+  const int ngroups = 2 * nchunks;
+  issue(0, 0u);
+  issue(1, STAGE);
+  if (ngroups > 2) {
+    issue(2, 2u * STAGE);
+    asm volatile("s_waitcnt vmcnt(12) lgkmcnt(0)\n\ts_barrier" ::: "memory");
+  } else {
+    asm volatile("s_waitcnt vmcnt(6) lgkmcnt(0)\n\ts_barrier" ::: "memory");
+  }
+  unsigned soff = 0u;   // the stage of the group in the MFMAs
+  DMDX_PREAD(FA0, FB0, soff);
+  for (int c = 0; c < nchunks; ++c) {
+    const int q = 2 * c;
+    DMDX_PHEAD(FA0, FB0, true);
+    DMDX_PHANDOVER(FA1, FB1, q);
+    DMDX_PTAIL(FA0, FB0);
+    DMDX_PHEAD(FA1, FB1, false);
+    if (c + 1 < nchunks) {
+      DMDX_PHANDOVER(FA0, FB0, q + 1);
+    }
+    DMDX_PTAIL(FA1, FB1);
+    // (one chunk per MFMA chain, as in tn_unit: the bf16 MFMA cuts its sum below the ulp of a grown accumulator)
+#pragma unroll
+    for (int mi = 0; mi < 2; ++mi)
+#pragma unroll
+      for (int ni = 0; ni < 2; ++ni) {
+        acc2[mi][ni] += acc[mi][ni];
+#pragma unroll
+        for (int r = 0; r < 16; ++r) acc[mi][ni][r] = 0.f;
+      }
+  }
+#undef DMDX_PHANDOVER
+#undef DMDX_PTAIL
+#undef DMDX_PHEAD
+#undef DMDX_PMFMA
+#undef DMDX_PREAD
+#undef DMDX_PDMA3
+  // ---- the verdict (tn_unit's): a NaN in the unit's result <= a non-finite input fed it: nothing is committed here
+  bool nan_ = false;
+#pragma unroll
+  for (int mi = 0; mi < 2; ++mi)
+#pragma unroll
+    for (int ni = 0; ni < 2; ++ni)
+#pragma unroll
+      for (int r = 0; r < 16; ++r) nan_ |= bf16split::alarm(acc[mi][ni][r] + acc2[mi][ni][r]);
+  if (__builtin_amdgcn_ballot_w64(nan_) != 0ull) *alarm_word = 1;
+  __syncthreads();   // (every LDS-DMA piece has been waited for: nothing in flight)
+  if (__builtin_amdgcn_readfirstlane(*alarm_word) != 0) {
+    // the mark: a committed tile of a unit without alarm holds no NaN anywhere
+    if (tid == 0) __builtin_nontemporal_store(__builtin_nan(""), Pt);
+    return;
+  }
+  commit();
+}
+
 // XCD-aware unit order: groups of 512 consecutive blocks; the 64 blocks of a group that land on
 // one XCD (blockIdx % 8) take 64 consecutive units (an 8 x 8 patch of tiles).  `b` counts from
 // the start of a range whose first block index is a multiple of 8.
@@ -902,7 +1098,9 @@ __device__ __forceinline__ int xcd_unit(int b, int total) {
 // D (+)= sum_j A_j^T B_j over a batch of row blocks (TnBatch); p carries what the blocks share
 // (shape of D, tiles, P).  SYRK: A_j == B_j, triangle tiles.  A single product is the batch of one
 // block: unit_begin = {0, units}, slab_begin = {0, nsplit}, no padding.
-// PL: the plane k-step of tn_unit (the 128 x 128 SYRK tiles of K1, unless DMDX_K1_ARITH=f32).
+// PL: the plane k-step of tn_unit (the 128 x 128 SYRK tiles of K1, unless DMDX_K1_ARITH=f32).  PL = 2 / 3 (aligned
+// blocks with stored planes, dmdx_syrk_blocks_planes_f32): the plane-fed fast pass, tn_unit_planes, and the launch
+// behind it that runs the class-safe pass of the units it marked.
 template <bool DMA, int SK = 0, int H16 = 0, int PL = 0>
 __global__ __launch_bounds__(NTH, 2) void syrk_batch_kernel(TnParams p, TnBatch bt) {
   constexpr int TM = SK ? 32 * SK + 16 * H16 : BT;
@@ -936,7 +1134,14 @@ __global__ __launch_bounds__(NTH, 2) void syrk_batch_kernel(TnParams p, TnBatch 
     c0 = __builtin_amdgcn_s_memtime();
     r0 = __builtin_amdgcn_s_memrealtime();
   }
-  tn_unit<DMA, DMDX_TN_ABL, SK, H16, PL>(p, split, ta * TM, tb * BT, Pt, lds);
+  if constexpr (PL == 2) {   // the fast pass on the stored planes; a unit that raised the alarm leaves its mark
+    tn_unit_planes(p, bt.planes[j], split, ta * TM, tb * BT, Pt, lds);
+  } else if constexpr (PL == 3) {   // the rerun launch behind PL = 2: the class-safe pass of the marked units alone
+    if (!bf16split::alarm((float)__builtin_nontemporal_load(Pt))) return;
+    tn_unit<DMA, DMDX_TN_ABL, SK, H16, PL>(p, split, ta * TM, tb * BT, Pt, lds);
+  } else {
+    tn_unit<DMA, DMDX_TN_ABL, SK, H16, PL>(p, split, ta * TM, tb * BT, Pt, lds);
+  }
   if (bt.clk != nullptr) {
     const unsigned long long c1 = __builtin_amdgcn_s_memtime(), r1 = __builtin_amdgcn_s_memrealtime();
     if (wave0 == 0 && lane_now() == 0) {
@@ -1122,9 +1327,17 @@ size_t batch_ws(const int64_t* K, int nblocks, int64_t nrow, int64_t ncol, int s
 // The one launch path of all four entry points.  Nothing is refused here: the entry points have
 // put the leading dimensions and the workspace (batch_ws) through tn_refusal before the first launch.
 // probe: the launches feed dmdx_set_clock_probe (include/dmdx.h lists which entry points do).
+// planes: null, or the first plane image of every block (dmdx_syrk_blocks_planes_f32 alone: a Gram of full tiles whose
+// blocks are all aligned, not under DMDX_K1_ARITH=f32): the fast pass of K1 streams them (PL = 2).
+inline bool tn_block_aligned(const float* A, int64_t la) { return la % 4 == 0 && dmdx_aligned16(A) && la < (int64_t(1) << 22); }
+inline bool k1_arith_f32() {   // A/B knob: K1's full tiles on the fp32 MFMA (rounding only)
+  const char* arith = getenv("DMDX_K1_ARITH");
+  return arith != nullptr && strcmp(arith, "f32") == 0;
+}
 int run_batch(const float* const* A, const int64_t* lda, const float* const* B, const int64_t* ldb,
               const int64_t* K, int nblocks, int64_t nrow, int64_t ncol, int syrk, double* D64, int64_t ld64,
-              float* D32, int64_t ld32, int accumulate, void* ws, hipStream_t stream, bool probe) {
+              float* D32, int64_t ld32, int accumulate, void* ws, hipStream_t stream, bool probe,
+              const unsigned char* const* planes = nullptr) {
   for (int j0 = 0; j0 < nblocks; j0 += MAXB) {
     const int nb = group_len(nblocks, j0);
     TnBatch bt{};
@@ -1148,8 +1361,8 @@ int run_batch(const float* const* A, const int64_t* lda, const float* const* B, 
       const int u = pl.nsplit * pl.ntiles;
       units += (j + 1 < nb) ? (u + 511) / 512 * 512 : u;
       slabs += pl.nsplit;
-      aligned = aligned && (la % 4 == 0) && (lb % 4 == 0) && dmdx_aligned16(A[j0 + j]) &&
-                dmdx_aligned16(B[j0 + j]) && la < (int64_t(1) << 22) && lb < (int64_t(1) << 22);
+      aligned = aligned && tn_block_aligned(A[j0 + j], la) && tn_block_aligned(B[j0 + j], lb);
+      bt.planes[j] = planes ? planes[j0 + j] : nullptr;
     }
     bt.unit_begin[nb] = units;
     bt.slab_begin[nb] = slabs;
@@ -1162,9 +1375,13 @@ int run_batch(const float* const* A, const int64_t* lda, const float* const* B, 
     p.P = reinterpret_cast<double*>(ws);
     const dim3 grid((unsigned)units);
     // K1's full tiles run the bf16-plane k-step; DMDX_K1_ARITH=f32 keeps them on the fp32 MFMA (A/B, rounding only)
-    const char* arith = getenv("DMDX_K1_ARITH");
-    if (pl.tm == BT && pl.syrk && !(arith != nullptr && strcmp(arith, "f32") == 0)) {
-      if (aligned) hipLaunchKernelGGL((syrk_batch_kernel<true, 0, 0, 1>), grid, dim3(NTH), 0, stream, p, bt);
+    if (pl.tm == BT && pl.syrk && !k1_arith_f32()) {
+      if (aligned && planes) {
+        hipLaunchKernelGGL((syrk_batch_kernel<true, 0, 0, 2>), grid, dim3(NTH), 0, stream, p, bt);
+        DMDX_LAUNCH_CHECK();
+        bt.clk = nullptr;   // (the probe counts the fast launch's workgroups)
+        hipLaunchKernelGGL((syrk_batch_kernel<true, 0, 0, 3>), grid, dim3(NTH), 0, stream, p, bt);
+      } else if (aligned) hipLaunchKernelGGL((syrk_batch_kernel<true, 0, 0, 1>), grid, dim3(NTH), 0, stream, p, bt);
       else hipLaunchKernelGGL((syrk_batch_kernel<false, 0, 0, 1>), grid, dim3(NTH), 0, stream, p, bt);
     } else
     switch (pl.tm) {
@@ -1659,6 +1876,82 @@ int dmdx_syrk_blocks_f32(const float* const* X, const int64_t* m, const int64_t*
                                        dmdx_syrk_blocks_workspace_bytes(m, nblocks, n)));
   return run_batch(X, ldx, X, ldx, m, nblocks, n, n, 1, G64, ldg, G32, ldg32, accumulate, workspace,
                    (hipStream_t)stream, true);
+}
+
+size_t dmdx_syrk_planes_bytes(const int64_t* m, int nblocks, int64_t n) { return plane_image::total_bytes(m, nblocks, n); }
+
+// Every LDS-DMA address of the plane-fed pass (tn_unit_planes: the groups 2 c_begin .. 2 c_end - 1 of the unit's two
+// panels, 12 288 bytes each) lies in [0, planes_bytes), block j's first image at off[j]: walked on the host over the
+// plan the launch will use, first and last panel, every K-split.  Not an independent bound per block: it recomputes
+// make_plan and group_offset as the kernel does, so what it can catch is a plan whose chunks or panels are not those
+// the images were sized with, and a buffer shorter than the blocks' sum.
+static bool planes_dma_inside(const int64_t* m, int nblocks, int64_t n, const size_t* off, size_t planes_bytes) {
+  for (int j0 = 0; j0 < nblocks; j0 += MAXB) {
+    const int nb = group_len(nblocks, j0);
+    for (int j = j0; j < j0 + nb; ++j) {
+      const Plan pl = make_plan(m[j], n, n, 1, nb);
+      if (pl.chunks_total != plane_image::chunks_of(m[j]) || pl.ntr != plane_image::panels_of(n)) return false;
+      for (const int64_t pn : {(int64_t)0, (int64_t)pl.ntr - 1})
+        for (int s = 0; s < pl.nsplit; ++s) {
+          const int64_t cb = (int64_t)s * pl.chunks_per_split, ce = std::min<int64_t>(cb + pl.chunks_per_split, pl.chunks_total);
+          if (ce <= cb) continue;
+          const int64_t first = plane_image::group_offset(pn, pl.chunks_total, 2 * cb);
+          const int64_t end = plane_image::group_offset(pn, pl.chunks_total, 2 * ce - 1) + plane_image::kHalfBytes;
+          if (first < 0 || end < first || off[j] > planes_bytes || (size_t)end > planes_bytes - off[j]) return false;
+        }
+    }
+  }
+  return true;
+}
+
+int dmdx_syrk_blocks_planes_f32(const float* const* X, const int64_t* m, const int64_t* ldx, int nblocks, int64_t n,
+                                double* G64, int64_t ldg, float* G32, int64_t ldg32, int accumulate, void* workspace,
+                                size_t workspace_bytes, void* planes, size_t planes_bytes, void* stream) {
+  DMDX_CHECK_ARG(X && m && ldx && G64 && nblocks >= 1, "syrk_blocks_planes: null pointer or no blocks");
+  DMDX_CHECK_ARG(n >= 1 && n < (1 << 30) && ldg >= n && (!G32 || ldg32 >= n), "syrk_blocks_planes: bad n / ldg");
+  for (int j = 0; j < nblocks; ++j)
+    DMDX_CHECK_ARG(X[j] && m[j] >= 1 && ldx[j] >= 1, "syrk_blocks_planes: bad block %d", j);
+  const size_t ws_need = dmdx_syrk_blocks_workspace_bytes(m, nblocks, n);
+  DMDX_REFUSE_BEFORE_LAUNCH(tn_refusal("syrk_blocks_planes", ldx, ldx, nblocks, LD_LIMIT_BLOCKS, workspace, workspace_bytes,
+                                       ws_need));
+  // the plane buffer: present, large enough for every block (a size that saturated fits nothing), and apart from
+  // everything else the call reads or writes
+  const size_t need = dmdx_syrk_planes_bytes(m, nblocks, n);
+  if (planes == nullptr || need == SIZE_MAX || planes_bytes < need) {
+    dmdx_set_error("syrk_blocks_planes: plane buffer %zu bytes < required %zu", planes ? planes_bytes : (size_t)0, need);
+    return DMDX_E_WORKSPACE;
+  }
+  DMDX_CHECK_ARG(((uintptr_t)planes & 15u) == 0, "syrk_blocks_planes: the plane buffer is not 16-byte aligned");
+  bool apart = plane_image::disjoint(planes, need, workspace, ws_need) &&
+               plane_image::disjoint(planes, need, G64, sizeof(double) * (size_t)((n - 1) * ldg + n)) &&
+               (!G32 || plane_image::disjoint(planes, need, G32, sizeof(float) * (size_t)((n - 1) * ldg32 + n)));
+  for (int j = 0; j < nblocks; ++j)   // (ldx < 2^24, n < 2^30: the extent fits 64 bits)
+    apart = apart && plane_image::disjoint(planes, need, X[j], sizeof(float) * (size_t)((n - 1) * ldx[j] + m[j]));
+  DMDX_CHECK_ARG(apart, "syrk_blocks_planes: the plane buffer overlaps X, G or the workspace");
+  // the plane-fed pass takes what the aligned plane k-step takes today; anything else runs as dmdx_syrk_blocks_f32
+  // does and leaves the planes untouched
+  bool fed = n > 96 && !k1_arith_f32();
+  for (int j = 0; j < nblocks && fed; ++j) fed = tn_block_aligned(X[j], ldx[j]) && dmdx_plane_split_fits(m[j], n);
+  std::vector<size_t> off((size_t)nblocks);
+  std::vector<const unsigned char*> img((size_t)nblocks);
+  size_t at = 0;
+  for (int j = 0; j < nblocks; ++j) {
+    off[j] = at;
+    img[j] = reinterpret_cast<const unsigned char*>(planes) + at;
+    at += plane_image::block_bytes(m[j], n);
+  }
+  if (fed && !planes_dma_inside(m, nblocks, n, off.data(), planes_bytes)) {
+    dmdx_set_error("syrk_blocks_planes: the unit plan reaches outside the plane buffer");
+    return DMDX_E_INVALID;
+  }
+  if (!fed)
+    return run_batch(X, ldx, X, ldx, m, nblocks, n, n, 1, G64, ldg, G32, ldg32, accumulate, workspace,
+                     (hipStream_t)stream, true);
+  for (int j = 0; j < nblocks; ++j)
+    if (const int rc = dmdx_plane_split_launch(X[j], m[j], n, ldx[j], const_cast<unsigned char*>(img[j]), (hipStream_t)stream))
+      return rc;
+  return run_batch(X, ldx, X, ldx, m, nblocks, n, n, 1, G64, ldg, G32, ldg32, accumulate, workspace,
+                   (hipStream_t)stream, true, img.data());
 }
 
 size_t dmdx_gemm_tn_workspace_bytes(int64_t K, int64_t na, int64_t nb) {

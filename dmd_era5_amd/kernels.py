@@ -19,6 +19,7 @@ the GPU is missing.
 from __future__ import annotations
 
 import ctypes
+import os
 
 import numpy as np
 import torch
@@ -139,6 +140,7 @@ class HipKernels:
         if not torch.cuda.is_available():
             raise _lib.DmdxError("no HIP device visible: the dmdx kernels have no CPU fallback")
         self._ws: dict[int, torch.Tensor] = {}
+        self._planes: dict[int, torch.Tensor] = {}   # K1's bf16 planes (_plane_groups), cached like the workspaces
         # when set to a list, every launch is bracketed by HIP events on the launch
         # stream and (name, shape, start, stop) is appended (bench.py reads these)
         self.events: list | None = None
@@ -158,10 +160,13 @@ class HipKernels:
         self.events.append((name, shape, e0, e1))
         return rc
 
-    def _workspace(self, device: torch.device, nbytes: int) -> torch.Tensor:
+    def _ws_key(self, device: torch.device) -> tuple:
         # one scratch buffer per (device, stream): launches on different streams may overlap
         idx = device.index if device.index is not None else torch.cuda.current_device()
-        key = (idx, torch.cuda.current_stream(device).cuda_stream if device.type == "cuda" else 0)
+        return (idx, torch.cuda.current_stream(device).cuda_stream if device.type == "cuda" else 0)
+
+    def _workspace(self, device: torch.device, nbytes: int) -> torch.Tensor:
+        key = self._ws_key(device)
         ws = self._ws.get(key)
         if ws is None or ws.numel() < nbytes:
             self._ws[key] = ws = torch.empty(max(nbytes, 1), dtype=torch.uint8, device=device)
@@ -190,21 +195,94 @@ class HipKernels:
         return planes
 
     def release_workspace(self) -> int:
-        """Drop the cached partial-tile workspaces (K1 / K3: 128 KB per (row block, K-split, tile)
+        """Drop the cached partial-tile workspaces and K1's bf16 planes (K1 / K3: 128 KB per (row block, K-split, tile)
         of a launch -- 5.1 GB for cfg2's Gram, 9.5 GB for a cfg3 shard; they are kept between calls
         because re-allocating them costs more than the eigen stage).  Callers that are about to
         fill the HBM with something else (main() before a larger slice, the 227 GB cfg4 matrix)
         call this first.  Returns the number of bytes released."""
-        n = sum(int(w.numel()) for w in self._ws.values())
+        n = sum(int(w.numel()) for w in self._ws.values()) + sum(int(w.numel()) for w in self._planes.values())
         self._ws.clear()
+        self._planes.clear()
         return n
 
     # -- K1 -----------------------------------------------------------------
+    # HBM left free next to the plane buffer of a Gram call (the allocator's slack and whatever the caller allocates
+    # between the Gram and the next release_workspace()); the buffer also never takes more than half of what is free
+    PLANE_RESERVE_BYTES = 16 << 30
+
+    def _plane_groups(self, dev: torch.device, ms: list, n: int):
+        """The memory policy of K1's bf16 planes (6 bytes per value of X, made once per call, cached like the
+        workspaces): the groups [(a, b), ...] of whole row blocks that each run as one dmdx_syrk_blocks_planes_f32 call --
+        one group where the planes of the whole call fit half of what torch.cuda.mem_get_info reports free and leave
+        PLANE_RESERVE_BYTES of it (a cached buffer counts as free), else as few groups as fit, summed with ``accumulate`` --
+        or None for the entry without planes: a Gram of n <= 96 columns (the library runs those without planes), not one
+        block fits, or DMDX_K1_PLANES=0 (A/B knob, results unchanged)."""
+        if n <= 96 or os.environ.get("DMDX_K1_PLANES") == "0":
+            return None
+
+        # (the library's count of one block; a call's planes are the sum over its blocks)
+        per_block = [int(self._lib.dmdx_syrk_planes_bytes((ctypes.c_int64 * 1)(m), 1, n)) for m in ms]
+        have = self._planes.get(self._ws_key(dev))
+        have = int(have.numel()) if have is not None else 0
+        free = int(torch.cuda.mem_get_info(dev)[0]) + have
+        room = max(have, min(free - self.PLANE_RESERVE_BYTES, free // 2))
+        groups, a, held = [], 0, 0
+        for b, nbytes in enumerate(per_block):
+            if nbytes <= 0 or nbytes > room:
+                return None
+            if held + nbytes > room:
+                groups.append((a, b))
+                a, held = b, 0
+            held += nbytes
+        groups.append((a, len(ms)))
+        return groups
+
+    def _plane_buffer(self, dev: torch.device, nbytes: int) -> torch.Tensor:
+        key = self._ws_key(dev)
+        buf = self._planes.get(key)
+        if buf is None or buf.numel() < nbytes:
+            # The smaller buffer goes back to the DEVICE before the larger one is asked for, not into torch's cache:
+            # _plane_groups has counted it as free, and a block of this size that stays reserved next to its
+            # successor (55 GB next to 102 GB, cfg2 then a cfg3 shard) is of no use to any later allocation.
+            # Side effects, only on a call whose planes outgrow the cached buffer: empty_cache() hands EVERY unused
+            # cached block of the process back, so the allocations that follow pay the device allocator once more, and
+            # the call itself -- inside its event pair when events are recorded -- pays the release and the new buffer.
+            if self._planes.pop(key, None) is not None:
+                buf = None
+                torch.cuda.empty_cache()
+            self._planes[key] = buf = torch.empty(max(nbytes, 16), dtype=torch.uint8, device=dev)
+        return buf
+
+    def _gram(self, dev, ptr_list, ms, ld_list, n, G64, G32, accumulate: bool, without_planes):
+        """G64 (+)= sum_j X_j^T X_j [, G32] through dmdx_syrk_blocks_planes_f32 in the groups of _plane_groups;
+        ``without_planes()``: the call of the entry that takes none, where the policy says so.  -> (rc, entry)."""
+        groups = self._plane_groups(dev, ms, n) if max(ld_list) < (1 << 24) else None
+        if groups is None:
+            return without_planes()
+        L = self._lib
+        calls = []
+        for a, b in groups:
+            nb = b - a
+            m_arr = (ctypes.c_int64 * nb)(*ms[a:b])
+            calls.append((nb, (ctypes.c_void_p * nb)(*ptr_list[a:b]), m_arr, (ctypes.c_int64 * nb)(*ld_list[a:b]),
+                          int(L.dmdx_syrk_blocks_workspace_bytes(m_arr, nb, n)), int(L.dmdx_syrk_planes_bytes(m_arr, nb, n))))
+        ws = self._workspace(dev, max(c[4] for c in calls))
+        planes = self._plane_buffer(dev, max(c[5] for c in calls))
+        rc = 0
+        for i, (nb, p_arr, m_arr, ld_arr, _, _) in enumerate(calls):
+            rc = L.dmdx_syrk_blocks_planes_f32(p_arr, m_arr, ld_arr, nb, n, _ptr(G64), n, _ptr(G32), n,
+                                               int(accumulate or i > 0), _ptr(ws), ws.numel(), _ptr(planes),
+                                               planes.numel(), self._stream())
+            if rc:
+                break
+        return rc, "dmdx_syrk_blocks_planes_f32"
+
     def syrk(self, Xt: torch.Tensor, want32: bool = False, out: torch.Tensor | None = None):
         """G = X^T X (fp64, both triangles).  Xt: (n, m) fp32.  -> G64 [, G32].
 
         ``out``: an (n, n) fp64 tensor to accumulate into (G64 = out += X^T X): the
-        Gram of a row-blocked snapshot matrix is the sum over its blocks."""
+        Gram of a row-blocked snapshot matrix is the sum over its blocks.  A batch of one block through the
+        entry of ``syrk_blocks`` (same arithmetic as dmdx_syrk_f32, which still takes what that entry does not)."""
         m, n, ld = _check_mat(Xt, torch.float32, "syrk X")
         if out is not None:
             if out.shape != (n, n) or out.dtype != torch.float64 or not out.is_contiguous():
@@ -213,13 +291,15 @@ class HipKernels:
         else:
             G64 = torch.empty((n, n), dtype=torch.float64, device=Xt.device)
         G32 = torch.empty((n, n), dtype=torch.float32, device=Xt.device) if want32 else None
-        nbytes = self._lib.dmdx_syrk_workspace_bytes(m, n)
-        ws = self._workspace(Xt.device, nbytes)
-        rc = self._timed("syrk", (m, n), lambda: self._lib.dmdx_syrk_f32(
-            _ptr(Xt), m, n, ld, _ptr(G64), n, _ptr(G32), n, int(out is not None), _ptr(ws),
-            ws.numel(), self._stream()
-        ))
-        _lib.check(rc, "dmdx_syrk_f32")
+
+        def without_planes():
+            ws = self._workspace(Xt.device, self._lib.dmdx_syrk_workspace_bytes(m, n))
+            return self._lib.dmdx_syrk_f32(_ptr(Xt), m, n, ld, _ptr(G64), n, _ptr(G32), n, int(out is not None), _ptr(ws),
+                                           ws.numel(), self._stream()), "dmdx_syrk_f32"
+
+        rc, entry = self._timed("syrk", (m, n), lambda: self._gram(
+            Xt.device, [Xt.data_ptr()], [m], [ld], n, G64, G32, out is not None, without_planes))
+        _lib.check(rc, entry)
         return (G64, G32) if want32 else G64
 
     def syrk_blocks(self, blocks, out: torch.Tensor | None = None) -> torch.Tensor:
@@ -238,14 +318,20 @@ class HipKernels:
         else:
             G64 = torch.empty((n, n), dtype=torch.float64, device=dev)
         nb = len(blocks)
-        ptrs = (C.c_void_p * nb)(*[B.data_ptr() for B in blocks])
-        ms = (C.c_int64 * nb)(*[s[0] for s in shapes])
-        lds = (C.c_int64 * nb)(*[s[2] for s in shapes])
-        ws = self._workspace(dev, self._lib.dmdx_syrk_blocks_workspace_bytes(ms, nb, n))
-        rc = self._timed("syrk_blocks", (sum(s[0] for s in shapes), n, nb), lambda: self._lib.dmdx_syrk_blocks_f32(
-            ptrs, ms, lds, nb, n, _ptr(G64), n, None, 0, int(out is not None), _ptr(ws), ws.numel(), self._stream()
-        ))
-        _lib.check(rc, "dmdx_syrk_blocks_f32")
+
+        def without_planes():
+            ptrs = (C.c_void_p * nb)(*[B.data_ptr() for B in blocks])
+            ms = (C.c_int64 * nb)(*[s[0] for s in shapes])
+            lds = (C.c_int64 * nb)(*[s[2] for s in shapes])
+            ws = self._workspace(dev, self._lib.dmdx_syrk_blocks_workspace_bytes(ms, nb, n))
+            return self._lib.dmdx_syrk_blocks_f32(ptrs, ms, lds, nb, n, _ptr(G64), n, None, 0, int(out is not None),
+                                                  _ptr(ws), ws.numel(), self._stream()), "dmdx_syrk_blocks_f32"
+
+        # (the pre-split of the planes is part of the call: inside the event pair)
+        rc, entry = self._timed("syrk_blocks", (sum(s[0] for s in shapes), n, nb), lambda: self._gram(
+            dev, [B.data_ptr() for B in blocks], [s[0] for s in shapes], [s[2] for s in shapes], n, G64, None,
+            out is not None, without_planes))
+        _lib.check(rc, entry)
         return G64
 
     # -- K3 -----------------------------------------------------------------

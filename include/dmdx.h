@@ -206,6 +206,27 @@ int dmdx_syrk_blocks_f32(const float* const* X, const int64_t* m, const int64_t*
                          int64_t n, double* G64, int64_t ldg, float* G32, int64_t ldg32,
                          int accumulate, void* workspace, size_t workspace_bytes, void* stream);
 
+/* The same Gram with the bf16 planes of X made ONCE per call instead of in every tile (K1's full 128 x 128 tiles
+ * split every fp32 value into three bf16 planes; a value is staged by about 138 wave passes per call at n = 8760).
+ * A streaming kernel writes the planes of every block into `planes` (images of 128 columns x 32 rows x 3 planes:
+ * csrc/plane_image.h), K1's fast pass reads its MFMA operands from them.  Same planes, same MFMAs in the same order,
+ * same folds: G64 and G32 are those of dmdx_syrk_blocks_f32 in every bit, non-finite input included (a work unit whose
+ * result holds a NaN runs again from X on the class-safe planes, in a second launch over the marked units).
+ * dmdx_syrk_planes_bytes: sum over the blocks of ceil(n / 128) ceil(m[j] / 32) 24 576 bytes; 0 for a bad argument,
+ * SIZE_MAX where the sum does not fit.  planes: a device buffer of at least that many bytes, 16-byte aligned, apart
+ * from X, G64, G32 and the workspace; its contents after the call are unspecified.  The workspace is that of
+ * dmdx_syrk_blocks_f32 (dmdx_syrk_blocks_workspace_bytes).
+ * The planes are used when n > 96, every block is 16-byte aligned with ldx % 4 == 0 and ldx < 2^22, and
+ * DMDX_K1_ARITH is not f32; any other call runs exactly as dmdx_syrk_blocks_f32 does and does not touch `planes`.
+ * Refused before the first launch, outputs, workspace and planes untouched: what dmdx_syrk_blocks_f32 refuses; a
+ * null, misaligned or too small plane buffer (DMDX_E_WORKSPACE when null or small); a plane buffer that overlaps X, G or
+ * the workspace; a unit plan that would read outside the plane buffer (checked on the host for every call). */
+size_t dmdx_syrk_planes_bytes(const int64_t* m, int nblocks, int64_t n);
+int dmdx_syrk_blocks_planes_f32(const float* const* X, const int64_t* m, const int64_t* ldx, int nblocks,
+                                int64_t n, double* G64, int64_t ldg, float* G32, int64_t ldg32,
+                                int accumulate, void* workspace, size_t workspace_bytes, void* planes,
+                                size_t planes_bytes, void* stream);
+
 /* ---- K3: C = A^T B, A: K x na, B: K x nb (both K-contiguous) ---------------
  * Z = X^T Y of the randomized range finder (extmath.py:351, `A.T @ Q`) and
  * B = Q^T X (extmath.py:577).  C64: na x nb fp64 (ldc); C32 nullable.  */
