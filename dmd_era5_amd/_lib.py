@@ -145,6 +145,10 @@ SIGNATURES = {
     "dmdx_gap_fill_max_k": (C.c_int, []),
     "dmdx_gap_fill_workspace_bytes": (_sz, [_i64, _i64, _i64]),
     "dmdx_gap_fill_f32": (C.c_int, [_p, _i64, _i64, _i64, _p, _i64, _i64, _p, _p, _p, _i64, _p, _i64, _p, _p, _sz, _p]),
+    "dmdx_mk_max_n": (C.c_int, []),
+    "dmdx_sen_max_ranks": (C.c_int, []),
+    "dmdx_mk_stats_f32": (C.c_int, [_p, _i64, _i64, _i64, _p, _i64, _p]),
+    "dmdx_sen_slopes_f32": (C.c_int, [_p, _i64, _i64, _i64, _p, _p, _i64, C.c_int, _p, _i64, _p]),
     "dmdx_pack_triu_f64": (C.c_int, [_p, _i64, _i64, _p, _p]),
     "dmdx_unpack_triu_f64": (C.c_int, [_p, _i64, _p, _i64, _p]),
     "dmdx_exp_basis": (C.c_int, [_p, _p, _i64, _i64, _p, _p, C.c_int, _p]),

@@ -181,5 +181,15 @@ class Periods:
     def n_periods(self) -> int:
         return int(self.bounds.shape[0]) - 1
 
+    def period_years(self) -> np.ndarray:
+        """The decimal year of the first stamp of every period, (P,) fp64 (2001.0 for 2001-01-01T00, the fraction by
+        the length of its own year): the time coordinate ``MannKendall.fit`` takes.  A ValueError without ``times``."""
+        if self.times is None:
+            raise ValueError(f"{type(self).__name__}.period_years: fitted without times: the periods have no dates")
+        t = self.times[np.asarray(self.bounds[:-1]).astype(np.int64)].astype("datetime64[ns]")
+        year = t.astype("datetime64[Y]")
+        start, end = year.astype("datetime64[ns]"), (year + 1).astype("datetime64[ns]")
+        return 1970.0 + year.astype(np.int64) + (t - start).astype(np.int64) / (end - start).astype(np.int64)
+
     def _when(self, offsets: list, scale: int, who: str) -> list:
         return when(offsets, self.bounds[:-1], scale, self.times, f"{type(self).__name__}.{who}")

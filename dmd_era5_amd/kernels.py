@@ -1473,6 +1473,59 @@ class HipKernels:
         _lib.check(rc, "dmdx_gap_fill_f32")
         return change
 
+    # -- K32 ----------------------------------------------------------------
+    @property
+    def mk_max_n(self) -> int:
+        """The longest series (time points per row) of :meth:`mk_stats` and :meth:`sen_slopes`."""
+        return int(self._lib.dmdx_mk_max_n())
+
+    @property
+    def sen_max_ranks(self) -> int:
+        return int(self._lib.dmdx_sen_max_ranks())
+
+    def _mk_series(self, Yt: torch.Tensor, who: str) -> tuple[int, int, int]:
+        m, n, ldy = _check_mat(Yt, torch.float32, f"{who} Y")
+        if not 1 <= n <= self.mk_max_n:
+            raise _lib.DmdxError(f"{who}: {n} time points, 1 .. {self.mk_max_n} asked for")
+        return m, n, ldy
+
+    def mk_stats(self, Yt: torch.Tensor, out: torch.Tensor | None = None) -> torch.Tensor:
+        """The Mann-Kendall statistics of every row of a series block.  Yt: (n, m) fp32 (any row stride), n <=
+        ``mk_max_n`` time points; a point counts if it is finite -> (4, m) int32: the valid points v, S = sum over the
+        pairs a < b of sgn(y_b - y_a), the tied pairs E, and the tie term G of Var(S), the sum over the tie groups of
+        g (g - 1) (2 g + 5).  ``out``: a (4, m) int32 view to write into (inner stride 1).  One read of Yt."""
+        m, n, ldy = self._mk_series(Yt, "mk_stats")
+        res, ldo = _out_view(out, m, 4, torch.int32, Yt.device, "mk_stats", " int32")
+        rc = self._timed("mk_stats", (m, n), lambda: self._lib.dmdx_mk_stats_f32(
+            _ptr(Yt), m, n, ldy, _ptr(res), ldo, self._stream()
+        ))
+        _lib.check(rc, "dmdx_mk_stats_f32")
+        return res
+
+    def sen_slopes(self, Yt: torch.Tensor, coord, ranks: torch.Tensor, out: torch.Tensor | None = None) -> torch.Tensor:
+        """Order statistics of the pairwise slopes of every row of a series block.  Yt as :meth:`mk_stats`; ``coord``:
+        the n time coordinates (host numbers, finite, strictly ascending); ``ranks``: (J, m) int32 on the device
+        (inner stride 1), J <= ``sen_max_ranks``, 0-based ranks per row among the N = v (v - 1) / 2 slopes
+        fp32(fp64(y_b - y_a) / (t_b - t_a)) of the valid points, ordered by the key of their bits (-0.0 before +0.0)
+        -> (J, m) fp32: the slope of that rank with its bits, NaN where the rank lies outside 0 .. N - 1.  ``out``: a
+        (J, m) fp32 view to write into.  One read of Yt, no workspace."""
+        who = "sen_slopes"
+        m, n, ldy = self._mk_series(Yt, who)
+        tc = np.asarray(coord, dtype=np.float64).reshape(-1)
+        if tc.shape[0] != n or not np.isfinite(tc).all() or not (np.diff(tc) > 0).all():
+            raise _lib.DmdxError(f"{who}: coord must hold {n} finite, strictly ascending numbers")
+        if not isinstance(ranks, torch.Tensor) or ranks.dim() != 2 or not 1 <= int(ranks.shape[0]) <= self.sen_max_ranks:
+            raise _lib.DmdxError(f"{who}: ranks must be a (J, {m}) int32 tensor, J in 1 .. {self.sen_max_ranks}")
+        J = int(ranks.shape[0])
+        ldr = _check_field(ranks, m, J, torch.int32, Yt.device, who, "ranks", " int32")
+        res, ldo = _out_view(out, m, J, torch.float32, Yt.device, who)
+        host = (ctypes.c_double * n)(*tc.tolist())
+        rc = self._timed("sen_slopes", (m, n, J), lambda: self._lib.dmdx_sen_slopes_f32(
+            _ptr(Yt), m, n, ldy, host, _ptr(ranks), ldr, J, _ptr(res), ldo, self._stream()
+        ))
+        _lib.check(rc, "dmdx_sen_slopes_f32")
+        return res
+
     # -- K6 -----------------------------------------------------------------
     def delay_shift_sum(self, G64: torch.Tensor, d: int, want32: bool = False):
         """Gd[i, j] = sum_{k<d} G[i+k, j+k]."""

@@ -1194,6 +1194,47 @@ int dmdx_gap_fill_f32(const float* U, int64_t m, int64_t k, int64_t ldu, const f
                       const float* mu, const float* sigma, const uint32_t* W, int64_t ldw, float* X, int64_t ldx,
                       double* change_row, void* workspace, size_t workspace_bytes, void* stream);
 
+/* ---- K32: the Mann-Kendall test and the Theil-Sen slope of every row of a row block ------------------------------------
+ * The trend of an index series (K27 / K29: one value per year and grid point) as it is reported: annual maxima, wet-day
+ * totals and spell lengths are skewed, tied and partly missing, so the slope is the median of all pairwise slopes, its
+ * confidence interval two other order statistics of them, and the significance a rank test.  Y is a row block as
+ * everywhere: n columns (time points) of m floats, ldy >= m, only read; 1 <= n <= dmdx_mk_max_n() = DMDX_MK_MAX_N (128).
+ *   tc     (HOST fp64) the n time coordinates, finite and strictly ascending; they travel by value.
+ *   rank   (device int32) J x m, ldr >= m, 1 <= J <= dmdx_sen_max_ranks() = DMDX_SEN_MAX_RANKS (4): 0-based ranks per row.
+ * A point of row i is VALID iff it is finite (K20's test of the bit pattern: NaN and +-Inf are missing, as in K29);
+ * y_0 .. y_{v-1} and t_0 .. t_{v-1} are the valid points of the row in ascending time, N = v (v - 1) / 2 their pairs.
+ *
+ * dmdx_mk_stats_f32: the DMDX_MK_NQ = 4 planes, int32, at out[q ldo + i], ldo >= m, every value an exact integer:
+ *   0 v   the number of valid points
+ *   1 S   sum over a < b of sgn(y_b - y_a); IEEE comparisons: > gives +1, < gives -1, equal 0; -0.0 equals +0.0
+ *   2 E   the number of pairs a < b with y_a == y_b
+ *   3 G   sum over a of (c_a - 1) (2 c_a + 5), c_a the number of valid b (a included) with y_b == y_a: the sum over the
+ *         tie groups of g (g - 1) (2 g + 5), the tie term of Var(S); at most 128 127 261
+ *
+ * dmdx_sen_slopes_f32: for every pair a < b of valid points, in IEEE fp64: d = fp64(y_b) - fp64(y_a) (rounded once),
+ * h = t_b - t_a (rounded once, > 0), s = d / h (one correctly rounded division), e = fp32(s) (to nearest even).  Nothing
+ * is fused and nothing is flushed; no e is a NaN, +-Inf and denormals are ordinary values.  The N values are ordered by
+ * K25's key of the bit pattern (~u if the sign bit is set, else u | 0x80000000: a total order, -0.0 before +0.0):
+ * e_(0) <= ... <= e_(N-1).  out[j ldo + i] holds the bits of e_(rank[j ldr + i]) if 0 <= rank < N and the quiet NaN
+ * 0x7fc00000 otherwise.  Rounding to fp32 is monotone: this is the fp32 rounding of the same order statistic of the
+ * fp64 slopes.
+ *
+ * No atomics, no workspace, no allocation, no synchronisation.  The bits depend on the operands only -- not on the body
+ * that ran, the launch geometry or the alignment of Y or ldy.  Memory: only the logical elements of Y and rank are
+ * read; every logical element of out is written and nothing else.  No alignment is required beyond that of the elements.
+ * A refused call (DMDX_E_INVALID: a null Y, out, tc or rank; n outside 1 .. 128; J outside 1 .. 4; a negative size; m or
+ * a leading dimension >= 2^31; ldy, ldo or ldr < m; a pointer not aligned to its element; tc not finite or not strictly
+ * ascending; out overlapping Y or rank) names the entry point in dmdx_last_error(), has written nothing and made no HIP
+ * call.  m == 0 returns 0 after the checks without a launch. */
+#define DMDX_MK_MAX_N 128
+#define DMDX_MK_NQ 4
+#define DMDX_SEN_MAX_RANKS 4
+int dmdx_mk_max_n(void);
+int dmdx_sen_max_ranks(void);
+int dmdx_mk_stats_f32(const float* Y, int64_t m, int64_t n, int64_t ldy, int32_t* out, int64_t ldo, void* stream);
+int dmdx_sen_slopes_f32(const float* Y, int64_t m, int64_t n, int64_t ldy, const double* tc /* HOST, n */,
+                        const int32_t* rank /* device */, int64_t ldr, int J, float* out, int64_t ldo, void* stream);
+
 /* ---- upper triangle of a symmetric fp64 matrix <-> packed row by row ---------------------
  * packed[i (2n - i + 1) / 2 + (j - i)] = A[i][j], j >= i: what the Gram all-reduce of the
  * row-sharded path moves (n (n + 1) / 2 doubles instead of n^2).  unpack writes both triangles. */
